@@ -1,6 +1,6 @@
 """bench.py - training throughput (sessions/sec) of the HIP hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--model MSGIFSR|SRGNN|NISER|LESSR]
+    python bench.py --gpus N --steps K --warmup W [--model MSGIFSR|SRGNN|NISER|LESSR] [--full] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path over one batch: embedding gather -> session encoder ->
 fused full-catalog scoring + softmax-CE forward/backward -> fused Adam (dense over the item
@@ -15,11 +15,16 @@ item table is then row-sharded over the ranks (dist.VocabParallel, RCCL).  Defau
 global batch N * 512); `--global-batch 512` = strong scaling: the SAME 512 consecutive samples per step as one GPU,
 each rank encoding its contiguous slice of them (the reference's 512-sample loss semantics, train.py:94-101).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step).
+A plain run sets up, runs W warm-up steps, times exactly K steps, and prints that line; `--dump-outputs DIR` also writes
+what the last timed step computed (dump_outputs).  Everything else is measured only with `--full`:
   "roofline":     dominant kernel (fused scoring/CE backward launch) timed live with HIP events around a hipGraph of
                   back-to-back launches on the launch stream
   "cpu_baseline": the CPU oracle (pure-PyTorch restatement of the reference math) timed on the
-                  host cores of the same box on a bounded sample of the same workload.
+                  host cores of the same box on a bounded sample of the same workload
+  "fp32", "end_to_end", "quality": the fp32 side run, the DataLoader-inclusive loop, the trained Recall@20 / MRR@20
+  N > 1:          "strong" (the 512-session batch over the ranks), "correctness", per-exchange collective times
+and the timed region is repeated (--repeats, default 3 with --full, else 1).
 """
 import argparse
 import importlib
@@ -511,6 +516,32 @@ def run_timed(step, dev_batches, warmup, steps, repeats, dist, dev):
     return regions, loss
 
 
+DUMP_LIMIT = 64 * 10 ** 6          # bytes of all --dump-outputs files together
+DUMP_ROWS = 8192                   # rows kept of a longer parameter (the item table): a fixed, seeded sample
+
+
+def dump_outputs(outdir, model, loss):
+    """`--dump-outputs DIR`: what the timed step hands its caller after the last timed step - that step's loss and the
+    parameters it updated in place - as DIR/<name>.npy in float32 (loss.npy, param.<state_dict key>.npy).  A parameter of
+    more than DUMP_ROWS rows keeps the rows np.random.default_rng(0).choice(rows, DUMP_ROWS, replace=False), sorted
+    (param.<key>.rows_sample.npy): the same rows in every run of the same arguments."""
+    arrays = {'loss': loss.detach().float().cpu().reshape(1).numpy()}
+    for k, v in model.state_dict().items():
+        if not v.is_floating_point():
+            continue
+        a = v.detach().float().cpu().numpy()
+        if a.ndim >= 1 and a.shape[0] > DUMP_ROWS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_ROWS, replace=False))]
+            k += '.rows_sample'
+        arrays['param.' + k] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, 'outputs of %d bytes exceed %d' % (total, DUMP_LIMIT)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + '.npy'), a)
+    print('dumped %d arrays (%.1f MB) to %s' % (len(arrays), total / 1e6, outdir), file=sys.stderr)
+
+
 _JSON_OUT = None
 
 
@@ -519,6 +550,26 @@ def emit(obj):
     f = _JSON_OUT or sys.stdout
     f.write(json.dumps(obj) + '\n')
     f.flush()
+
+
+def headline(args, run, world, ranks_seen, graphed, strong_run):
+    """the result line of the main run; `--full` adds its side measurements (roofline, fp32, end_to_end, quality,
+    cpu_baseline) to it, a plain run leaves them None"""
+    V, d, B, Bg, strong, dt, ms = args.items, args.dim, run['B'], run['Bg'], run['strong'], run['dt'], run['ms']
+    return dict(metric='sessions/sec training, Yoochoose-1/64 batch 512', value=Bg * args.steps / dt,
+                unit='sessions/s', n_gpus=world, ranks_seen=ranks_seen, collectives=run['coll'], correctness=run['check'],
+                strong=strong_run,
+                steps=args.steps, warmup=args.warmup,
+                ms_per_step=dt / args.steps * 1e3, repeats_ms_per_step=ms, spread_ms=max(ms) - min(ms),
+                higher_is_better=True, scaling='strong' if strong else 'weak', vs_baseline=None,
+                dtype='f32' if args.precision == 'fp32' else 'bf16 (MFMA operands; fp32 accumulate, master weights, scoring)', data='synthetic', launch='hipGraph replay' if graphed else 'eager',
+                config=dict(workload='%s training step, synthetic Yoochoose-1/64 shape (V=%d items, d=%d, batch %d per GPU, '
+                                     'session length<=20%s)' % (args.model, V, d, B,
+                                                                ', order %d, dropout %g' % (args.order, args.dropout) if args.model == 'MSGIFSR' else ''),
+                            global_batch=Bg, parallelism=('item table row-sharded x%d (vocab-parallel scoring, RCCL all-gather/reduce-scatter), '
+                                         'encoder replicated, %s' % (world, 'each rank encodes its slice of one 512-session batch' if strong else 'each rank feeds its own batch')) if world > 1 else 'single GPU',
+                            final_loss=run['final_loss']),
+                full=bool(args.full), roofline=None, fp32=None, end_to_end=None, quality=None, cpu_baseline=None)
 
 
 class Env:
@@ -672,7 +723,7 @@ def run_job(env, args, precision, strong, Bg, B, n_batches, warm, steps, repeats
     job = make_job(env, args, precision, batches, dev_batches, strong)
     shard = job['shard']
     check = None
-    if shard is not None and world > 1:
+    if shard is not None and world > 1 and args.full:
         check = loss_check(env, args, job, dev_batches[0], first, strong)
     if not args.no_graph:
         capture_job(env, args, job, dev_batches)
@@ -694,13 +745,13 @@ def run_job(env, args, precision, strong, Bg, B, n_batches, warm, steps, repeats
         coll['bucket_copy_tasks'] = dict(getattr(shard, 'copy_tasks_last', {}))
     regions, loss = run_timed(job['step'], dev_batches, warm, steps, max(repeats, 1), dist if world > 1 or args.shard else None, dev)
     final_loss = loss.item()
-    if coll is not None and with_timing and (world > 1 or args.shard) and not args.step_only:
+    if coll is not None and with_timing and (world > 1 or args.shard) and args.full and not args.step_only:
         coll['timed'] = time_collectives(env, job, dev_batches)   # (eager steps next to a captured graph: also on the 1-rank rehearsal)
     dt = sorted(regions)[len(regions) // 2]              # median region
     ms = [r / steps * 1e3 for r in regions]
     nodes = job['gstep'].node_counts() if job['graphed'] and hasattr(job['gstep'], 'node_counts') else None
     return dict(job=job, batches=batches, samples=samples, dev_batches=dev_batches, coll=coll, check=check, dt=dt, ms=ms,
-                nodes=nodes, final_loss=final_loss, Bg=Bg, B=B, strong=strong, steps=steps)
+                nodes=nodes, loss=loss, final_loss=final_loss, Bg=Bg, B=B, strong=strong, steps=steps)
 
 
 def record_tape(args):
@@ -830,7 +881,14 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=3, help='timed regions of --steps steps each; value = the median region')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each; value = the median region (default 1; 3 with --full or --replay-rank)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline kernel timing, CPU baseline, fp32 side run, '
+                         'end-to-end loop, trained quality; N > 1: strong scaling, correctness bit, per-exchange times')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the loss and the parameters of the last timed step to DIR/<name>.npy '
+                         '(float32; the item table as a fixed sample of its rows; rank 0)')
     ap.add_argument('--model', default='MSGIFSR')
     ap.add_argument('--order', type=int, default=3)
     ap.add_argument('--dim', type=int, default=256)
@@ -868,6 +926,10 @@ def main():
     ap.add_argument('--of', type=int, default=None, help='world size of the job whose rank --replay-rank is replayed')
     ap.add_argument('--record-tape', default=None, help=argparse.SUPPRESS)      # (rank side of --replay-rank)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if (args.full or args.replay_rank is not None) else 1
+    if not args.full:
+        args.no_strong = args.no_cpu_baseline = args.no_fp32 = args.no_end_to_end = args.no_quality = True
     if args.step_only:
         args.no_cpu_baseline = args.no_fp32 = args.no_end_to_end = args.no_quality = True
         args.repeats = 1
@@ -940,6 +1002,8 @@ def main():
     batches, samples, dev_batches = main_run['batches'], main_run['samples'], main_run['dev_batches']
     coll, dt, ms, nodes, final_loss = main_run['coll'], main_run['dt'], main_run['ms'], main_run['nodes'], main_run['final_loss']
     strong = only_strong
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, main_run['loss'])
     # every rank contributes 1 through the job's own backend (RCCL): the sum is the number of ranks the collectives reach
     ranks_seen = 1
     if dist is not None:
@@ -988,6 +1052,8 @@ def main():
     if rank == 0 and args.step_only:
         emit(dict(step_only=True, ms_per_step=dt / args.steps * 1e3, value=Bg * args.steps / dt, launches=nodes,
                   final_loss=final_loss, collectives=coll))
+    elif rank == 0 and not args.full:
+        emit(headline(args, main_run, world, ranks_seen, graphed, strong_run))
     elif rank == 0:
         Vk = V if shard is None else shard.n_live      # rows of the catalog this rank scores
         kt = time_dominant_kernel(model, Bg, Vk, d, dev)
@@ -1037,21 +1103,8 @@ def main():
         cpu = None
         if not args.no_cpu_baseline and world == 1:        # the CPU baseline belongs to the N = 1 line (rank 0)
             cpu = cpu_baseline(args.model, samples, V, d, args.order, state, dropout=args.dropout)   # whole 512-session batches
-        scaling = 'strong' if strong else 'weak'
-        out = dict(metric='sessions/sec training, Yoochoose-1/64 batch 512', value=Bg * args.steps / dt,
-                   unit='sessions/s', n_gpus=world, ranks_seen=ranks_seen, collectives=coll, correctness=main_run['check'],
-                   strong=strong_run,
-                   steps=args.steps, warmup=args.warmup,
-                   ms_per_step=dt / args.steps * 1e3, repeats_ms_per_step=ms, spread_ms=max(ms) - min(ms),
-                   higher_is_better=True, scaling=scaling, vs_baseline=None,
-                   dtype='f32' if args.precision == 'fp32' else 'bf16 (MFMA operands; fp32 accumulate, master weights, scoring)', data='synthetic', launch='hipGraph replay' if graphed else 'eager',
-                   config=dict(workload='%s training step, synthetic Yoochoose-1/64 shape (V=%d items, d=%d, batch %d per GPU, '
-                                        'session length<=20%s)' % (args.model, V, d, B,
-                                                                   ', order %d, dropout %g' % (args.order, args.dropout) if args.model == 'MSGIFSR' else ''),
-                               global_batch=Bg, parallelism=('item table row-sharded x%d (vocab-parallel scoring, RCCL all-gather/reduce-scatter), '
-                                            'encoder replicated, %s' % (world, 'each rank encodes its slice of one 512-session batch' if strong else 'each rank feeds its own batch')) if world > 1 else 'single GPU',
-                               final_loss=final_loss),
-                   roofline=roof, fp32=fp32, end_to_end=e2e, quality=qual, cpu_baseline=cpu)
+        out = headline(args, main_run, world, ranks_seen, graphed, strong_run)
+        out.update(roofline=roof, fp32=fp32, end_to_end=e2e, quality=qual, cpu_baseline=cpu)
         emit(out)
     if dist is not None:
         dist.barrier()                      # the other ranks wait for rank 0's kernel timing / CPU baseline

@@ -425,7 +425,7 @@ def test_bench_two_ranks_over_gloo_on_one_gpu(dev):
     env = dict(os.environ, SREC_BENCH_BACKEND='gloo')
     env.pop('WORLD_SIZE', None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--repeats', '1', '--no-cpu-baseline'], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                        '--repeats', '1', '--no-cpu-baseline', '--full'], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
