@@ -939,6 +939,8 @@ class VocabParallel:
 
     def ops_flush(self):
         from . import ops
+        # not final: the step-scalar rider stays for the end of the backward - backward nodes still to run re-derive their
+        # dropout masks from the step counter it advances
         ops.flush_deferred()
 
     def sync_replicated_grads(self, params, optimizer=None):

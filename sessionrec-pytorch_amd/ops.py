@@ -686,7 +686,7 @@ def defer_slab_sum(part, out, ok=True, tall=False):
         return
     if not _DEFERRED:
         try:
-            torch.autograd.Variable._execution_engine.queue_callback(flush_deferred)
+            torch.autograd.Variable._execution_engine.queue_callback(_flush_final)
         except RuntimeError:                        # not inside a backward pass: nothing to wait for
             _launch_slab_sums([(part, out, tall)])
             return
@@ -696,8 +696,10 @@ def defer_slab_sum(part, out, ok=True, tall=False):
 
 
 # the optimizer's step-scalar launch as a rider of the END-of-backward slab-sum launch of a captured step (optim.FusedAdam.hyper_rider
-# puts the arguments of srec_adam_hyper_multi here before the backward pass; flush_deferred takes them along and notes which slots
-# it advanced in HYPER_DONE; FusedAdam.launch then skips its own launch)
+# puts the arguments of srec_adam_hyper_multi here before the backward pass; flush_deferred(final=True) takes them along and notes
+# which slots it advanced in HYPER_DONE; FusedAdam.launch then skips its own launch).  Only the end-of-backward flush may take it: the
+# kernel advances the (0, 0) step counter the dropout masks are keyed by, and a backward node that runs after a mid-backward flush
+# (dist.VocabParallel.bucket_ready) re-derives its forward's masks from that counter
 PENDING_HYPER = []
 HYPER_DONE = []
 
@@ -724,15 +726,22 @@ def _launch_slab_sums(tasks, rider=None):
                                         _ct.addressof(a_t), _ct.addressof(a_w), _ct.addressof(a_l), stream())
 
 
-def flush_deferred():
+def flush_deferred(final=False):
+    """launch the waiting slab sums.  final: the backward pass is complete (its end-of-backward callback, the optimizer) - only
+    then does the step-scalar rider leave with them; a flush from inside the backward leaves PENDING_HYPER alone"""
     if _DEFERRED:
         tasks = list(_DEFERRED)
         _DEFERRED.clear()
-        pend = PENDING_HYPER.pop() if PENDING_HYPER else None
-        del PENDING_HYPER[:]
+        pend = PENDING_HYPER.pop() if (final and PENDING_HYPER) else None
+        if final:
+            del PENDING_HYPER[:]
         _launch_slab_sums(tasks, pend[0] if pend is not None else None)
         if pend is not None:
             HYPER_DONE[:] = [pend[1]]
+
+
+def _flush_final():
+    flush_deferred(final=True)
 
 
 # ------------------------------------------------------------------------------------------ gradient arenas

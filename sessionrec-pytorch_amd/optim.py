@@ -173,7 +173,7 @@ class FusedAdam(torch.optim.Optimizer):
     def _work(self):
         """[(group idx, group, [(p, g, state)])] for every parameter that has a gradient now"""
         from . import ops
-        ops.flush_deferred()                  # (normally already done by the end-of-backward callback)
+        ops.flush_deferred(final=True)        # (normally already done by the end-of-backward callback)
         table, tgrad, _ = self._table_info()
         zero_ids = {}
         if self.model is not None and hasattr(self.model, 'zero_grad_params'):

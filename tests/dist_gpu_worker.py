@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from util import load_golden, pkg
+from util import load_golden, pkg, reseed
 
 
 def synth_samples(n, V, seed, max_len=20, mean_len=6.2):
@@ -64,12 +64,13 @@ def make_case(case):
             samples = long_ + short
     else:                                              # 'synth': MSGIFSR at a synthetic shape (C3: V 37484, d 256, order 3)
         V, d, K = case['V'], case['d'], case['order']
+        p = float(case.get('dropout', 0.0))            # feature, attention and lookup dropout (run_rank reseeds every step)
         samples = synth_samples(case['B'], V, 123, max_len=case.get('max_len', 20), mean_len=case.get('mean_len', 6.2))
         name = 'msgifsr'
 
         def build():
             torch.manual_seed(123)
-            return sp.MSGIFSR(V, 'synthetic', d, 1, dropout=0.0, order=K, extra=False, fusion=False)
+            return sp.MSGIFSR(V, 'synthetic', d, 1, dropout=p, order=K, extra=False, fusion=False)
 
     def collate(caps=None):
         if name.startswith(('niser', 'srgnn')):
@@ -134,6 +135,12 @@ def live_samples(samples, world, partial):
     return out
 
 
+def step_seed(step):
+    """the seed a case with dropout reseeds with before step `step` (0-based): a rank re-run from the tape draws the nonces
+    of the job's step with it"""
+    return 1000 + 17 * step
+
+
 def run_rank(rank, world, port, case, outdir):
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
@@ -173,6 +180,8 @@ def run_rank(rank, world, port, case, outdir):
             if group is not None:
                 group.tape = []
             D.STATS['count'] = D.STATS['bytes'] = 0
+            if case.get('dropout'):
+                reseed(step_seed(step))
             opt.zero_grad()
             loss = model.fused_loss(*inputs, labels)
             loss.backward()

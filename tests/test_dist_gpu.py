@@ -14,9 +14,10 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
-from dist_gpu_worker import build_on, digest, digest_rows, live_samples, make_case, rank_slice, run_rank, touched_items
+from dist_gpu_worker import (build_on, digest, digest_rows, live_samples, make_case, rank_slice, run_rank, step_seed,
+                             touched_items)
 from test_models_gpu import adam_close
-from util import close, pkg
+from util import close, pkg, reseed
 
 pytestmark = pytest.mark.gpu
 
@@ -409,6 +410,131 @@ def test_one_rank_of_the_job_replayed_under_hipgraph_capture(dev, tmp_path, name
         assert nodes['kernel'] > 10
     if name.startswith('msgifsr'):
         assert vp.early_launches >= 2 and vp._side is not None      # buckets 0 and 1 left from inside the (captured) backward
+
+
+@pytest.mark.parametrize('world,rank', [(2, 1), (8, 5)])
+def test_step_rider_in_a_captured_row_sharded_step_with_dropout(dev, tmp_path, monkeypatch, world, rank):
+    """The optimizer's step-scalar kernel rides in the END-of-backward slab-sum launch of a captured step
+    (optim.FusedAdam.hyper_rider).  It advances the (0, 0) step counter the dropout masks are keyed by, and in a row-sharded
+    step the gradient buckets flush the deferred slab sums from INSIDE the backward (dist.VocabParallel.bucket_ready): were the
+    rider to leave with such a flush, the GAT layers' backward and the sharded lookup's backward behind it would re-derive their
+    masks from the next step's counter.  Rank `rank` of a W-rank job with feature, attention and lookup dropout at the width
+    whose backward defers slab sums (bf16 matmuls, d = 128, order 3), re-run from its tape and captured twice - with and
+    without the rider - must land BIT-identically after several replays: table rows, replicated parameters, the losses of the
+    loss ring and the step counter, and - since under replay every collective's RESULT comes from the tape, so that the
+    parameters follow the job whatever this rank's own backward computed - what the captured step hands IN to each of its
+    collectives: the lookup's masked per-item gradient rows and the gradient buckets."""
+    D, G, ops, train, optim = pkg('dist'), pkg('graph'), pkg('ops'), pkg('train'), pkg('optim')
+    p = 0.2
+    # (512 sessions per rank, the benchmarked batch: the read-out head's weight gradients are split-K sums that wait for a flush)
+    case = dict(kind='synth', V=5000, d=128, order=3, B=512 * world, precision='bf16', dropout=p, steps=2, padded=True,
+                record=True)
+    replays = 5
+
+    class Tapped(D.ReplayGroup):
+        """under replay every collective's RESULT comes from the tape, so the rank's parameters follow the job whatever its own
+        backward computed: what the captured step hands IN to each collective is copied into static buffers by the graph
+        itself (they hold the last replay's inputs) - among them the lookup's per-item gradient rows and the gradient buckets"""
+
+        def load(self, tape):
+            self.taps = []
+            return super().load(tape)
+
+        def collective(self, kind, t):
+            if t.is_cuda and torch.cuda.is_current_stream_capturing():
+                keep = torch.empty_like(t)
+                keep.copy_(t)
+                self.taps.append((kind, keep))
+            return super().collective(kind, t)
+
+    try:
+        res = _launch(world, case, tmp_path)
+        job = res[rank]
+        assert job['lo'] > 0
+        ops.set_precision('bf16')
+        build, collate, samples, V = make_case(case)
+        mine, n = rank_slice(samples, world, rank, False)
+        caps = pkg('collate').default_caps(n, 20)
+        inputs, labels = collate(caps)(mine)
+        inputs, labels = [x.to(dev) for x in inputs], labels.to(dev)
+        runs = {}
+        for rider in ('0', '1'):
+            monkeypatch.setenv('SREC_HYPER_RIDER', rider)
+            model = build().to(dev)
+            group = Tapped(world, rank, dev).load(job['steps'][0]['tape'])
+            vp = D.VocabParallel(model, group=group, idx_cap=inputs[0].cap('uniq_items'))
+            vp.side_stream = True
+            opt = optim.FusedAdam(train.fix_weight_decay(model), lr=1e-3, weight_decay=1e-4, model=model, fuse_projection=True)
+            replicated = [q for q in model.parameters() if q is not model._table() and q.requires_grad]
+            model.train()
+            # step 1, eager, with the job's nonces (every collective input is checked against the tape)
+            reseed(step_seed(0))
+            ops.DROP_TAP = []
+            try:
+                opt.zero_grad()
+                loss = model.fused_loss(*inputs, labels)
+                loss.backward()
+                taps = ops.DROP_TAP
+            finally:
+                ops.DROP_TAP = None
+            vp.sync_replicated_grads(replicated, opt)
+            opt.step()
+            assert group.pos == len(group.kinds) and group.checked == len(group.kinds)
+            assert abs(loss.item() - job['steps'][0]['loss']) <= 1e-6 * max(1.0, abs(job['steps'][0]['loss']))
+            del loss
+            # dropout really is on: the GAT layer's feature masks drop ~p and scale the rest by 1 / (1 - p)
+            assert len(taps) >= 1
+            ms = taps[0]['ms']
+            assert abs((ms == 0).float().mean().item() - p) < 0.03
+            assert torch.allclose(ms[ms != 0], torch.full_like(ms[ms != 0], 1 / (1 - p)), rtol=1e-6)
+            # step 2: the eager warm-up lap draws the job's nonces of step 2 (its collective inputs are checked against the
+            # tape), then the capture; the replays run on the recorded collective results
+            group.load(job['steps'][1]['tape'])
+            reseed(step_seed(1))
+            early0 = vp.early_launches
+            gs = G.GraphedTrainStep(model, opt, inputs, labels, after_backward=lambda: vp.sync_replicated_grads(replicated, opt),
+                                    warmup=1)
+            assert group.pos == 2 * len(group.kinds) and group.checked == len(group.kinds)
+            # buckets 0 and 1 left from inside the backward: in the warm-up lap and in the capture
+            assert vp.early_launches - early0 >= 4 and vp._side is not None, (early0, vp.early_launches)
+            losses = [gs(inputs, labels).item() for _ in range(replays)]
+            torch.cuda.synchronize()
+            gs.check()
+            nodes = gs.node_counts()
+            runs[rider] = dict(table=model._table().detach()[:vp.n_live].clone(),
+                               params={k: q.detach().clone() for k, q in model.named_parameters() if q is not model._table()},
+                               losses=losses, ring=gs.loss_ring.clone(),
+                               counter=int(opt._hyper[(0, 0)]['counter'].item()), kernels=nodes['kernel'] if nodes else None,
+                               taps=[(k, t.clone()) for k, t in group.taps])
+            del gs, model, opt, vp
+            torch.cuda.empty_cache()
+        r0, r1 = runs['0'], runs['1']
+        diffs = {'table': (r0['table'] - r1['table']).abs().max().item()}
+        for k in r0['params']:
+            diffs[k] = (r0['params'][k] - r1['params'][k]).abs().max().item()
+        kinds = [k for k, _ in r0['taps']]
+        assert kinds == [k for k, _ in r1['taps']] and 'all_gather' in kinds and 'all_reduce:SUM' in kinds, kinds
+        for i, ((k, a), (_, b)) in enumerate(zip(r0['taps'], r1['taps'])):
+            diffs['collective %d (%s) input' % (i, k)] = (a.double() - b.double()).abs().max().item() if a.numel() else 0.0
+        worst = sorted(diffs.items(), key=lambda kv: -kv[1])[:6]
+        print('rider on vs off: largest differences', worst, 'kernels', r0['kernels'], r1['kernels'])
+        # the rider IS taken in the captured step (one kernel node less) - else the comparison below would hold by construction
+        if r0['kernels'] is not None:
+            assert r1['kernels'] == r0['kernels'] - 1, (r0['kernels'], r1['kernels'])
+        # what this rank hands in to every collective of the replayed step - the masked per-item rows of the lookup backward, the
+        # gradient buckets of the GAT layers and the GRUs - is the same with and without the rider
+        for i, ((k, a), (_, b)) in enumerate(zip(r0['taps'], r1['taps'])):
+            assert torch.equal(a, b), 'input of collective %d (%s) differs with the rider: %r' % (i, k, worst)
+        assert r0['counter'] == r1['counter'] == 1 + replays, (r0['counter'], r1['counter'])   # (the eager step + the replays)
+        assert torch.equal(r0['table'], r1['table']), 'table rows differ with the rider: %r' % (worst,)
+        for k in r0['params']:
+            assert torch.equal(r0['params'][k], r1['params'][k]), '%s differs with the rider: %r' % (k, worst)
+        assert torch.equal(r0['ring'], r1['ring']) and r0['losses'] == r1['losses']
+        assert bool(torch.isfinite(torch.tensor(r0['losses'])).all()), r0['losses']
+    finally:
+        ops.DROP_TAP = None
+        ops.set_precision('fp32')
+        torch.cuda.empty_cache()
 
 
 def test_bench_two_ranks_over_gloo_on_one_gpu(dev):

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import close, pkg
+from util import close, pkg, reseed
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +21,11 @@ def _samples(rng, n, V, max_len=12):
     return out
 
 
-def _setup(kind, dev, V=400, d=32):
+def _setup(kind, dev, V=400, d=32, dropout=0.0):
     sp, c = pkg(), pkg('collate')
     torch.manual_seed(1)
     if kind == 'msgifsr':
-        model = sp.MSGIFSR(V, 'x', d, 1, order=3, extra=False, fusion=False).to(dev)
+        model = sp.MSGIFSR(V, 'x', d, 1, dropout=dropout, order=3, extra=False, fusion=False).to(dev)
         mk = lambda caps: c.collate_fn_factory_ccs((c.seq_to_ccs_graph,), 3, caps=caps)
     elif kind == 'niser':
         model = sp.NISER(V, d, 1).to(dev)
@@ -265,24 +265,28 @@ def test_mailbox_fault_is_contained(dev, kind):
             runner.train(1, log_interval=2)
 
 
-@pytest.mark.parametrize('kind', ['msgifsr', 'niser', 'msgifsr_bf16_d128'])
+@pytest.mark.parametrize('kind', ['msgifsr', 'niser', 'msgifsr_bf16_d128', 'msgifsr_bf16_d128_drop'])
 def test_step_scalars_riding_in_the_slab_sum_launch_change_nothing(dev, kind, monkeypatch):
     """In a captured step the optimizer's step-scalar kernel (device step counters, Adam bias corrections, the loss tap) rides in the
     end-of-backward slab-sum launch (optim.FusedAdam.hyper_rider -> srec_sum_slabs_multi_hyper) instead of being a launch of its
     own behind it: one kernel node less, the same arithmetic - parameters, losses (read from the device ring the rider writes) and
-    step counters after six replays are BIT-identical to the captured step without the rider (SREC_HYPER_RIDER=0)."""
+    step counters after six replays are BIT-identical to the captured step without the rider (SREC_HYPER_RIDER=0).  `_drop`:
+    feature, attention and lookup dropout 0.2 - the rider advances the step counter the masks are keyed by, so it must leave
+    only after every backward node has re-derived its masks."""
     c, train, optim, G = pkg('collate'), pkg('train'), pkg('optim'), pkg('graph')
     V = 400
     caps = c.default_caps(32, 12)
     runs = {}
-    wide = kind == 'msgifsr_bf16_d128'                      # (the configuration whose backward DOES defer slab sums: the rider is taken)
+    wide = kind.startswith('msgifsr_bf16_d128')             # (the configuration whose backward DOES defer slab sums: the rider is taken)
+    pdrop = 0.2 if kind.endswith('_drop') else 0.0
     if wide:
         monkeypatch.setitem(pkg('ops').PRECISION, 'matmul', 'bf16')        # (restored by the fixture, whatever happens below)
         pkg('ops').weights_changed()
     for rider in ('0', '1'):
         monkeypatch.setenv('SREC_HYPER_RIDER', rider)
         rng = np.random.default_rng(9)
-        model, mk = _setup('msgifsr' if wide else kind, dev, V, d=128 if wide else 32)
+        model, mk = _setup('msgifsr' if wide else kind, dev, V, d=128 if wide else 32, dropout=pdrop)
+        reseed(5)                                           # (both runs draw the same nonces)
         opt = optim.FusedAdam(train.fix_weight_decay(model), lr=1e-2, weight_decay=1e-4, model=model)
         model.train()
         padded = [mk(caps)(_samples(rng, n, V)) for n in (32, 32, 20, 32, 27, 32)]

@@ -247,25 +247,55 @@ def test_model_matches_reference_fixture(dev, name):
     assert agree > 0.98, 'top-20 agreement %.3f' % agree
 
 
-@pytest.mark.parametrize('name', ['niser_s32', 'msgifsr_K2_edge', 'msgifsr_K3_fus_s32', 'msgifsr_K3_ext_fus_edge',
-                                  'msgifsr_K1_ext_s32'])
-def test_vocab_parallel_single_rank_equals_plain_path(dev, name):
+def _set_msgifsr_dropout(m, p):
+    """MSGIFSR's feature dropout (embedding rows, GAT inputs, read-out) and attention dropout set to p"""
+    for mod in m.modules():
+        if isinstance(mod, torch.nn.Dropout):
+            mod.p = p
+        if hasattr(mod, 'feat_drop') and isinstance(mod.feat_drop, float):       # GATConv
+            mod.feat_drop = mod.attn_drop = p
+
+
+_PLAIN_NAMES = ['niser_s32', 'msgifsr_K2_edge', 'msgifsr_K3_fus_s32', 'msgifsr_K3_ext_fus_edge', 'msgifsr_K1_ext_s32']
+
+
+@pytest.mark.parametrize('name,p', [pytest.param(n, 0.0, id=n) for n in _PLAIN_NAMES] +
+                         [pytest.param(n, 0.2, id=n + '-drop0.2') for n in _PLAIN_NAMES if n.startswith('msgifsr')])
+def test_vocab_parallel_single_rank_equals_plain_path(dev, name, p):
     """dist.VocabParallel with one rank (no process group) must give the plain fused path's loss and
-    table gradient: exercises HipLocal (masked gather, segmented rows, rank-by-rank add, sharded CE)."""
+    table gradient: exercises HipLocal (masked gather, segmented rows, rank-by-rank add, sharded CE).  p > 0: feature,
+    attention and lookup dropout - the masks are keyed by (position, nonce, step counter, salt), so with the same nonce
+    stream and the same counter both paths drop the same elements (the sharded lookup's mask rides in
+    srec_gather_rows_drop / srec_scatter_add_sorted_drop over the two-level item layout)."""
     import copy
-    D = pkg('dist')
+    D, ops = pkg('dist'), pkg('ops')
     z, samples, init = load_golden(name)
     V = init[[k for k in init if k.startswith('embedding')][0]].shape[0]
     plain = _build(name, init, V, dev)
+    if p > 0:
+        _set_msgifsr_dropout(plain, p)
     sharded = copy.deepcopy(plain)
     vp = D.VocabParallel(sharded)
+    if p > 0:
+        # the device step counter the masks are keyed by (FusedAdam registers its own the same way): 3, not 0, in both
+        for m in (plain, sharded):
+            m.__dict__['_srec_rng_counter'] = torch.full((1,), 3, dtype=torch.int32, device=dev)
     inputs, labels = _collate(name, samples)
     inputs = [x.to(dev) for x in inputs]
     labels = labels.to(dev)
     plain.train()
     sharded.train()
-    l1 = plain.fused_loss(*inputs, labels)
+    reseed(31)
+    ops.DROP_TAP = [] if p > 0 else None
+    try:
+        l1 = plain.fused_loss(*inputs, labels)
+        taps = ops.DROP_TAP
+    finally:
+        ops.DROP_TAP = None
+    if p > 0:                                          # dropout really is on
+        assert taps and abs((taps[0]['ms'] == 0).float().mean().item() - p) < 0.05
     l1.backward()
+    reseed(31)
     l2 = sharded.fused_loss(*inputs, labels)
     l2.backward()
     close(l2, l1, rtol=1e-6, atol=1e-6, what='loss')

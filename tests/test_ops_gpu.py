@@ -1174,6 +1174,182 @@ def test_lookup_with_fused_dropout(dev):
             ops.RNG_COUNTER[str(dev)] = old
 
 
+def _skewed_lookup(V, pad, seed=3):
+    """item id of every looked-up position of a Zipf-like batch - one item at 1200 positions, one at 40 (the chunk level
+    splits both over several wavefronts), a Zipf body and 200 items looked up once - and its item CSR as a FlatBatch holds it:
+    (items, uptr, upos, cptr, chunk_ptr) + the inverse map, capacity-padded by `pad` (offset arrays repeat their last value,
+    index arrays -1).  -> (idx [n] int64, n, uniq5 on the host, inv, live U)"""
+    col = importlib.import_module('sessionrec-pytorch_amd.collate')
+    rng = np.random.default_rng(seed)
+    w = 1.0 / np.arange(1, V - 320 + 1)
+    body = 20 + rng.choice(V - 320, size=1500, p=w / w.sum())
+    single = rng.choice(np.arange(V - 250, V), size=200, replace=False)
+    idx = np.concatenate([np.full(1200, 3), np.full(40, 11), body, single])
+    idx = idx[rng.permutation(idx.size)].astype(np.int64)
+    items, uptr, upos, inv = col._uniq_csr(idx)
+    cptr, chunk_ptr = col._chunk_csr(uptr)
+    n, U, C = idx.size, items.size, chunk_ptr.size - 1
+    cnt = np.diff(uptr)
+    assert cnt.max() > 1000 and ((cnt > 16) & (cnt < 1000)).any() and (cnt == 1).sum() >= 200
+    if pad:
+        rep = lambda a, k: np.concatenate([a, np.full(k, a[-1], a.dtype)])
+        neg = lambda a, k: np.concatenate([a, np.full(k, -1, a.dtype)])
+        items, uptr, cptr = neg(items, 13), rep(uptr, 13), rep(cptr, 13)
+        upos, inv, chunk_ptr = neg(upos, 37), neg(inv, 37), rep(chunk_ptr, 9)
+    assert chunk_ptr.size - 1 >= C and cptr[-1] <= chunk_ptr.size - 1 and chunk_ptr[-1] == n
+    return idx, n, (items, uptr, upos, cptr, chunk_ptr), inv, U
+
+
+def _masked_rows_ref(g, inv, mask, n, U_cap):
+    """float64 per-item sums of the masked gradient rows of the n live positions, and the sums of their magnitudes (the
+    scale of the fp32 summation error)"""
+    t = g[:n].double() * mask.double()
+    ref = torch.zeros(U_cap, g.shape[1], dtype=torch.float64, device=g.device).index_add_(0, inv[:n].long(), t)
+    mag = torch.zeros_like(ref).index_add_(0, inv[:n].long(), t.abs())
+    return ref, mag
+
+
+def _within(a, ref, mag, what):
+    """|a - ref| <= 1e-5 sum|terms| + 1e-6 elementwise: fp32 round-off of the sums, far below one wrongly masked term"""
+    err = (a.double() - ref).abs()
+    bound = 1e-5 * mag + 1e-6
+    assert bool((err <= bound).all()), '%s: max err %.3e, worst excess %.3e' % (what, err.max().item(), (err - bound).max().item())
+
+
+@pytest.mark.parametrize('d', [32, 100, 256, 516])
+@pytest.mark.parametrize('pad', [False, True])
+def test_sharded_lookup_dropout_against_float64(dev, d, pad):
+    """The lookup of the row-sharded path with its fused feature dropout (dist.ShardedLookup -> dist.HipLocal): the masked
+    gather srec_gather_rows_drop of the exchanged rows at the batch positions, and its backward srec_scatter_add_sorted_drop
+    over the two-level item layout (<= 16 positions per chunk, then the chunks of each item) and over the one-level one, then
+    the rank's add into its shard of the table gradient - against table[idx] * mask and a float64 index_add of g * mask.
+    Skewed items, singletons, widths that are no multiple of 64, a counter that is not 0, items of other shards (-1 after
+    localisation) and a capacity-padded batch whose padded positions hold garbage gradients."""
+    D = importlib.import_module('sessionrec-pytorch_amd.dist')
+    local = D.HipLocal()
+    V, p, salt = 4000, 0.3, 7
+    idx, n, uniq_h, inv_h, U = _skewed_lookup(V, pad)
+    uniq5 = tuple(torch.from_numpy(a).to(dev) for a in uniq_h)
+    uniq3 = uniq5[:3]
+    inv = torch.from_numpy(inv_h).to(dev)
+    n_cap, U_cap = inv.numel(), uniq5[0].numel()
+    g0 = torch.Generator().manual_seed(d)
+    full = (torch.rand(V, d, generator=g0) + 0.5).to(dev)          # no zeros: output / input recovers the mask
+    lo, n_loc = 1984, 1600                                          # this rank's shard; rows [lo, lo + n_loc) of the table
+    shard = full[lo:lo + n_loc].contiguous()
+    counter = torch.full((1,), 5, dtype=torch.int32, device=dev)
+    drop = (p, 12345, counter.data_ptr(), salt)
+    items = uniq5[0]
+    rel = local.localize(items, lo, n_loc)
+    itl = items.long()
+    owned = (itl >= lo) & (itl < lo + n_loc)
+    assert owned.any() and (~owned & (itl >= 0)).any()              # the batch reads rows of this shard and of others
+    assert torch.equal(rel, torch.where(owned, itl - lo, torch.full_like(itl, -1)).int())
+    # the rows of every item of the batch after the exchange (the reduce-scatter's result) and this shard's own contribution
+    mine = torch.where((itl >= 0)[:, None], full[itl.clamp(min=0)], torch.zeros(1, d, device=dev))
+    own = local.gather_masked(shard, rel)
+    assert torch.equal(own, torch.where(owned[:, None], mine, torch.zeros_like(mine)))
+    idx_d = torch.from_numpy(idx).to(dev)
+    ref_in = full[idx_d]
+    masks = {}
+    for key, dr in (('a', drop), ('b', drop), ('nonce', (p, 12346, drop[2], salt))):
+        out = local.gather_masked(mine, inv, dr)
+        assert out.shape == (n_cap, d)
+        assert torch.equal(out[n:], torch.zeros_like(out[n:]))          # padded positions: zero rows
+        masks[key] = out[:n] / ref_in
+        # the mask is keyed by the position, not by what is gathered: this shard's rows through it give the same products
+        part = local.gather_masked(own, inv, dr)[:n]
+        ownp = owned[inv[:n].long()]
+        assert torch.equal(part[ownp], out[:n][ownp]) and not part[~ownp].any()
+    counter.fill_(6)
+    masks['counter'] = local.gather_masked(mine, inv, drop)[:n] / ref_in
+    counter.fill_(5)
+    mask = masks['a']
+    keep = mask > 0
+    assert torch.allclose(mask[keep], torch.full_like(mask[keep], 1 / (1 - p)), rtol=1e-6)
+    assert abs(keep.float().mean().item() - (1 - p)) < 0.01
+    assert torch.equal(masks['a'], masks['b'])
+    for k in ('nonce', 'counter'):
+        diff = ((masks[k] > 0) != keep).float().mean().item()
+        assert 0.3 < diff < 0.5, (k, diff)                              # independent masks: 2 p (1 - p) = 0.42 of them differ
+    mask = torch.where(keep, torch.full_like(mask, 1 / (1 - p)), torch.zeros_like(mask))
+    # backward: one summed row per item, the forward's mask re-derived from (nonce, counter, salt)
+    g = torch.randn(n_cap, d, generator=g0).to(dev)
+    if n_cap > n:
+        g[n:] = 1e6                                                     # positions past the live count contribute nothing
+    ref, mag = _masked_rows_ref(g, inv, mask, n, U_cap)
+    rows5 = local.segment_rows(g, uniq5, drop)
+    rows3 = local.segment_rows(g, uniq3, drop)
+    _within(rows5, ref, mag, 'two-level segment rows')
+    _within(rows3, ref, mag, 'one-level segment rows')
+    assert not rows5[U:].any()                                          # padded items: zero rows
+    # the rank's add into its shard of the table gradient, which already holds the scoring gradient: only its own items
+    dst0 = torch.randn(n_loc, d, generator=g0).to(dev)
+    dst = dst0.clone()
+    local.add_rows(rows5, rel, dst)
+    hit = torch.zeros(n_loc, dtype=torch.bool, device=dev)
+    hit[rel[rel >= 0].long()] = True
+    assert torch.equal(dst[~hit], dst0[~hit])
+    sel = rel >= 0
+    want = dst0.double().index_add(0, rel[sel].long(), ref[sel])
+    wmag = dst0.double().abs().index_add(0, rel[sel].long(), mag[sel])
+    _within(dst[hit], want[hit], wmag[hit], 'shard gradient rows')
+
+
+@pytest.mark.parametrize('d', [32, 100, 256, 516])
+def test_lookup_with_fused_dropout_two_level_padded(dev, d):
+    """test_lookup_with_fused_dropout on the layout the models hand over: the 5-tuple of a capacity-padded FlatBatch (chunk
+    level <= 16 positions per wavefront, then the chunks of each item), live counts below the capacities (dyn_n / dyn_u),
+    a non-zero step counter, and the backward ADDED into a table gradient that already holds the scoring gradient"""
+    ops = _ops()
+    V, p = 4000, 0.3
+    idx_h, n, uniq_h, inv_h, U = _skewed_lookup(V, True, seed=5)
+    uniq = tuple(torch.from_numpy(a).to(dev) for a in uniq_h)
+    n_cap = inv_h.size
+    idx = torch.full((n_cap,), -1, dtype=torch.int32, device=dev)
+    idx[:n] = torch.from_numpy(idx_h).to(dev).int()
+    dyn_n = torch.tensor([n], dtype=torch.int32, device=dev)
+    dyn_u = torch.tensor([U], dtype=torch.int32, device=dev)
+    g0 = torch.Generator().manual_seed(100 + d)
+    table = (torch.rand(V, d, generator=g0) + 0.5).to(dev).requires_grad_()
+    counter = torch.full((1,), 9, dtype=torch.int32, device=dev)
+    old = ops.RNG_COUNTER.get(str(dev))
+    ops.RNG_COUNTER[str(dev)] = counter
+    try:
+        tg = ops.TableGrad(table.detach())
+        grad0 = torch.randn(V, d, generator=g0).to(dev)
+        tg.buf.copy_(grad0)
+        torch.manual_seed(21)
+        ops.seed_dropout()
+        out = ops.embedding_lookup(table, idx, uniq, tg, dyn_n, dyn_u, (p, 7))
+        assert torch.equal(out[n:], torch.zeros_like(out[n:]))
+        mask = (out[:n] / table[idx[:n].long()]).detach()
+        keep = mask > 0
+        assert torch.allclose(mask[keep], torch.full_like(mask[keep], 1 / (1 - p)), rtol=1e-6)
+        assert abs(keep.float().mean().item() - (1 - p)) < 0.01
+        g = torch.randn(n_cap, d, generator=g0).to(dev)
+        g[n:] = 1e6
+        out.backward(g)
+        assert table.grad is None                                        # added into the TableGrad buffer
+        mask = torch.where(keep, torch.full_like(mask, 1 / (1 - p)), torch.zeros_like(mask))
+        t = g[:n].double() * mask.double()
+        want = grad0.double().index_add(0, idx[:n].long(), t)
+        mag = grad0.double().abs().index_add(0, idx[:n].long(), t.abs())
+        _within(tg.buf, want, mag, 'two-level dropout lookup backward')
+        # a different counter: another mask
+        counter.fill_(10)
+        torch.manual_seed(21)
+        ops.seed_dropout()
+        out2 = ops.embedding_lookup(table, idx, uniq, None, dyn_n, dyn_u, (p, 7))
+        diff = ((out2[:n] > 0) != keep).float().mean().item()
+        assert 0.3 < diff < 0.5, diff
+    finally:
+        if old is None:
+            ops.RNG_COUNTER.pop(str(dev), None)
+        else:
+            ops.RNG_COUNTER[str(dev)] = old
+
+
 def test_gemm_f32_group_mixed_layouts(dev):
     """one grouped launch of exact-fp32 products in all three operand layouts, with bias, beta, dynamic row counts, a strided
     output view and a long-K weight gradient (k-split into slabs + grouped reduce)"""
