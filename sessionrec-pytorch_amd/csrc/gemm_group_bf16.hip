@@ -266,7 +266,10 @@ extern "C" int srec_gemm_group_bf16(const void* desc_, int mode, void* stream) {
     const int tile = (mode == 0 && t128 >= 256) ? 128 : 64;
     int blocks = 0;
     for (int p = 0; p < d->np; ++p) {
-        if (d->nseg[p] <= 0 || d->nseg[p] > MAXS || d->M[p] <= 0 || d->N[p] <= 0 || d->K[p] < 4) return SREC_BAD_ARG;
+        // (k-contiguous operands are read 4 / 8 along k with the last read clamped to K - 4 / K - 8; a reduction-major
+        // operand is read one reduction row at a time, clamped to the last live row: a weight gradient over the 1 - 3 nodes
+        // of a node type in a batch of short sessions is a valid problem)
+        if (d->nseg[p] <= 0 || d->nseg[p] > MAXS || d->M[p] <= 0 || d->N[p] <= 0 || d->K[p] < (mode == 2 ? 1 : 4)) return SREC_BAD_ARG;
         if (mode != 2 && (d->K[p] & (d->a16 ? 7 : 3))) return SREC_BAD_ARG;   // k-contiguous 16-B reads
         if ((mode == 2 && (d->M[p] & 3)) || (mode != 0 && (d->N[p] & 3))) return SREC_BAD_ARG;
         g.M[p] = d->M[p]; g.N[p] = d->N[p]; g.K[p] = d->K[p]; g.nseg[p] = d->nseg[p]; g.C[p] = d->C[p]; g.dyn[p] = d->dyn[p];
