@@ -316,8 +316,9 @@ int srec_adam_hyper(int* counter, const void* cfg, float* hyper, void* stream);
  * Adam kernel of the step the identity (parameters and moments keep their bits), the loss slot reads NaN. */
 int srec_adam_hyper_multi(int n, const void* counter, const void* cfg, const void* hyper, const int* tap_counter,
                           const float* tap_src, float* tap_ring, int tap_n, const int* skip, void* stream);
-/* one launch for many small tensors (48 per launch): desc = HOST srec_adam_multi_desc below; the pointers travel by
- * value in the kernel arguments (nothing staged in device memory; a captured hipGraph bakes them into the node) */
+/* one launch for many small tensors (MT per launch, csrc/adam.hip: 88; any nt, launched MT at a time): desc = HOST
+ * srec_adam_multi_desc below; the pointers travel by value in the kernel arguments (nothing staged in device memory; a
+ * captured hipGraph bakes them into the node) */
 typedef struct srec_adam_multi_desc {
     int nt;                    /* number of tensors */
     const int* use_wd;         /* [nt] apply the group's weight decay (0 for bias / batch_norm / activation, train.py:18) */

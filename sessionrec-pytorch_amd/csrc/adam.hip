@@ -75,6 +75,11 @@ __global__ void adam_rows_kernel(float* __restrict__ W, const float* __restrict_
     if (i >= n) return;
     const Hyper h = load_hyper(hyper);
     const float wd = use_wd ? h.wd : 0.f, step = h.step, rs2 = h.bc2s;
+    // the skip scalars of hyper_role ({0, 1, 1, eps, 0, 0, 0, 1}: the Adam arithmetic below keeps every bit): the renorm must
+    // not be written either - a row the last step scaled to max_norm recomputes, in fp32, to a norm an ulp above it about as
+    // often as not and would be scaled again ("parameters and moments keep their bits", srec.h).  cs is still that of the
+    // renormed row, dst16 still the copy of W as it stands.
+    if (h.step == 0.f && h.omb1 == 0.f && h.omb2 == 0.f && h.b2 == 1.f) renorm_write = 0;
     const size_t off = (size_t)i * ld;
     // proj_cs != NULL: the chain rule of the catalog-row normalisation (rownorm_project) is applied HERE, to the gradient row as
     // it is read: g = G - W (<W, G> - radial) inv^2, inv = proj_cs * proj_inv_scale (the column scale of this step's forward;

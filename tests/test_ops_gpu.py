@@ -268,8 +268,9 @@ def test_fused_adam_matches_torch(dev):
 
 
 def test_fused_adam_multi_tensor_launch_shapes(dev):
-    """srec_adam_multi: more tensors than one launch carries (48), sizes that are not multiples of 4 or of the 4096
-    chunk, and a parameter whose storage is only 4-byte aligned (scalar path)."""
+    """srec_adam_multi: 64 tensors, all decayed - both words of wd_mask, ONE launch (a launch carries MT tensors, csrc/adam.hip:
+    88; more than one launch and mixed decay flags: test_table_step_gpu.py::test_adam_multi_across_launches) - sizes that are
+    not multiples of 4 or of the 4096 chunk, and a parameter whose storage is only 4-byte aligned (scalar path)."""
     optim = importlib.import_module('sessionrec-pytorch_amd.optim')
     torch.manual_seed(9)
     sizes = [1, 2, 3, 5, 7, 64, 255, 1023, 4095, 4096, 4097, 9001, 70001] + [13 + 3 * i for i in range(50)]
