@@ -479,6 +479,22 @@ int srec_score_topk_ws(int B, int V, int K, long* bytes);
 int srec_score_topk(const float* sr, int ld_sr, const float* E, int ld_e, const float* cs, int B, int V, int d, int K,
                     float* out_val, int* out_idx, void* ws, void* stream);
 
+/* ---- evaluation: rank of the label among ALL items, any cutoff, mixtures of soft-maxes too (rank.hip) ---------------
+ * Replaces `logits = model(...); logits.topk(20)` of train.py:36-55 by the one integer every HR / MRR / NDCG @k is a function
+ * of, also where the score mixes several soft-maxes (msgifsr.py:281-321: order fusion, repeat / explore gate):
+ *   s[b,v] = logsumexp_{c<C}( cs[v] * <sr_c[b], E_v> + off[c,b] ),  off = off_in if v is in listed[b,:] else off_ex
+ * sr: C blocks [B, d] (row stride ld_sr, block stride comp_stride); off_ex / off_in [C, B] (NULL = 0); listed [B, L] item
+ * ids, -1 = empty slot, every id at most once per session (NULL / L = 0: none); labels[b] global id (< 0: rank -1);
+ * id_lo: global id of local row 0 (row-sharded tables).  rank[b] = # local rows v with id_lo + v != labels[b] and
+ * (s > target[b] or (s == target[b] and id_lo + v < labels[b])): ties towards the lower id, as srec_score_topk.
+ * target [B]: written here (the label's score where this table owns the label, else 0) unless target_given.  Ranks and
+ * targets of disjoint row shards add up; rank == NULL runs the target pass alone (a shard's share, ahead of that sum).
+ * 1 <= C <= 4, d % 4 == 0, d <= 1024, L <= 64; fp32 MFMA, no (B, V) tensor. */
+int srec_score_rank_ws(int B, int V, int d, int C, int L, long* bytes);
+int srec_score_rank(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                    const float* off_ex, const float* off_in, const int* listed, int L, const int* labels, long id_lo,
+                    int B, int V, int d, int C, float* target, int target_given, int* rank, void* ws, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

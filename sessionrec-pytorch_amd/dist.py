@@ -418,6 +418,11 @@ class HipLocal:
         from . import ops
         return ops.score_topk(sr, table, cs, k)
 
+    def rank(self, srs, table, cs, labels, off_ex, off_in, listed, id_lo, target=None, target_only=False):
+        """this shard's share of (rank, target) of ops.score_rank: rows [id_lo, id_lo + n) of the catalog"""
+        from . import ops
+        return ops.score_rank(srs, table, cs, labels, off_ex, off_in, listed, id_lo, target, target_only)
+
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
 
@@ -788,6 +793,48 @@ class VocabParallel:
         if data_parallel:
             val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
         return val, idx.to(torch.int32)
+
+    def target_rank(self, srs, table, cs, labels, off_ex=None, off_in=None, listed=None, data_parallel=False):
+        """rank of every session's label over the sharded table (ops.score_rank's contract; srs: list of C [B, d] session
+        vectors, off_ex / off_in [C, B], listed [B, L]).  The number of items ahead of the label is a SUM over disjoint row
+        ranges: each rank scores the labels and listed items it owns (every id has one owner, the others contribute 0 ->
+        sum-all-reduce of `target`), counts its own rows against that common target, and one sum-all-reduce of B integers
+        finishes it - no gather of candidate lists, no merge.  data_parallel as in topk(): every rank passes its own B / world
+        sessions (session vectors, labels, offsets and lists are all-gathered first) and gets its own sessions' ranks."""
+        n_loc = srs[0].shape[0]
+        labels = labels.to(torch.int64)
+        if data_parallel:
+            srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
+            labels = all_gather_cat(labels.contiguous(), self.group)
+            gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
+            off_ex, off_in = gat(off_ex), gat(off_in)
+            if listed is not None:           # lists of different widths on the ranks: pad to the widest
+                w = torch.tensor([listed.shape[1]], dtype=torch.int64, device=listed.device)
+                if _active(self.group):
+                    all_reduce_(w, dist.ReduceOp.MAX, self.group)
+                pad = listed.new_full((listed.shape[0], int(w.item())), -1)
+                pad[:, :listed.shape[1]] = listed
+                listed = all_gather_cat(pad, self.group)
+        live = table[:self.n_live]
+        csl = None if cs is None else cs[:self.n_live]
+        B = srs[0].shape[0]
+        if self.n_live > 0:
+            _, target = self.local.rank(srs, live, csl, labels, off_ex, off_in, listed, self.lo, None, True)
+        else:
+            target = torch.zeros(B, device=srs[0].device, dtype=torch.float32)
+        all_reduce_sum(target, self.group)
+        if self.n_live > 0:
+            rank, _ = self.local.rank(srs, live, csl, labels, off_ex, off_in, listed, self.lo, target, False)
+        else:
+            rank = torch.where(labels < 0, -1, 0).to(torch.int32)
+        if _active(self.group):
+            # sessions without a label carry -1 on every rank: summed as 0, restored afterwards
+            rank = all_reduce_sum(torch.where(labels < 0, torch.zeros_like(rank), rank), self.group)
+        # (a fix-up correction within round-off of the target may overshoot by one: see _ScoringMixin._rank_of)
+        rank = torch.where(labels < 0, torch.full_like(rank, -1), rank.clamp(min=0))
+        if data_parallel:
+            rank = rank[self.rank * n_loc:(self.rank + 1) * n_loc]
+        return rank
 
     # ---- replicated-parameter gradients: bucketed all-reduce, launched in backward order ----------------------------------
     N_BUCKETS = 3

@@ -559,6 +559,46 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             return -torch.where(live, logp, torch.zeros_like(logp)).sum() / dynB.to(logp.dtype).clamp(min=1).sum()
         return -logp.mean()
 
+    def target_rank(self, *inputs, labels):
+        """rank of the label under the score forward() returns, WITHOUT its (B, V) matrices (one per order, plus the
+        in-session mask): the mixture of msgifsr.py:281-321 is logsumexp_c(z_c[b,v] + off_c[b]) with per-session offsets
+        built from what fused_loss computes anyway - off_ex = log softmax(alpha)_c + log phi_c[b, explore] - lse_ex_c[b],
+        off_in = ... + log phi_c[b, repeat] - lse_in_c[b] for the session's own items (`listed`); without `extra`
+        off_ex = log softmax(alpha)_c - lse_c[b]; without fusion one component.  See _ScoringMixin.target_rank."""
+        if not (self.extra or (self.fusion and self.order > 1)):
+            return super().target_rank(*inputs, labels=labels)
+        (mg,) = inputs
+        with torch.no_grad():
+            srs = self.session_repr(mg)
+            if not isinstance(srs, (list, tuple)):
+                srs = [srs]
+            B = srs[0].shape[0]
+            st = self._state(B)
+            cs, inv_scale = self._col_scale(st)
+            la = torch.log_softmax(self.alpha, 0) if len(srs) > 1 else srs[0].new_zeros(1)
+            lab32 = labels.to(torch.int32)
+            listed = None
+            if self.extra:
+                posc, valid, items, _ = self._in_session(mg)
+                listed = torch.where(valid, items, torch.full_like(items, -1)).to(torch.int32)
+            off_ex, off_in = [], []
+            for c, sr in enumerate(srs):
+                if self.shard is not None:
+                    lse, _ = self.shard.stats(sr, self._table(), cs, labels, inv_scale)
+                else:
+                    lse, _ = ops.score_stats(sr, self._table(), cs, lab32, st['ws'][B], st['tgrad'], None, inv_scale, None)
+                if self.extra:
+                    zin = 12.0 * (self._s1_feat[posc] * sr[:, None, :]).sum(-1)
+                    lse_in = torch.logsumexp(zin.masked_fill(~valid, float('-inf')), dim=1)
+                    lse_ex = lse + torch.log1p(-torch.exp(lse_in - lse).clamp(max=1.0 - 1e-7))
+                    lphi = self._log_phi(sr, None)
+                    off_in.append(la[c] + lphi[:, 0] - lse_in)
+                    off_ex.append(la[c] + lphi[:, 1] - lse_ex)
+                else:
+                    off_ex.append(la[c] - lse)
+            return self._rank_of(srs, cs, labels, torch.stack(off_ex, 0), torch.stack(off_in, 0) if self.extra else None,
+                                 listed)
+
     def forward(self, mg):
         sr = self.session_repr(mg)
         if self.extra:

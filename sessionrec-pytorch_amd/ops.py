@@ -1720,6 +1720,70 @@ def score_topk(sr, table, cs, k):
     return val, idx
 
 
+_RANK_WS = {}
+
+
+def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id_lo=0, target=None, target_only=False):
+    """(rank int32 [B], target fp32 [B]): the number of rows of `table` that score ahead of each session's label under
+    s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) (off_in for the items of listed[b,:], off_ex elsewhere; ties
+    towards the lower item id) - no (B, V) tensor, no cutoff (csrc/rank.hip).  srs: [B, d], [C, B, d] or a list of C
+    [B, d] tensors, C <= 4; off_ex / off_in: [C, B] or None (= 0); listed: [B, L] item ids, -1 = empty slot; labels:
+    global item ids (< 0: rank -1); id_lo: global id of table row 0 (a row shard).  target: the labels' scores when they
+    are already known (the sharded case: summed over the shards) - else computed here, 0 for labels other shards own.
+    target_only: (None, target) from the target pass alone - a shard's share ahead of that sum."""
+    if isinstance(srs, (list, tuple)):
+        srs = srs[0] if len(srs) == 1 else torch.stack([s.detach() for s in srs], 0)
+    srs = srs.detach()
+    if srs.dim() == 3 and srs.shape[0] == 1:
+        srs = srs[0]
+    if srs.dim() == 2:
+        srs = _rows(srs)
+        C, (B, d) = 1, srs.shape
+        ld_sr, comp = _ld(srs), 0
+    else:
+        assert srs.dim() == 3 and srs.dtype == torch.float32, (srs.shape, srs.dtype)
+        srs = srs.contiguous()
+        C, B, d = srs.shape
+        ld_sr, comp = d, B * d
+    table = _rows(table.detach())
+    V = table.shape[0]
+    dev = srs.device
+    if B == 0:
+        return torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.float32)
+
+    def offs(o):
+        if o is None:
+            return None
+        o = o.detach().to(torch.float32).reshape(C, B).contiguous()
+        return o
+    off_ex, off_in = offs(off_ex), offs(off_in)
+    L = 0
+    if listed is not None and listed.numel() > 0:
+        listed = listed.detach().to(torch.int32).reshape(B, -1).contiguous()
+        L = listed.shape[1]
+        if L > 64:
+            raise ValueError('score_rank: %d listed items per session; the fix-up pass of csrc/rank.hip takes at most 64 '
+                             '(evaluate such sessions with method="topk")' % L)
+    else:
+        listed = None
+    labels = labels.detach().to(torch.int32).contiguous()
+    assert labels.numel() == B, (labels.shape, B)
+    # the C ABI carries a workspace (partial counts per range are one legal implementation); the current kernels meet in
+    # integer atomics and ask for a token size only - the call still validates the shape contract up front
+    n = _ct.c_long()
+    lib.srec_score_rank_ws(B, V, d, C, L, _ct.addressof(n))
+    key = (dev.index, n.value)
+    ws = _RANK_WS.get(key)
+    if ws is None:
+        ws = _RANK_WS[key] = torch.empty(n.value, device=dev, dtype=torch.uint8)
+    given = target is not None
+    target = target.detach().to(torch.float32).contiguous() if given else torch.empty(B, device=dev, dtype=torch.float32)
+    rank = None if target_only else torch.empty(B, device=dev, dtype=torch.int32)
+    lib.srec_score_rank(ptr(srs), ld_sr, comp, ptr(table), table.stride(0), ptr(cs), ptr(off_ex), ptr(off_in), ptr(listed), L,
+                        ptr(labels), int(id_lo), B, V, d, C, ptr(target), int(given), ptr(rank), ptr(ws), stream())
+    return rank, target
+
+
 class ScoreLogProb(torch.autograd.Function):
     """(B,V) log-probabilities - the tensor the reference models' forward() returns (compat /
     evaluation path).  Backward materialises d z (B,V) and runs two MFMA GEMMs."""

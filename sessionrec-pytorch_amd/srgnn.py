@@ -203,6 +203,26 @@ class _ScoringMixin:
                 return self.shard.topk(sr, self._table(), cs, k, data_parallel=self.shard.eval_data_parallel)
             return ops.score_topk(sr, self._table(), cs, k)
 
+    def target_rank(self, *inputs, labels):
+        """int32 [B]: how many catalog items score ahead of each session's label (0 = the label is the top item; ties count
+        towards the lower item id, as topk does; a label < 0 gives -1) - one fused pass over the table, no (B, V) score
+        matrix and no cutoff: every HR / MRR / NDCG @k of train.evaluate(method='rank') follows from it (train.py:36-55)."""
+        with torch.no_grad():
+            sr = self.session_repr(*inputs)
+            cs, _ = self._col_scale(self._state(sr.shape[0]))
+            return self._rank_of([sr], cs, labels, None, None, None)
+
+    def _rank_of(self, srs, cs, labels, off_ex, off_in, listed):
+        if self.shard is not None:       # ranks of disjoint row shards add up: one all-reduce of B integers
+            return self.shard.target_rank(srs, self._table(), cs, labels, off_ex, off_in, listed,
+                                          data_parallel=self.shard.eval_data_parallel)
+        rank = ops.score_rank(srs, self._table(), cs, labels, off_ex, off_in, listed)[0]
+        if listed is not None:
+            # the fix-up pass re-scores a listed item in another summation order than the count pass: where its "ex" score is
+            # within round-off of the target the two comparisons can disagree and the correction overshoots by one
+            rank = torch.where(labels >= 0, rank.clamp(min=0), rank)
+        return rank
+
     def _log_probs(self, sr):
         B = sr.shape[0]
         st = self._state(B)

@@ -29,7 +29,44 @@ def prepare_batch(batch, device):
     return [x.to(device) for x in inputs], labels.to(device, non_blocking=labels.is_pinned())
 
 
-def evaluate(model, data_loader, device, cutoff=20):
+def metrics_from_ranks(ranks, cutoffs):
+    """{'hit@k', 'mrr@k', 'ndcg@k' for k in cutoffs} from the labels' ranks (0 = the label is the best item): hit = rank < k,
+    mrr = 1 / (rank + 1) and ndcg = 1 / log2(rank + 2) inside the cutoff, 0 outside, averaged over the sessions.  A rank of
+    -1 (a session without a label) is left out of numerator and denominator."""
+    r = th.as_tensor(ranks).detach().reshape(-1).to('cpu', th.float64)
+    r = r[r >= 0]
+    n = max(int(r.numel()), 1)
+    out = {}
+    for k in cutoffs:
+        k = int(k)
+        inside = r < k
+        out['hit@%d' % k] = float(inside.sum()) / n
+        out['mrr@%d' % k] = float((1.0 / (r[inside] + 1.0)).sum()) / n
+        out['ndcg@%d' % k] = float((1.0 / th.log2(r[inside] + 2.0)).sum()) / n
+    return out
+
+
+def ranks_from_scores(scores, labels):
+    """the labels' ranks in a materialised (B, V) score matrix under the rule of the fused kernels: an item is ahead of the
+    label if it scores higher, or the same with a lower id; the label itself never counts; label < 0 -> -1"""
+    lab = labels.long()
+    safe = lab.clamp(min=0)
+    t = scores.gather(1, safe.unsqueeze(1))
+    ids = th.arange(scores.shape[1], device=scores.device).unsqueeze(0)
+    ahead = (scores > t) | ((scores == t) & (ids < safe.unsqueeze(1)))
+    ahead &= ids != safe.unsqueeze(1)
+    return th.where(lab >= 0, ahead.sum(1), th.full_like(lab, -1))
+
+
+def evaluate(model, data_loader, device, cutoff=20, method='topk', cutoffs=None):
+    """(MRR@cutoff, HR@cutoff) as the reference (train.py:36-55).  method='rank': from the label's rank among ALL items
+    (model.target_rank on the GPU: one fused pass, no (B, V) tensor, mixtures of soft-maxes included; a CPU model's
+    materialised forward() output otherwise) instead of the `cutoff` best items.  cutoffs: return the metrics_from_ranks
+    dict for these cutoffs instead of the pair."""
+    assert method in ('topk', 'rank'), method
+    check_eval_options(method, cutoffs)
+    if method == 'rank' or cutoffs is not None:
+        return _evaluate_ranks(model, data_loader, device, cutoff, method, cutoffs)
     model.eval()
     mrr, hit, num_samples = 0.0, 0, 0
     with th.no_grad():
@@ -48,9 +85,46 @@ def evaluate(model, data_loader, device, cutoff=20):
     return mrr / num_samples, hit / num_samples
 
 
+TOPK_MAX = 32        # srec_score_topk keeps at most 32 items per session (include/srec.h)
+
+
+def check_eval_options(method, cutoffs):
+    """cutoffs beyond the fused top-K kernel's limit need the rank method - said before training starts, not after an epoch"""
+    if method == 'topk' and cutoffs and max(cutoffs) > TOPK_MAX:
+        raise ValueError('evaluation cutoffs above %d need method="rank" (--eval-method rank): the top-K evaluation keeps '
+                         'at most %d items per session' % (TOPK_MAX, TOPK_MAX))
+
+
+def _evaluate_ranks(model, data_loader, device, cutoff, method, cutoffs):
+    model.eval()
+    kmax = max([int(cutoff)] + [int(k) for k in (cutoffs or ())])
+    ranks = []
+    with th.no_grad():
+        for batch in data_loader:
+            inputs, labels = prepare_batch(batch, device)
+            if method == 'rank':
+                if hasattr(model, 'target_rank') and labels.is_cuda:
+                    r = model.target_rank(*inputs, labels=labels)
+                else:
+                    r = ranks_from_scores(model(*inputs), labels)
+            else:       # the `kmax` best items: a label outside them is a miss at every cutoff
+                if hasattr(model, 'topk') and labels.is_cuda:
+                    topk = model.topk(*inputs, k=kmax)[1].long()
+                else:
+                    topk = model(*inputs).topk(k=kmax)[1]
+                found = topk == labels.unsqueeze(-1)
+                r = th.where(found.any(1), found.float().argmax(1), th.full_like(labels, kmax))
+            ranks.append(r.long().cpu())
+    ranks = th.cat(ranks) if ranks else th.zeros(0, dtype=th.long)
+    if cutoffs is not None:
+        return metrics_from_ranks(ranks, cutoffs)
+    m = metrics_from_ranks(ranks, (cutoff,))
+    return m['mrr@%d' % cutoff], m['hit@%d' % cutoff]
+
+
 class TrainRunner:
     def __init__(self, dataset, model, train_loader, test_loader, device, lr=1e-3, weight_decay=0, patience=3,
-                 checkpoint=None, resume=True, hooks=(), graph='auto', shard=None):
+                 checkpoint=None, resume=True, hooks=(), graph='auto', shard=None, eval_method='topk', eval_cutoffs=None):
         """Same positional surface as the reference (train.py:57-69).  Additions (the reference has
         neither): `checkpoint` = path written after every epoch (model, optimizer incl. Adam moments and step counts,
         scheduler, epoch / batch counters, best metrics) and, with `resume`, read back at the start of train();
@@ -60,7 +134,13 @@ class TrainRunner:
         backward, FusedAdam) instead of ~120 eager launches; a batch with another layout or relation pattern runs
         eagerly, with the same result.  `shard` (dist.VocabParallel, multi-GPU): the item table is row-sharded over the
         ranks and every rank feeds its slice of each batch (dataset.RankSliceBatchSampler); the replicated encoder
-        gradients are all-reduced after backward, evaluation merges per-shard top-k lists, only rank 0 prints."""
+        gradients are all-reduced after backward, evaluation merges per-shard top-k lists, only rank 0 prints.
+        `eval_method` ('topk' | 'rank') and `eval_cutoffs` (e.g. (5, 10, 20)): see evaluate(); the extra cutoffs' HR / MRR / NDCG
+        are printed on a line of their own after the reference's epoch line and ride in the 'epoch' hook event as `metrics`."""
+        assert eval_method in ('topk', 'rank'), eval_method
+        self.eval_method = eval_method
+        self.eval_cutoffs = tuple(int(k) for k in eval_cutoffs) if eval_cutoffs else None
+        check_eval_options(self.eval_method, self.eval_cutoffs)
         self.shard = shard
         self.rank = shard.rank if shard is not None else 0
         self.replicated = ([p for p in model.parameters() if p is not model._table() and p.requires_grad]
@@ -305,9 +385,20 @@ class TrainRunner:
             if self._gstep is not None:
                 self._gstep.check()            # end of the epoch: also a run / tail shorter than a flush interval is checked
             self.scheduler.step()
-            mrr, hit = evaluate(self.model, self.test_loader, self.device)
+            metrics = None
+            if self.eval_cutoffs:
+                metrics = evaluate(self.model, self.test_loader, self.device, method=self.eval_method,
+                                   cutoffs=sorted(set(self.eval_cutoffs) | {20}))
+                mrr, hit = metrics['mrr@20'], metrics['hit@20']
+            else:
+                mrr, hit = evaluate(self.model, self.test_loader, self.device, method=self.eval_method)
             self._print(f'Epoch {self.epoch}: MRR = {mrr * 100:.3f}%, Hit = {hit * 100:.3f}%')
-            self._emit(kind='epoch', epoch=self.epoch, mrr=mrr, hit=hit)
+            if metrics is not None:
+                self._print('         ' + ', '.join(f'{n}@{k} = {metrics["%s@%d" % (key, k)] * 100:.3f}%' for k in self.eval_cutoffs
+                                                   for n, key in (('HR', 'hit'), ('MRR', 'mrr'), ('NDCG', 'ndcg'))))
+                self._emit(kind='epoch', epoch=self.epoch, mrr=mrr, hit=hit, metrics=metrics)
+            else:
+                self._emit(kind='epoch', epoch=self.epoch, mrr=mrr, hit=hit)
             stop = False
             if mrr < max_mrr and hit < max_hit:
                 bad_counter += 1

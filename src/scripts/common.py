@@ -20,6 +20,18 @@ DEFAULTS = {
 }
 
 
+def _cutoffs(text):
+    ks = tuple(int(k) for k in text.split(',') if k.strip())
+    if not ks or min(ks) < 1:
+        raise argparse.ArgumentTypeError('expected positive cutoffs separated by commas, e.g. 5,10,20')
+    return ks
+
+
+def eval_options(args):
+    """the TrainRunner keywords of --eval-method / --eval-cutoffs"""
+    return dict(eval_method=args.eval_method, eval_cutoffs=args.eval_cutoffs)
+
+
 def parse(model):
     d = DEFAULTS[model]
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -51,6 +63,12 @@ def parse(model):
     p.add_argument('--gpus', type=int, default=int(os.environ.get('SREC_GPUS', '1')),
                    help='(not in the reference) train on this many GPUs of the node: item table row-sharded over them (RCCL), '
                         'encoder replicated, every rank encoding its slice of each --batch-size batch (same loss as one GPU)')
+    p.add_argument('--eval-method', default='topk', choices=['topk', 'rank'],
+                   help='(not in the reference) topk: the reference evaluation (MRR@20 / HR@20 from the 20 best items); rank: the '
+                        "label's rank among ALL items in one fused pass - any cutoff, and no (B, V) score matrix for --extra / "
+                        '--fusion either (with --extra: sessions of at most 64 distinct items)')
+    p.add_argument('--eval-cutoffs', type=_cutoffs, default=None, metavar='K1,K2,...',
+                   help='(not in the reference) also report HR / MRR / NDCG at these cutoffs after every epoch, e.g. 5,10,20')
     if model == 'MSGIFSR':
         p.add_argument('--order', type=int, default=3, help='order of msg')
         p.add_argument('--reducer', type=str, default='mean', help='method for reducer')
@@ -58,6 +76,8 @@ def parse(model):
         p.add_argument('--extra', action='store_true', help='whether use REnorm.')
         p.add_argument('--fusion', action='store_true', help='whether use IFR.')
     args = p.parse_args()
+    if args.eval_method == 'topk' and args.eval_cutoffs and max(args.eval_cutoffs) > 32:
+        p.error('--eval-cutoffs above 32 need --eval-method rank (the top-K evaluation keeps at most 32 items per session)')
     if int(os.environ.get('RANK', '0')) == 0:
         print(args)
     return args
@@ -230,7 +250,7 @@ def run(model_name):
     runner = TrainRunner(args.dataset_dir, model, train_loader, test_loader, device=device, lr=args.lr,
                          weight_decay=args.weight_decay, patience=args.patience, checkpoint=args.checkpoint,
                          hooks=[_jsonl(args.metrics_log)] if args.metrics_log and rank == 0 else (),
-                         graph=False if args.no_graph else 'auto', shard=shard)
+                         graph=False if args.no_graph else 'auto', shard=shard, **eval_options(args))
     print('start training')
     mrr, hit = runner.train(args.epochs, args.log_interval)
     if runner.graph_steps:
