@@ -986,9 +986,7 @@ class VocabParallel:
 
     def ops_flush(self):
         from . import ops
-        # not final: the step-scalar rider stays for the end of the backward - backward nodes still to run re-derive their
-        # dropout masks from the step counter it advances
-        ops.flush_deferred()
+        ops.flush_deferred()                           # (the mid-backward flush: the step-scalar rider stays, stepq.StepQueue)
 
     def sync_replicated_grads(self, params, optimizer=None):
         """sum the replicated-parameter gradients over ranks in N_BUCKETS flat buckets whose layout is the same on every

@@ -114,7 +114,7 @@ class GraphedTrainStep:
                     self._capture_intake()
                     self.loss = self.model.fused_loss(*self.static_inputs, self.static_labels)
                     from . import ops as _ops
-                    if _ops.PENDING_INTAKE:
+                    if _ops.STEP.intake_pending():
                         raise RuntimeError('the model never launched the batch intake of its captured step (ops.flush_intake)')
                     # the tap and the intake's fault flag are arguments of THIS capture's launches only (see below); the
                     # optimizer's step-scalar kernel rides in the end-of-backward slab-sum launch when there is one
@@ -150,17 +150,7 @@ class GraphedTrainStep:
                 raise err
         except BaseException:
             # capture refused: nothing ran on the device, but host bookkeeping may be half advanced - undo it all
-            optimizer._frozen = None
-            self._restore(model, optimizer, snap_p, snap_b, snap_o)
-            optimizer.zero_grad(set_to_none=True)
-            from . import ops as _ops
-            del _ops.PENDING_INTAKE[:]                   # (an intake the dead capture never launched)
-            del _ops.PENDING_HYPER[:], _ops.HYPER_DONE[:]
-            sh = getattr(model, 'shard', None)
-            if sh is not None and hasattr(sh, 'abort_step'):
-                sh.abort_step()                          # early gradient buckets recorded by the dead capture never ran
-            if hasattr(optimizer, 'grad_join'):
-                optimizer.grad_join = None
+            self._discard((snap_p, snap_b, snap_o))
             raise
         # collectives captured inside the step (row-sharded table): count and payload bytes of ONE step
         self.collectives = {k: _dist.STATS[k] - c0[k] for k in c0}
@@ -249,8 +239,8 @@ class GraphedTrainStep:
         if self._mb is None:
             return
         from . import ops
-        ops.PENDING_INTAKE[:] = [(self._mb['box'][i].data_ptr(), _MAILBOX, self._mb['counter'].data_ptr(), st.buf.data_ptr(),
-                                  st.buf.numel(), self._mb['err'].data_ptr(), self._mb) for i, st in enumerate(self.static_inputs)]
+        ops.STEP.offer_intake([(self._mb['box'][i].data_ptr(), _MAILBOX, self._mb['counter'].data_ptr(), st.buf.data_ptr(),
+                                st.buf.numel(), self._mb['err'].data_ptr(), self._mb) for i, st in enumerate(self.static_inputs)])
 
     def _post(self, i, x, T):
         """entry T % _MAILBOX of input i <- (address, words, T); the batch buffer must stay untouched until the replay has
@@ -339,6 +329,23 @@ class GraphedTrainStep:
             return out
         except Exception:
             return None
+
+    def _discard(self, snap=None):
+        """host-side undo of a captured step that will not be replayed.  snap = (parameters, buffers, optimizer state) to go back
+        to: the capture died half way and host bookkeeping may be half advanced; None: it completed (nothing to restore) and
+        the ranks agreed to drop it (capture_agreed)"""
+        from . import ops
+        model, optimizer = self.model, self.opt
+        optimizer._frozen = None
+        if snap is not None:
+            self._restore(model, optimizer, *snap)
+            optimizer.zero_grad(set_to_none=True)
+        ops.STEP.abort()                                 # sums, a rider, an intake the dead capture never launched
+        sh = getattr(model, 'shard', None)
+        if sh is not None and hasattr(sh, 'abort_step'):
+            sh.abort_step()                              # early gradient buckets recorded by the dead capture never ran
+        if hasattr(optimizer, 'grad_join'):
+            optimizer.grad_join = None
 
     @staticmethod
     def _restore(model, optimizer, snap_p, snap_b, snap_o):
@@ -467,5 +474,6 @@ def capture_agreed(make, agree_min=None, retries=1, log=None):
         if ok >= 1.0:
             return gs, attempt + 1, None
         err = e if e is not None else err
-        gs = None                                        # (another rank failed: this rank's graph is dropped too)
+        if gs is not None:                               # (another rank failed: this rank's graph is dropped too)
+            gs._discard()
     return None, retries + 1, err

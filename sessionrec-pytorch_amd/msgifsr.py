@@ -329,11 +329,8 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         # every parameter of this model feeds exactly one backward node per layer / order: the slab sums that finish their
         # gradients may wait for ONE launch at the end of the backward pass.  The permission holds for the nodes created by
         # THIS forward only (they snapshot it: ops.defer_scope) and is withdrawn when the forward returns
-        ops.DEFER['on'] = bool(mg.buf.is_cuda and self.training)
-        try:
+        with ops.STEP.deferring(mg.buf.is_cuda and self.training):
             return self._session_repr(mg, tgrad)
-        finally:
-            ops.DEFER['on'] = False
 
     def _step_prologue(self, mg):
         """the operand copies of this step's weights (k-gram GRUs, the first MSHGNN layer's fc weights and its folded attention

@@ -13,6 +13,7 @@ import os
 import torch
 
 from ._lib import lib, ptr, stream
+from .stepq import StepQueue
 
 
 def _rows(t):
@@ -639,31 +640,13 @@ def permute_and_pick(x, perm, inv, picks, dyn_n=None, dyn_b=None):
     return outs[0], list(outs[1:])
 
 
-# ------------------------------------------------------------------------------------------ deferred slab sums
-# Several backward nodes end in "out = sum over R partial slabs" kernels whose results only the optimizer reads (weight
-# gradients of the row-split GEMMs).  Each is a ~5 us kernel node of the captured step whatever its size.  A node may
-# register (slabs, out) here instead of launching, and ONE launch at the end of the backward pass (autograd's
-# queue_callback) sums them all: the gradients are complete when backward() returns, as before.
-# Deferring hands autograd a gradient tensor that is not written yet, which is only safe when AccumulateGrad takes the
-# buffer over as it is: the target parameter has no gradient yet (otherwise `p.grad += out` would read the unwritten
-# buffer: a second backward before a step, zero_grad(set_to_none=False)) and no hook that reads it.  So the permission is
-# scoped twice: a model switches DEFER['on'] for the duration of ITS training forward (every parameter of it feeds exactly
-# one backward node per layer / order), the forward of a node snapshots it (ctx.defer = defer_scope()), and the backward
-# asks can_defer(ctx.defer, params) when it gets there - anything else launches the sum on the spot.
-DEFER = {'on': False}
-_DEFERRED = []
-
-
+# ------------------------------------------------------------------------------------------ deferred slab sums, riders
+# Small launches of a training step that wait to leave inside other launches (the slab sums of the backward pass, the optimizer's
+# step-scalar rider, the batch intake of a captured step): STEP owns what waits and says who may send it off when
+# (stepq.StepQueue); the launches themselves are here.
 def defer_scope():
     """snapshot for an autograd node's forward: may its backward defer its slab sums at all?"""
-    return bool(DEFER['on'])
-
-
-def drop_stale_deferred():
-    """a backward pass that raised leaves its waiting sums behind (the engine drops its callbacks): forget them before the next
-    forward - their buffers belong to a graph that is gone, and a non-empty list would keep the next pass from registering its
-    own end-of-backward callback"""
-    del _DEFERRED[:]
+    return STEP.may_defer
 
 
 def can_defer(flag, params):
@@ -676,32 +659,6 @@ def can_defer(flag, params):
         if q.grad is not None or getattr(q, '_backward_hooks', None) or getattr(q, '_post_accumulate_grad_hooks', None):
             return False
     return True
-
-
-def defer_slab_sum(part, out, ok=True, tall=False):
-    """out [n] (any shape, contiguous) = sum over the leading dimension of part [R, n...]: now, or (ok) deferred to the
-    end of the running backward pass.  tall: few columns, hundreds of rows (bias partials)"""
-    if not ok:
-        _launch_slab_sums([(part, out, tall)])
-        return
-    if not _DEFERRED:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_flush_final)
-        except RuntimeError:                        # not inside a backward pass: nothing to wait for
-            _launch_slab_sums([(part, out, tall)])
-            return
-    # (an ALIAS of out: autograd takes a returned gradient as it is only when nothing else refers to the tensor object -
-    #  with a second reference AccumulateGrad would clone it, before the sum has been written)
-    _DEFERRED.append((part, out.detach(), tall))
-
-
-# the optimizer's step-scalar launch as a rider of the END-of-backward slab-sum launch of a captured step (optim.FusedAdam.hyper_rider
-# puts the arguments of srec_adam_hyper_multi here before the backward pass; flush_deferred(final=True) takes them along and notes
-# which slots it advanced in HYPER_DONE; FusedAdam.launch then skips its own launch).  Only the end-of-backward flush may take it: the
-# kernel advances the (0, 0) step counter the dropout masks are keyed by, and a backward node that runs after a mid-backward flush
-# (dist.VocabParallel.bucket_ready) re-derives its forward's masks from that counter
-PENDING_HYPER = []
-HYPER_DONE = []
 
 
 def _launch_slab_sums(tasks, rider=None):
@@ -726,22 +683,15 @@ def _launch_slab_sums(tasks, rider=None):
                                         _ct.addressof(a_t), _ct.addressof(a_w), _ct.addressof(a_l), stream())
 
 
-def flush_deferred(final=False):
-    """launch the waiting slab sums.  final: the backward pass is complete (its end-of-backward callback, the optimizer) - only
-    then does the step-scalar rider leave with them; a flush from inside the backward leaves PENDING_HYPER alone"""
-    if _DEFERRED:
-        tasks = list(_DEFERRED)
-        _DEFERRED.clear()
-        pend = PENDING_HYPER.pop() if (final and PENDING_HYPER) else None
-        if final:
-            del PENDING_HYPER[:]
-        _launch_slab_sums(tasks, pend[0] if pend is not None else None)
-        if pend is not None:
-            HYPER_DONE[:] = [pend[1]]
+def _launch_intake(box, M, counter, dst, cap, err):
+    lib.srec_copy_words_mailbox(box, M, counter, dst, cap, err, stream())
 
 
-def _flush_final():
-    flush_deferred(final=True)
+STEP = StepQueue(_launch_slab_sums, _launch_intake)
+defer_slab_sum = STEP.defer_slab_sum
+flush_deferred = STEP.flush                  # (from inside a backward pass; its end: STEP.finish)
+drop_stale_deferred = STEP.drop_stale
+flush_intake = STEP.flush_intake             # (where a model first reads its batch on the device: the lookup)
 
 
 # ------------------------------------------------------------------------------------------ gradient arenas
@@ -2856,18 +2806,7 @@ class StepPrepDesc(_ct.Structure):
                 ('box_cap', _ct.c_long), ('box_err', _ct.c_void_p)]
 
 
-# graph.GraphedTrainStep: the mailbox intake of the step being captured, (mailbox, M, counter, dst, cap, err) as srec_copy_words_mailbox
-# takes them, waiting to leave with the model's prologue launch (or on its own, ahead of the first read of the batch: flush_intake)
-PENDING_INTAKE = []
 STEP_PROLOGUE = os.environ.get('SREC_STEP_PROLOGUE', '1') != '0'     # (tests / A-B runs: 0 = the one-launch-per-reader sequence)
-
-
-def flush_intake():
-    """launch a pending batch intake on its own: called where a model first reads its batch on the device (the lookup) - a model
-    with a prologue launch (MSGIFSR) has taken it along before"""
-    while PENDING_INTAKE:
-        box, M, counter, dst, cap, err = PENDING_INTAKE.pop(0)[:6]
-        lib.srec_copy_words_mailbox(box, M, counter, dst, cap, err, stream())
 
 
 def step_prologue(w16=(), gru=(), head=(), fold=None):
@@ -2905,8 +2844,7 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
         hd = plan.fill(HgDesc(), small, lay, None, None, flat, None, None)
         q.hg = _ct.addressof(hd)
         keep.append((hd, flat))
-    box = PENDING_INTAKE.pop() if PENDING_INTAKE else None           # (one intake rides along; others leave ahead of it)
-    flush_intake()
+    box = STEP.take_intake()                       # (one intake of a captured step rides along; others leave ahead of it)
     if box is not None:
         q.mailbox, q.M, q.counter, q.box_dst, q.box_cap, q.box_err = box[:6]
     lib.srec_step_prep(_ct.addressof(q), stream())

@@ -173,7 +173,7 @@ class FusedAdam(torch.optim.Optimizer):
     def _work(self):
         """[(group idx, group, [(p, g, state)])] for every parameter that has a gradient now"""
         from . import ops
-        ops.flush_deferred(final=True)        # (normally already done by the end-of-backward callback)
+        ops.STEP.finish()                     # (normally already done by the end-of-backward callback)
         table, tgrad, _ = self._table_info()
         zero_ids = {}
         if self.model is not None and hasattr(self.model, 'zero_grad_params'):
@@ -219,33 +219,34 @@ class FusedAdam(torch.optim.Optimizer):
                     ent['cfg_host'] = cfg
         return work
 
+    def _hyper_args(self, ents, tap, skip):
+        """-> (arguments of srec_adam_hyper_multi for the slots `ents` without the stream, the arrays they point into)"""
+        n = len(ents)
+        arr = _ct.c_void_p * n
+        cs, cf, hy = (arr(*[e[k].data_ptr() for e in ents]) for k in ('counter', 'cfg', 'hyper'))
+        first = self._hyper.get((0, 0)) if isinstance(self._hyper, dict) else None
+        if tap is not None and first is not None and any(e is first for e in ents):
+            tapped = (ptr(first['counter']), ptr(tap[0]), ptr(tap[1]), tap[1].numel())
+        else:
+            tapped = (None, None, None, 0)
+        return (n, _ct.addressof(cs), _ct.addressof(cf), _ct.addressof(hy)) + tapped + (ptr(skip),), (cs, cf, hy, tap, skip)
+
     def hyper_rider(self, tap=None, skip=None):
         """Before the backward pass of a CAPTURED step: hand the step-scalar launch of the coming launch() to the end-of-backward
-        slab-sum launch (ops.PENDING_HYPER -> srec_sum_slabs_multi_hyper: one workgroup more there, one ~6 us graph node less).
+        slab-sum launch (ops.STEP -> srec_sum_slabs_multi_hyper: one workgroup more there, one ~6 us graph node less).
         The slots are those the eager warm-up step advanced (_used_keys); launch() checks that the rider advanced exactly the slots
         of its work list and raises otherwise (the capture is then refused, nothing has run).  Without waiting slab sums the
         rider is never taken and launch() runs its own kernel as always."""
         from . import ops
-        del ops.PENDING_HYPER[:], ops.HYPER_DONE[:]
+        ops.STEP.rider_result()                                 # (nothing of an earlier step stays)
         keys = sorted(getattr(self, '_used_keys', ()) or ())
         if not keys or len(keys) > 16 or not isinstance(getattr(self, '_hyper', None), dict):
             return False
-        ents = []
-        for gi, off in keys:
-            ent = self._hyper.get((gi, off))
-            if ent is None or ent.get('cfg_host') is None:
-                return False
-            ents.append(ent)
-        n = len(ents)
-        arr = _ct.c_void_p * n
-        cs, cf, hy = (arr(*[e[k].data_ptr() for e in ents]) for k in ('counter', 'cfg', 'hyper'))
-        first = self._hyper.get((0, 0))
-        if tap is not None and first is not None and any(e is first for e in ents):
-            args = (n, _ct.addressof(cs), _ct.addressof(cf), _ct.addressof(hy), ptr(first['counter']), ptr(tap[0]), ptr(tap[1]),
-                    tap[1].numel(), ptr(skip))
-        else:
-            args = (n, _ct.addressof(cs), _ct.addressof(cf), _ct.addressof(hy), None, None, None, 0, ptr(skip))
-        ops.PENDING_HYPER[:] = [(args, frozenset(keys), (cs, cf, hy, tap, skip))]          # (last: kept alive until the launch)
+        ents = [self._hyper.get(k) for k in keys]
+        if any(ent is None or ent.get('cfg_host') is None for ent in ents):
+            return False
+        args, keep = self._hyper_args(ents, tap, skip)
+        ops.STEP.offer_rider(args, keys, keep)
         return True
 
     def launch(self, work, tap=None, skip=None):
@@ -254,6 +255,8 @@ class FusedAdam(torch.optim.Optimizer):
         ring; given per call, by the captured launch only - never optimizer state that outlives its graph);
         skip = device int32: non-zero turns the whole step into the identity (srec_adam_hyper_multi; the batch-intake fault
         flag of a captured step)."""
+        from . import ops as _ops
+        done = _ops.STEP.rider_result()                         # the slots a rider of this step has advanced already, or None
         table, tgrad, st = self._table_info()
         model = self.model
         T = getattr(self, '_T', 0)
@@ -268,24 +271,12 @@ class FusedAdam(torch.optim.Optimizer):
                 ents.append(ent)
                 used.add((gi, off))
         self._used_keys = used                                  # (group, step offset) slots this step advanced
-        from . import ops as _ops
-        done = _ops.HYPER_DONE.pop() if _ops.HYPER_DONE else None
-        del _ops.PENDING_HYPER[:], _ops.HYPER_DONE[:]             # (a rider nobody took: this launch does the work itself)
         if done is not None and done != frozenset(used):
             raise RuntimeError('the step scalars were advanced for other slots than this step uses (hyper_rider): %r vs %r'
                                % (sorted(done), sorted(used)))
         for i in range(0, len(ents) if done is None else 0, 16):
-            chunk = ents[i:i + 16]
-            n = len(chunk)
-            arr = _ct.c_void_p * n
-            cs, cf, hy = (arr(*[e[k].data_ptr() for e in chunk]) for k in ('counter', 'cfg', 'hyper'))
-            first = self._hyper.get((0, 0)) if isinstance(self._hyper, dict) else None
-            if tap is not None and first is not None and any(e is first for e in chunk):
-                lib.srec_adam_hyper_multi(n, _ct.addressof(cs), _ct.addressof(cf), _ct.addressof(hy), ptr(first['counter']),
-                                          ptr(tap[0]), ptr(tap[1]), tap[1].numel(), ptr(skip), stream())
-            else:
-                lib.srec_adam_hyper_multi(n, _ct.addressof(cs), _ct.addressof(cf), _ct.addressof(hy), None, None, None, 0,
-                                          ptr(skip), stream())
+            args, keep = self._hyper_args(ents[i:i + 16], tap, skip)
+            lib.srec_adam_hyper_multi(*args, stream())
         # small tensors of ALL groups that step together: groups which differ only in weight decay (fix_weight_decay: the
         # biases / norms are the same Adam with wd 0) share ONE multi-tensor launch - the kernel takes the decay per tensor
         merged = {}                          # (lr, betas, eps, slot) -> [gi of the hyper to use, wd of it, rows]

@@ -130,7 +130,7 @@ class _ScoringMixin:
         p = drop.p if isinstance(drop, nn.Dropout) and drop.training else 0.0
         # the device step counter the dropout masks of THIS model's forward are keyed by (ops.rng_args): that of its own
         # FusedAdam, or none (another optimizer: the per-call nonce alone renews the masks)
-        ops.flush_intake()          # (a captured step's batch intake that no prologue launch took along: ahead of the first read)
+        ops.flush_intake()          # (a captured step's batch intake: ahead of the first read)
         W = self._table()
         c = self.__dict__.get('_srec_rng_counter')
         if c is not None and c.device == W.device:
@@ -159,15 +159,12 @@ class _ScoringMixin:
         self._sr_ws = st['ws'][B] if (self.shard is None and ops.use_bf16_scoring(self._table().shape[1])) else None
         # every parameter of these models feeds exactly one backward node: the split-K sums of the small grouped backward
         # launches may wait for ONE launch at the end of the backward pass (ops.defer_scope; MSGIFSR switches it itself)
-        prev_defer = ops.DEFER['on']
-        if not prev_defer:
-            ops.drop_stale_deferred()          # (left behind by a backward pass that raised)
-        ops.DEFER['on'] = bool(prev_defer or (self.training and self._table().is_cuda and getattr(self, 'defer_slab_sums', True)))
+        defer = ops.STEP.may_defer or (self.training and self._table().is_cuda and getattr(self, 'defer_slab_sums', True))
         try:
-            sr = self.session_repr(*inputs, tgrad=st['tgrad'])
+            with ops.STEP.deferring(defer):
+                sr = self.session_repr(*inputs, tgrad=st['tgrad'])
         finally:
             self._sr_ws = None
-            ops.DEFER['on'] = prev_defer
         if self.shard is not None:
             return self.shard.loss(sr, self._table(), cs, labels, inv_scale)
         loss, _ = ops.score_ce(sr, self._table(), cs, labels.to(torch.int32), st['ws'][B], st['tgrad'], dynB, inv_scale,

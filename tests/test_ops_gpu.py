@@ -1651,9 +1651,9 @@ def test_deferred_sums_of_an_aborted_backward_are_forgotten(dev):
     x = torch.ones(3, device=dev, requires_grad=True)
     with pytest.raises(RuntimeError, match='boom'):
         Boom.apply(x).sum().backward()
-    assert len(ops._DEFERRED) == 1
+    assert ops.STEP.waiting() == 1
     ops.drop_stale_deferred()
-    assert len(ops._DEFERRED) == 0 and float(out.sum()) == 0.0
+    assert ops.STEP.waiting() == 0 and float(out.sum()) == 0.0
 
     class Fine(torch.autograd.Function):
         @staticmethod
@@ -1667,7 +1667,7 @@ def test_deferred_sums_of_an_aborted_backward_are_forgotten(dev):
 
     Fine.apply(x).sum().backward()
     torch.cuda.synchronize()
-    assert len(ops._DEFERRED) == 0 and float(out.sum()) == 32.0
+    assert ops.STEP.waiting() == 0 and float(out.sum()) == 32.0
 
 
 @pytest.mark.parametrize('w,ucap,nloc,proj', [(2, 256, 700, False), (8, 512, 4332, True), (5, 300, 97, True)])

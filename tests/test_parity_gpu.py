@@ -267,9 +267,9 @@ def test_two_backwards_before_one_step_accumulate_like_the_undeferred_path(dev):
                 if mode == 'separate' or not per:
                     m.zero_grad(set_to_none=True)
                 loss = m.fused_loss(mg.to(dev), lab.to(dev))
-                assert not ops.DEFER['on']             # withdrawn when the forward returns
+                assert not ops.STEP.may_defer          # withdrawn when the forward returns
                 loss.backward()
-                assert not ops._DEFERRED               # nothing left pending after backward()
+                assert ops.STEP.waiting() == 0         # nothing left pending after backward()
                 per.append({k: p.grad.detach().clone() for k, p in m.named_parameters()
                             if p.grad is not None and p is not m._table()})
             grads.append(per)
