@@ -12,8 +12,22 @@ import os
 
 import torch
 
-from ._lib import lib, ptr, stream
+from ._lib import CONST, STRUCTS, lib, ptr, ptr_array, stream
 from .stepq import StepQueue
+
+# host descriptor structs and capacity limits of the launchers: bound from include/srec_hg.h (_lib.parse_structs), never retyped
+HgDesc = STRUCTS['srec_hg_desc']
+GemmGroup = STRUCTS['srec_gemm_group']
+GemmGroup16 = STRUCTS['srec_gemm16_group']
+GemmF32Group = STRUCTS['srec_gemm_f32_group']
+GruStepDesc = STRUCTS['srec_gru_step_desc']
+GruFusedDesc = STRUCTS['srec_gru_fused_desc']
+GruFusedBwdDesc = STRUCTS['srec_gru_fused_bwd_desc']
+HeadDesc = STRUCTS['srec_head_desc']
+HeadBwdDesc = STRUCTS['srec_head_bwd_desc']
+StepPrepDesc = STRUCTS['srec_step_prep_desc']
+G16_MAXP, GEMM32_MAXP, GRU_MAXP = CONST['SREC_G16_MAXP'], CONST['SREC_GEMM32_MAXP'], CONST['SREC_GRU_MAXP']
+HEAD_MAXH, HEAD_MAXW = CONST['SREC_HEAD_MAXH'], CONST['SREC_HEAD_MAXW']
 
 
 def _rows(t):
@@ -206,8 +220,8 @@ def _linear_backward_group(gy, xs, ws, gws, need_x, need_b, dyn, defer=False):
         probs.append(('tn', _ones4(M, gy.device)[:M], gy, sums, None, dyn, 0.0))
         gb = sums[0]
     outs = ([gw for gw in gws if gw is not None] + ([sums] if need_b else [])) if defer else None
-    for c in range(0, len(probs), 16):
-        gemm_f32_group(probs[c:c + 16], defer=outs)
+    for c in range(0, len(probs), GEMM32_MAXP):
+        gemm_f32_group(probs[c:c + GEMM32_MAXP], defer=outs)
     return gxs, gb
 
 
@@ -1014,18 +1028,6 @@ def seg_attn(U, Vq, we, X, seg, dynB=None):
     return SegAttn.apply(U, Vq, we, X, seg, dynB)
 
 
-class GemmF32Group(_ct.Structure):
-    """host mirror of srec_gemm_f32_group (include/srec_hg.h)"""
-    _fields_ = [('np', _ct.c_int),
-                ('A', _ct.c_void_p * 16), ('a_rs', _ct.c_int * 16), ('a_cs', _ct.c_int * 16),
-                ('B', _ct.c_void_p * 16), ('b_rs', _ct.c_int * 16), ('b_cs', _ct.c_int * 16),
-                ('C', _ct.c_void_p * 16), ('ldc', _ct.c_int * 16), ('bias', _ct.c_void_p * 16),
-                ('M', _ct.c_int * 16), ('N', _ct.c_int * 16), ('K', _ct.c_int * 16),
-                ('dyn', _ct.c_void_p * 16), ('dyn_mode', _ct.c_int * 16),
-                ('alpha', _ct.c_float * 16), ('beta', _ct.c_float * 16), ('nsplit', _ct.c_int * 16), ('ws', _ct.c_void_p),
-                ('split3', _ct.c_int)]
-
-
 def gemm_f32_group(probs, split3=False, defer=None):
     """defer: a list of output tensors - the split-K slab sums of the group's weight-gradient ('tn', whole contiguous output
     tensor) problems that write one of them join the end-of-backward slab-sum launch (defer_slab_sum) instead of a reduce
@@ -1034,7 +1036,7 @@ def gemm_f32_group(probs, split3=False, defer=None):
     hi / lo bf16 splits on the bf16 matrix pipe, ~2^-17 relative).  A problem is
     (kind, a, b, out, bias, dyn, beta):  'nt' out[M,N] = a[M,K] b[N,K]^T + bias (dyn clamps M);  'nn' out[M,K] = a[M,N] b[N,K]
     (dyn clamps M);  'tn' out[N,K] = a[M,N]^T b[M,K] (dyn clamps the reduction rows M).  (+ beta * out)"""
-    assert 0 < len(probs) <= 16
+    assert 0 < len(probs) <= GEMM32_MAXP
     g = GemmF32Group()
     g.np, g.split3 = len(probs), int(split3)
     for p, (kind, a, b, out, bias, dyn, beta) in enumerate(probs):
@@ -1066,7 +1068,7 @@ def gemm_f32_group(probs, split3=False, defer=None):
             # next group); problems that may not wait (cnt[p] = 0 on entry: accumulating / clamped / strided outputs, outputs
             # somebody reads during the backward pass) keep their reduce launch
             ws = torch.empty(need, device=dev, dtype=torch.float32)
-            off, cnt = (_ct.c_long * 16)(), (_ct.c_int * 16)(*[int(o) for o in ok])
+            off, cnt = (_ct.c_long * GEMM32_MAXP)(), (_ct.c_int * GEMM32_MAXP)(*[int(o) for o in ok])
             lib.srec_gemm_f32_group_run_defer(_ct.addressof(g), ptr(ws), need, _ct.addressof(off), _ct.addressof(cnt), stream())
             for p, (kind, a, b, out, bias, dyn, beta) in enumerate(probs):
                 if off[p] >= 0 and cnt[p] > 1:
@@ -1219,14 +1221,14 @@ _HEAD_WF_CACHE = {}    # (data_ptr, shape, trans) -> hi / lo fragment-major bf16
 
 
 def _head_wfrag_args(ws, trans):
-    """output buffers + the HOST argument arrays of srec_head_wfrag for <= 16 weights (kept alive by the caller across the call)"""
+    """output buffers + the HOST argument arrays of srec_head_wfrag for <= SREC_HEAD_MAXW weights (kept alive by the caller across the call)"""
     m = len(ws)
-    assert 0 < m <= 16
+    assert 0 < m <= HEAD_MAXW
     for w in ws:
         assert w.is_contiguous() and w.dtype == torch.float32
     bufs = [torch.empty(2 * w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    arr, ints = _ct.c_void_p * m, _ct.c_int * m
-    return bufs, (arr(*[w.data_ptr() for w in ws]), arr(*[b.data_ptr() for b in bufs]), ints(*[w.shape[0] for w in ws]),
+    ints = _ct.c_int * m
+    return bufs, (ptr_array(ws), ptr_array(bufs), ints(*[w.shape[0] for w in ws]),
                   ints(*[w.shape[1] for w in ws]), ints(*[int(t) for t in trans]))
 
 
@@ -1240,27 +1242,13 @@ def head_wfrag(ws, trans):
             todo.append(i)
         else:
             out[i] = c
-    for c0 in range(0, len(todo), 16):
-        ch = todo[c0:c0 + 16]
+    for c0 in range(0, len(todo), HEAD_MAXW):
+        ch = todo[c0:c0 + HEAD_MAXW]
         bufs, args = _head_wfrag_args([ws[i] for i in ch], [trans[i] for i in ch])
         lib.srec_head_wfrag(len(ch), *[_ct.addressof(a) for a in args], stream())
         for i, b in zip(ch, bufs):
             out[i] = _HEAD_WF_CACHE[(ws[i].data_ptr(), tuple(ws[i].shape), int(trans[i]))] = b
     return out
-
-
-class HeadDesc(_ct.Structure):
-    """host mirror of srec_head_desc (include/srec_hg.h)"""
-    _fields_ = ([(nm, _ct.c_int) for nm in ('nh', 'd', 'B', 'NT', 'ld_x', 'ld16', 'eps_mode')] + [('eps', _ct.c_float)] +
-                [(nm, _ct.c_void_p) for nm in ('X', 'seg', 'dynB')] +
-                [(nm, _ct.c_void_p * 4) for nm in ('cat', 'Wu_f', 'Wv_f', 'Wsr_f', 'bu', 'we', 'alpha', 'U', 'Vq', 'y', 'inv', 'y16')])
-
-
-class HeadBwdDesc(_ct.Structure):
-    """host mirror of srec_head_bwd_desc (include/srec_hg.h)"""
-    _fields_ = ([(nm, _ct.c_int) for nm in ('nh', 'd', 'B', 'NT', 'ld_x', 'ld_gy')] + [(nm, _ct.c_void_p) for nm in ('X', 'seg', 'dynB')] +
-                [(nm, _ct.c_void_p * 4) for nm in ('gy', 'y', 'inv', 'WsrT_f', 'alpha', 'U', 'Vq', 'we', 'gs', 'gcat', 'dX', 'dU',
-                                                   'dVq', 'dwp')])
 
 
 class ReadoutHeadFused(torch.autograd.Function):
@@ -1366,7 +1354,7 @@ class ReadoutHeadFused(torch.autograd.Function):
             probs.append(('tn', ones[:B], dwp, s_we, None, dB, 0.0))
             blocks.append(s_we)
             grads.append((gv, gWu, gbu, gWv, sums[4:5], gWsr))
-        per_launch = 14 if len(probs) > 16 else 16          # whole orders per launch (7 problems each)
+        per_launch = GEMM32_MAXP if len(probs) <= GEMM32_MAXP else GEMM32_MAXP // 7 * 7      # whole orders per launch (7 problems each)
         later = ([t for gr in grads for t in (gr[1], gr[3], gr[5])] + blocks) if can_defer(ctx.defer, ctx.wparams) else None
         for c in range(0, len(probs), per_launch):
             gemm_f32_group(probs[c:c + per_launch], split3=True,       # (the forward's products are 3-term splits too)
@@ -1383,7 +1371,7 @@ HEAD_FUSED_MAX_B = 8192      # session capacity of the fused read-out head kerne
 def readout_head_fused_ok(allf, per_order):
     """the fused forward applies: bf16 mode, d = hidden = output in (128, 256), <= 4 heads, contiguous weights, every query
     tensor the tagged left half of a private [B, 2 d] buffer (norm_permute_pick / permute_and_pick)"""
-    if not (allf.is_cuda and PRECISION['matmul'] == 'bf16' and 1 <= len(per_order) <= 4 and FUSED_HEAD):
+    if not (allf.is_cuda and PRECISION['matmul'] == 'bf16' and 1 <= len(per_order) <= HEAD_MAXH and FUSED_HEAD):
         return False
     D = allf.shape[1]
     if D not in (128, 256) or allf.stride(1) != 1 or allf.stride(0) % 4:
@@ -1966,44 +1954,19 @@ def gru_expand(x, gru, k, dyn_n=None, dyn_rows=None, combine=True):
                            combine)
 
 
-class GruStepDesc(_ct.Structure):
-    """host mirror of srec_gru_step_desc (include/srec_hg.h)"""
-    _fields_ = ([('np', _ct.c_int), ('d', _ct.c_int), ('n', _ct.c_int * 4), ('k', _ct.c_int * 4), ('t', _ct.c_int * 4),
-                 ('dyn', _ct.c_void_p * 4)] +
-                [(nm, _ct.c_void_p * 4) for nm in ('GI', 'GH', 'bih', 'bhh', 'Hp', 'Hn', 'Hn16', 'gates', 'X', 'out',
-                                                   'dH', 'dout', 'dGI16', 'dGH16', 'dHp', 'dX', 'bias_part')] +
-                [('part_row0', _ct.c_int * 4)])
-
-
-class GruFusedDesc(_ct.Structure):
-    """host mirror of srec_gru_fused_desc (include/srec_hg.h)"""
-    _fields_ = ([('np', _ct.c_int), ('d', _ct.c_int), ('n', _ct.c_int * 4), ('k', _ct.c_int * 4), ('dyn', _ct.c_void_p * 4)] +
-                [(nm, _ct.c_void_p * 4) for nm in ('X', 'X16', 'Wih_f', 'Whh_f', 'bih', 'bhh', 'H', 'H16', 'gates', 'out')])
-
-
-class GruFusedBwdDesc(_ct.Structure):
-    """host mirror of srec_gru_fused_bwd_desc (include/srec_hg.h)"""
-    _fields_ = ([('np', _ct.c_int), ('d', _ct.c_int), ('n', _ct.c_int * 4), ('k', _ct.c_int * 4), ('dyn', _ct.c_void_p * 4)] +
-                [(nm, _ct.c_void_p * 4) for nm in ('gates', 'H', 'dout', 'Wih_f', 'Whh_f', 'dGI16', 'dGH16', 'dX', 'bias_part')] +
-                [('part_row0', _ct.c_int * 4)])
-
-
 def gru_wfrag_t(ws):
     """fragment-major bf16 copies of GRU weights [3 d, d] for the backward-data products (csrc/grufb.hip), one launch"""
     n, d = len(ws), ws[0].shape[1]
     outs = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    arr = _ct.c_void_p * n
-    a_w, a_o = arr(*[w.data_ptr() for w in ws]), arr(*[o.data_ptr() for o in outs])
+    a_w, a_o = ptr_array(ws), ptr_array(outs)
     lib.srec_gru_wfrag_t(n, _ct.addressof(a_w), _ct.addressof(a_o), d, stream())
     return outs
 
 
 def _gru_wfrag_args(ws):
-    n = len(ws)
     of = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
     ob = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    arr = _ct.c_void_p * n
-    return of, ob, (arr(*[w.data_ptr() for w in ws]), arr(*[o.data_ptr() for o in of]), arr(*[o.data_ptr() for o in ob]))
+    return of, ob, (ptr_array(ws), ptr_array(of), ptr_array(ob))
 
 
 def gru_wfrag_both(ws):
@@ -2024,14 +1987,13 @@ def gru_wfrag(ws):
         return [h[0] for h in hit]
     n, d = len(ws), ws[0].shape[1]
     outs = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    arr = _ct.c_void_p * n
-    a_w, a_o = arr(*[w.data_ptr() for w in ws]), arr(*[o.data_ptr() for o in outs])
+    a_w, a_o = ptr_array(ws), ptr_array(outs)
     lib.srec_gru_wfrag(n, _ct.addressof(a_w), _ct.addressof(a_o), d, stream())
     return outs
 
 
 def gru_fused_ok(d, P):
-    return d in (128, 256) and P <= 4 and FUSED_GRU
+    return d in (128, 256) and P <= GRU_MAXP and FUSED_GRU
 
 
 def gru_expand_fast_ok(d, reducer):
@@ -2229,8 +2191,8 @@ class GRUExpandAll(torch.autograd.Function):
             probs.append((d3, d, ns[p], segs, sl, dyn_ns[p], 0, nsp))
             if nsp > 1:
                 slabs.append((sl, gWhh[p]))
-        for i in range(0, len(probs), 16):
-            gemm16('tn', probs[i:i + 16], d3, d, d)
+        for i in range(0, len(probs), G16_MAXP):
+            gemm16('tn', probs[i:i + G16_MAXP], d3, d, d)
         # bias gradients from the partial rows
         gb = [grad_buf_pair(ctx.bparams[2 * p], ctx.bparams[2 * p + 1]) for p in range(P)]
         # the weight-gradient slab sums join the ONE end-of-backward launch (defer_slab_sum); the bias partials keep their own
@@ -2244,8 +2206,7 @@ class GRUExpandAll(torch.autograd.Function):
             for p in range(P):
                 defer_slab_sum(part[p], gb[p], True, tall=True)
         else:
-            arr = _ct.c_void_p * P
-            a_p, a_o = arr(*[t_.data_ptr() for t_ in part]), arr(*[t_.data_ptr() for t_ in gb])
+            a_p, a_o = ptr_array(part), ptr_array(gb)
             a_r = (_ct.c_int * P)(*[t_.shape[0] for t_ in part])
             lib.srec_gru_bias_final(P, _ct.addressof(a_p), _ct.addressof(a_r), 6 * d, _ct.addressof(a_o), st)
         grads = []
@@ -2596,32 +2557,6 @@ def edge_agg(x, coef, fwd_csr, bwd_csr, dyn=None):
 # ------------------------------------------------------------------------------------------ MSHGNN layer (batched)
 
 
-class HgDesc(_ct.Structure):
-    """host mirror of srec_hg_desc (include/srec_hg.h)"""
-    _T, _M, _B, _I = 4, 8, 16, 16
-    _fields_ = ([(n, _ct.c_int) for n in ('H', 'D', 'n_types', 'n_mods', 'n_blocks', 'n_inst', 'B')] +
-                [('slope', _ct.c_float), ('p16', _ct.c_int), ('dynB', _ct.c_void_p),
-                 ('row0', _ct.c_int * 4), ('ncap', _ct.c_int * 4), ('dyn_n', _ct.c_void_p * 4), ('seg', _ct.c_void_p * 4)] +
-                [(n, _ct.c_void_p * 8) for n in ('P', 'dP', 'W', 'V', 'Z', 'attn_l', 'attn_r', 'bias', 'd_attn_l', 'd_attn_r', 'd_bias')] +
-                [('xin', _ct.c_void_p * 8), ('xres', _ct.c_void_p), ('rm', _ct.c_void_p)] +
-                [(n, _ct.c_int * 16) for n in ('blk_mod', 'blk_type', 'blk_row')] +
-                [(n, _ct.c_void_p * 16) for n in ('eL', 'eR', 'wL', 'wR')] +
-                [(n, _ct.c_int * 16) for n in ('inst_mod', 'inst_sblk', 'inst_dblk')] +
-                [(n, _ct.c_void_p * 16) for n in ('in_ptr', 'in_idx', 'esrc', 'out_ptr', 'out_idx', 'edst', 'A', 'DP', 'der', 'Mk')] +
-                [('smean', _ct.c_void_p * 4), ('sess', _ct.c_void_p)] +
-                [('rm_cnt', _ct.c_void_p), ('rm_counter', _ct.c_void_p), ('rm_p', _ct.c_float), ('rm_seed', _ct.c_int),
-                 ('rm_salt', _ct.c_int)])
-
-
-class GemmGroup(_ct.Structure):
-    """host mirror of srec_gemm_group (include/srec_hg.h)"""
-    _fields_ = [('np', _ct.c_int), ('lda', _ct.c_int), ('ldb', _ct.c_int), ('ldc', _ct.c_int), ('beta', _ct.c_float),
-                ('a16', _ct.c_int), ('c16', _ct.c_int),
-                ('M', _ct.c_int * 8), ('N', _ct.c_int * 8), ('K', _ct.c_int * 8), ('nseg', _ct.c_int * 8),
-                ('A', (_ct.c_void_p * 4) * 8), ('B', (_ct.c_void_p * 4) * 8), ('C', _ct.c_void_p * 8),
-                ('dyn', _ct.c_void_p * 8)]
-
-
 def gemm_group(mode, probs, lda, ldb, ldc, beta=0.0, a16=False, c16=False):
     """probs: [(M, N, K, [(A, B), ...] segments, C, dyn)] tensors -> one srec_gemm_group_bf16 launch"""
     g = GemmGroup()
@@ -2633,21 +2568,11 @@ def gemm_group(mode, probs, lda, ldb, ldc, beta=0.0, a16=False, c16=False):
     lib.srec_gemm_group_bf16(_ct.addressof(g), mode, stream())
 
 
-class GemmGroup16(_ct.Structure):
-    """host mirror of srec_gemm16_group (include/srec_hg.h)"""
-    _fields_ = [('np', _ct.c_int), ('lda', _ct.c_int), ('ldb', _ct.c_int), ('ldc', _ct.c_int), ('beta', _ct.c_float),
-                ('c16', _ct.c_int),
-                ('M', _ct.c_int * 16), ('N', _ct.c_int * 16), ('K', _ct.c_int * 16), ('nseg', _ct.c_int * 16),
-                ('A', (_ct.c_void_p * 4) * 16), ('B', (_ct.c_void_p * 4) * 16), ('C', _ct.c_void_p * 16),
-                ('dyn', _ct.c_void_p * 16), ('koff', _ct.c_int * 16), ('nsplit', _ct.c_int * 16),
-                ('lda_p', _ct.c_int * 16), ('ldb_p', _ct.c_int * 16), ('ldc_p', _ct.c_int * 16), ('mhint', _ct.c_int * 16)]
-
-
 def gemm16(kind, probs, lda, ldb, ldc, beta=0.0, c16=False, keep_dead=False):
     """one grouped launch of the bf16-in-HBM GEMMs (csrc/gemm16.hip).  probs: [(M, N, K, [(A16, B16), ...], C, dyn)].
     kind 'nt': C [M, N] (+)= sum_s A_s [M, K] B_s [N, K]^T (c16: bf16 output);  'tn': C [M, N] = sum_s A_s [K, M]^T B_s [K, N]
     (reduction over the K rows, clamped by dyn)."""
-    assert 0 < len(probs) <= 16
+    assert 0 < len(probs) <= G16_MAXP
     g = GemmGroup16()
     g.np, g.lda, g.ldb, g.ldc, g.beta, g.c16 = len(probs), lda, ldb, ldc, beta, int(c16) | (2 if keep_dead else 0)
     for p, pr in enumerate(probs):
@@ -2679,9 +2604,7 @@ def _weights_bf16_args(ws, transposed=True):
     dev = ws[0].device
     w16 = [torch.empty(w.shape, device=dev, dtype=torch.bfloat16) for w in ws]
     wt16 = [torch.empty(w.shape[1], w.shape[0], device=dev, dtype=torch.bfloat16) if transposed else None for w in ws]
-    arr = _ct.c_void_p * n
-    return w16, wt16, (arr(*[w.data_ptr() for w in ws]), arr(*[w.data_ptr() for w in w16]),
-                       arr(*[(w.data_ptr() if w is not None else None) for w in wt16]),
+    return w16, wt16, (ptr_array(ws), ptr_array(w16), ptr_array(wt16),
                        (_ct.c_int * n)(*[w.shape[0] for w in ws]), (_ct.c_int * n)(*[w.shape[1] for w in ws]))
 
 
@@ -2708,7 +2631,8 @@ class HgPlan:
         self.layer_id = 0                                 # dropout-mask salt: distinct per MSHGNN layer of a model
         self.H, self.D, self.slope, self.B, self.dynB = H, D, slope, B, dynB
         self.types, self.modules, self.blocks, self.insts = types, modules, blocks, insts
-        assert len(types) <= 4 and len(modules) <= 8 and len(blocks) <= 16 and len(insts) <= 16
+        assert (len(types) <= CONST['SREC_HG_MAXT'] and len(modules) <= CONST['SREC_HG_MAXM'] and
+                len(blocks) <= CONST['SREC_HG_MAXB'] and len(insts) <= CONST['SREC_HG_MAXI'])
 
     def pieces(self, m):
         """[(row offset inside module m's projection, first stacked row, rows, dyn)] - one piece per node type the module
@@ -2796,16 +2720,6 @@ _HG_WS = {}
 
 
 # ---- the step's prologue launch (csrc/prep.hip) ----------------------------------------------------------------------------
-class StepPrepDesc(_ct.Structure):
-    """host mirror of srec_step_prep_desc (include/srec_hg.h)"""
-    _fields_ = [('hg', _ct.c_void_p), ('n_w16', _ct.c_int), ('w16_W', _ct.c_void_p), ('w16_out', _ct.c_void_p), ('w16_T', _ct.c_void_p),
-                ('w16_R', _ct.c_void_p), ('w16_C', _ct.c_void_p), ('n_gru', _ct.c_int), ('gru_d', _ct.c_int), ('gru_W', _ct.c_void_p),
-                ('gru_fwd', _ct.c_void_p), ('gru_bwd', _ct.c_void_p), ('n_head', _ct.c_int), ('head_W', _ct.c_void_p),
-                ('head_out', _ct.c_void_p), ('head_rows', _ct.c_void_p), ('head_cols', _ct.c_void_p), ('head_trans', _ct.c_void_p),
-                ('mailbox', _ct.c_void_p), ('M', _ct.c_int), ('counter', _ct.c_void_p), ('box_dst', _ct.c_void_p),
-                ('box_cap', _ct.c_long), ('box_err', _ct.c_void_p)]
-
-
 STEP_PROLOGUE = os.environ.get('SREC_STEP_PROLOGUE', '1') != '0'     # (tests / A-B runs: 0 = the one-launch-per-reader sequence)
 
 
@@ -2813,8 +2727,8 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
     """Everything a forward pass does to its WEIGHTS before it reads the first row of its batch, plus a pending batch intake, as
     ONE launch (srec_step_prep, csrc/prep.hip) instead of one small launch in front of each reader:
       w16:  fp32 matrices (<= 8) -> bf16 + transposed bf16 copies, taken by weights_bf16 (HGATLayer);
-      gru:  GRU weights [3 d, d] (<= 8) -> both fragment-major layouts, taken by gru_wfrag_both / gru_wfrag (GRUExpandAll);
-      head: [(W, trans)] (<= 16) -> hi / lo fragment-major copies, found by head_wfrag (ReadoutHeadFused) in its per-step cache;
+      gru:  GRU weights [3 d, d] (<= 2 SREC_GRU_MAXP) -> both fragment-major layouts, taken by gru_wfrag_both / gru_wfrag (GRUExpandAll);
+      head: [(W, trans)] (<= SREC_HEAD_MAXW) -> hi / lo fragment-major copies, found by head_wfrag (ReadoutHeadFused) in its per-step cache;
       fold: (plan, params) of an MSHGNN layer call -> plan.pre = its scratch with V / the bias sums written (HGATLayer).
     Purely an optimisation: a reader that does not find its copies makes them itself."""
     q, keep = StepPrepDesc(), []
@@ -2824,13 +2738,13 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
         q.n_w16 = len(w16)
         q.w16_W, q.w16_out, q.w16_T, q.w16_R, q.w16_C = (_ct.addressof(a) for a in args)
         keep.append(args)
-    gru = list(gru)[:8]
+    gru = list(gru)[:2 * GRU_MAXP]
     if gru:
         of, ob, args = _gru_wfrag_args(gru)
         q.n_gru, q.gru_d = len(gru), gru[0].shape[1]
         q.gru_W, q.gru_fwd, q.gru_bwd = (_ct.addressof(a) for a in args)
         keep.append(args)
-    head = [(w, int(t)) for w, t in head if (w.data_ptr(), tuple(w.shape), int(t)) not in _HEAD_WF_CACHE][:16]
+    head = [(w, int(t)) for w, t in head if (w.data_ptr(), tuple(w.shape), int(t)) not in _HEAD_WF_CACHE][:HEAD_MAXW]
     if head:
         hb, args = _head_wfrag_args([w for w, _ in head], [t for _, t in head])
         q.n_head = len(head)
@@ -2946,9 +2860,9 @@ class HGATLayer(torch.autograd.Function):
             live = getattr(plan, 'live', {})             # host-side live row counts per type start (tile heuristics only)
             probs = [(nc, HD, D, [(xin16(m)[t0:t0 + nc], w16[m])], P[m][o:o + nc], dyn_t, 0, 1, None, live.get(t0, 0))
                      for m in range(nm) for (o, t0, nc, dyn_t) in plan.pieces(m)]
-            for i in range(0, len(probs), 16):
+            for i in range(0, len(probs), G16_MAXP):
                 # rows past a type's live count are never read (every hgat.hip kernel walks the live prefix only)
-                gemm16('nt', probs[i:i + 16], D, D, HD, c16=True, keep_dead=True)
+                gemm16('nt', probs[i:i + G16_MAXP], D, D, HD, c16=True, keep_dead=True)
             g16 = (x16, wt16)
         elif grouped:
             gemm_group(0, [(nr, HD, D, [(xin(m)[r0:r0 + nr], params[4 * m])], P[m], dyn)
@@ -3061,7 +2975,7 @@ class HGATLayer(torch.autograd.Function):
                     gemm_nn(dP[m], _rows(params[4 * m]), tgt[r0:r0 + nr], dyn, 1 if dyn is not None else 0, beta=1.0)
         while pend:
             beta = pend[0][1]
-            batch = [pr for pr, b in pend if b == beta][:16]
+            batch = [pr for pr, b in pend if b == beta][:G16_MAXP]
             pend = [(pr, b) for pr, b in pend if not any(pr is q for q in batch)]
             gemm16('nt', batch, HD, HD, D, beta=beta)
         if late_dx:
@@ -3086,8 +3000,8 @@ class HGATLayer(torch.autograd.Function):
                 for pi, (o, t0, nc, dyn_t) in enumerate(pcs[m]):
                     tgt = gWs[m] if m not in slabs else slabs[m][pi:pi + 1]
                     probs.append((HD, D, nc, [(dP[m][o:o + nc], xin16(m)[t0:t0 + nc])], tgt, dyn_t, 0, 1))
-            for i in range(0, len(probs), 16):
-                gemm16('tn', probs[i:i + 16], HD, D, D)
+            for i in range(0, len(probs), G16_MAXP):
+                gemm16('tn', probs[i:i + G16_MAXP], HD, D, D)
             if multi and can_defer(ctx.defer, [ctx.wparams[m] for m in multi]):
                 for i, m in enumerate(multi):
                     defer_slab_sum(slabs[m], gWm[i])

@@ -16,14 +16,9 @@ import ctypes as _ct
 
 import torch
 
-from ._lib import lib, ptr, stream
+from ._lib import STRUCTS, lib, ptr, ptr_array, stream
 
-
-class _AdamMultiDesc(_ct.Structure):
-    """srec_adam_multi_desc (include/srec.h)"""
-    _fields_ = [('nt', _ct.c_int), ('use_wd', _ct.POINTER(_ct.c_int)), ('numel', _ct.POINTER(_ct.c_long)),
-                ('p', _ct.POINTER(_ct.c_void_p)), ('g', _ct.POINTER(_ct.c_void_p)), ('m', _ct.POINTER(_ct.c_void_p)),
-                ('v', _ct.POINTER(_ct.c_void_p))]
+_AdamMultiDesc = STRUCTS['srec_adam_multi_desc']      # bound from include/srec.h; its members are HOST arrays, passed by address
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -222,8 +217,7 @@ class FusedAdam(torch.optim.Optimizer):
     def _hyper_args(self, ents, tap, skip):
         """-> (arguments of srec_adam_hyper_multi for the slots `ents` without the stream, the arrays they point into)"""
         n = len(ents)
-        arr = _ct.c_void_p * n
-        cs, cf, hy = (arr(*[e[k].data_ptr() for e in ents]) for k in ('counter', 'cfg', 'hyper'))
+        cs, cf, hy = (ptr_array([e[k] for e in ents]) for k in ('counter', 'cfg', 'hyper'))
         first = self._hyper.get((0, 0)) if isinstance(self._hyper, dict) else None
         if tap is not None and first is not None and any(e is first for e in ents):
             tapped = (ptr(first['counter']), ptr(tap[0]), ptr(tap[1]), tap[1].numel())
@@ -358,11 +352,10 @@ class FusedAdam(torch.optim.Optimizer):
         for key, (gi, _, rows) in merged.items():    # every small tensor that steps together in ONE launch (by-value descriptor)
             slot = key[4]
             nt = len(rows)
-            arr = (_ct.c_void_p * nt)
-            a_wd, a_n = (_ct.c_int * nt)(*[r[3] for r in rows]), (_ct.c_long * nt)(*[r[0].numel() for r in rows])
-            a_p, a_g = arr(*[r[0].data_ptr() for r in rows]), arr(*[r[1].data_ptr() for r in rows])
-            a_m, a_v = arr(*[r[2]['exp_avg'].data_ptr() for r in rows]), arr(*[r[2]['exp_avg_sq'].data_ptr() for r in rows])
-            desc = _AdamMultiDesc(nt, a_wd, a_n, a_p, a_g, a_m, a_v)
+            keep = [(_ct.c_int * nt)(*[r[3] for r in rows]), (_ct.c_long * nt)(*[r[0].numel() for r in rows]),
+                    ptr_array([r[0] for r in rows]), ptr_array([r[1] for r in rows]),
+                    ptr_array([r[2]['exp_avg'] for r in rows]), ptr_array([r[2]['exp_avg_sq'] for r in rows])]
+            desc = _AdamMultiDesc(nt, *[_ct.addressof(a) for a in keep])       # (keep: alive across the call)
             hyper = self._buffers(gi, slot, rows[0][0].device)['hyper']
             lib.srec_adam_multi(_ct.addressof(desc), ptr(hyper), stream())
         if tgrad is not None:

@@ -382,7 +382,7 @@ def _multi_desc(tensors, use_wd):
     arr = ctypes.c_void_p * nt
     keep = [(ctypes.c_int * nt)(*use_wd), (ctypes.c_long * nt)(*[t[0].numel() for t in tensors])]
     keep += [arr(*[t[k].data_ptr() for t in tensors]) for k in range(4)]
-    desc = optim._AdamMultiDesc(nt, *keep)
+    desc = optim._AdamMultiDesc(nt, *[ctypes.addressof(a) for a in keep])
     return desc, keep
 
 
