@@ -345,14 +345,14 @@ int srec_adam_rows_proj(float* W, const float* G, float* M, float* V, int n, int
 /* ---- MSGIFSR MSHGNN layer, all relations of both HeteroGraphConvs in one batched pass (hgat.hip) ------------------
  * Replaces msgifsr.py:70-89 (conv1(g) + conv2(reverse g), relation sum, head max, + session mean) around the fc GEMMs
  * of the GAT modules; `desc` points to a host srec_hg_desc (srec_hg.h).
- *   fwd: the caller has filled P[m] = x[rows of m] fc_m^T (p16 bit 3: and run srec_hg_fold); writes out[NT, D] = max_h(sum_rel rst + bias + n_rel x) +
+ *   fwd: the caller has filled P[m] = x[rows of m] fc_m^T (p16 SREC_HG_FOLDED: and run srec_hg_fold); writes out[NT, D] = max_h(sum_rel rst + bias + n_rel x) +
  *        session mean of x, arg[NT, D] (winning head), and the saved A / eL / eR.
  *   bwd: g = d out; writes dx = n_rel g + session-mean term (the caller then accumulates dP[m] fc_m into it), dP[m],
  *        d_attn_l / d_attn_r / d_bias of every module.  ws: srec_hg_ws_floats() floats of scratch. */
 int srec_hg_ws_floats(const void* desc, long* n_floats);
 int srec_hg_fwd(const void* desc, const float* x, int ld_x, float* out, int ld_out, unsigned char* arg, void* stream);
 /* the weight-only part of srec_hg_fwd on its own: V[m] (attention vectors folded into fc_m, gatconv.py:285-292 as a product over x)
- * and the per-type bias sums of desc.  srec_hg_fwd runs it itself unless bit 3 of desc.p16 says it was done since the weights
+ * and the per-type bias sums of desc.  srec_hg_fwd runs it itself unless SREC_HG_FOLDED in desc.p16 says it was done since the weights
  * last changed - by this call or by the step's prologue launch: */
 int srec_hg_fold(const void* desc, void* stream);
 /* desc: HOST srec_step_prep_desc (srec_hg.h): fold + bf16 weight copies + GRU / head fragment copies + mailbox intake, one launch
@@ -373,7 +373,7 @@ int srec_hg_drop_prep16(const float* x, const float* cnt, int rows, int D, float
  * salt, the mask tensor is then neither written nor read) */
 int srec_hg_drop_merge(const float* t, int S, const float* ms, long n, float* dx, float p, int seed, const int* counter,
                        int salt, void* stream);
-/* feature-dropout calls: desc.p16 bit 2 makes srec_hg_bwd leave dx alone; after the caller's backward-data GEMMs
+/* feature-dropout calls: SREC_HG_LATE_DX in desc.p16 makes srec_hg_bwd leave dx alone; after the caller's backward-data GEMMs
  * srec_hg_pre_merge writes the whole d x in one pass (the pre-fill of srec_hg_bwd + srec_hg_drop_merge: one kernel, one pass
  * over dx less); t [2, S, NT, D] as for srec_hg_drop_merge, masks recomputed from desc.rm_* */
 int srec_hg_pre_merge(const void* desc, const float* g, int ld_g, const float* t, int S, float* dx, int ld_dx, void* stream);

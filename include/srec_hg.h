@@ -22,13 +22,17 @@
 #define SREC_HG_MAXB 16
 #define SREC_HG_MAXI 16
 
+/* flag bits of srec_hg_desc.p16 */
+#define SREC_HG_P16_BF16 1         /* P / dP hold bf16 (2-byte) elements (0: fp32) */
+#define SREC_HG_SKIP_DEAD_DP 2     /* srec_hg_bwd: leave the dP rows past the live count unwritten - the caller's readers of dP stop
+                                      at *dyn_n (srec_gemm16_group.dyn) */
+#define SREC_HG_LATE_DX 4          /* srec_hg_bwd: do not write dx - the caller finishes it with srec_hg_pre_merge */
+#define SREC_HG_FOLDED 8           /* srec_hg_fwd: V / the bias sums in Z are current (srec_hg_fold or srec_step_prep ran) */
+
 typedef struct {
     int H, D, n_types, n_mods, n_blocks, n_inst, B;
     float slope;
-    int p16;                       /* bit 0: P / dP hold bf16 (2-byte) elements (0: fp32); bit 1 (srec_hg_bwd): leave the dP rows past
-                                      the live count unwritten - the caller's readers of dP stop at *dyn_n (srec_gemm16_group.dyn);
-                                      bit 2 (srec_hg_bwd): do not write dx - the caller finishes it with srec_hg_pre_merge;
-                                      bit 3 (srec_hg_fwd): V / the bias sums in Z are current (srec_hg_fold or srec_step_prep ran) */
+    int p16;                       /* SREC_HG_P16_BF16 | SREC_HG_SKIP_DEAD_DP | SREC_HG_LATE_DX | SREC_HG_FOLDED */
     const int* dynB;
     /* node types */
     int row0[SREC_HG_MAXT], ncap[SREC_HG_MAXT];
@@ -100,10 +104,13 @@ typedef struct {
 /* problem table of srec_gemm16_nt / srec_gemm16_tn (srec.h): up to 16 problems, every operand bf16 in device memory */
 #define SREC_G16_MAXP 16
 #define SREC_G16_MAXS 4
+/* flag bits of srec_gemm16_group.c16 */
+#define SREC_G16_C_BF16 1          /* C outputs are bf16 (nt only) */
+#define SREC_G16_KEEP_DEAD 2       /* leave output rows past *dyn unwritten */
 typedef struct {
     int np, lda, ldb, ldc;
     float beta;
-    int c16;                       /* bit 0: C outputs are bf16 (nt only); bit 1: leave output rows past *dyn unwritten */
+    int c16;                       /* SREC_G16_C_BF16 | SREC_G16_KEEP_DEAD */
     int M[SREC_G16_MAXP], N[SREC_G16_MAXP], K[SREC_G16_MAXP], nseg[SREC_G16_MAXP];
     const void* A[SREC_G16_MAXP][SREC_G16_MAXS];
     const void* B[SREC_G16_MAXP][SREC_G16_MAXS];
@@ -288,7 +295,7 @@ typedef struct {
  * srec_copy_words_mailbox (srec.h; arguments as documented there, HOST arrays of n entries) as workgroup ranges of one kernel.
  * None of them reads the batch or another one's output.  A role is absent with hg = NULL / n = 0 / box_cap = 0. */
 typedef struct {
-    const void* hg;                    /* HOST srec_hg_desc whose fold is wanted (the caller then sets bit 3 of ITS p16 for srec_hg_fwd) */
+    const void* hg;                    /* HOST srec_hg_desc whose fold is wanted (the caller then sets SREC_HG_FOLDED in ITS p16 for srec_hg_fwd) */
     int n_w16;                         /* srec_weights_bf16 */
     const void* w16_W;
     const void* w16_out;

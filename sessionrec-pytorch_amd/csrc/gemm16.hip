@@ -548,7 +548,7 @@ int fill(G16Args& g, const void* desc_, int tm, int tn, bool tnmode, int& blocks
     const srec_gemm16_group* d = (const srec_gemm16_group*)desc_;
     if (d == nullptr || d->np <= 0 || d->np > G16_MAXP || (d->lda & 7) || (d->ldb & 7)) return SREC_BAD_ARG;
     g.np = d->np; g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc; g.beta = d->beta;
-    g.keep_dead = (d->c16 >> 1) & 1;
+    g.keep_dead = (d->c16 & SREC_G16_KEEP_DEAD) ? 1 : 0;
     blocks = 0;
     for (int p = 0; p < d->np; ++p) {
         if (d->nseg[p] <= 0 || d->nseg[p] > G16_MAXS || d->M[p] <= 0 || d->N[p] <= 0 || d->K[p] <= 0) return SREC_BAD_ARG;
@@ -603,7 +603,7 @@ extern "C" int srec_gemm16_nt(const void* desc_, void* stream) {
     // kernels: 64 x 128 tiles with 2 x 64-deep stages = 48 KB -> 3 per CU = 96 slots per XCD; 128 x 128 = 64 KB -> 2 per CU =
     // 64 slots, workgroup life +5 % for twice the work (tools/gemm16_bench.py).  The step's backward-data launch (960 64-row
     // tiles = 120 per XCD) ran 1.25 -> 2 rounds: 77 us; as 480 128-row tiles (60 per XCD) it is one round.
-    if (!(h->c16 & 1) && tm == 64 && t64x128 > 384) {
+    if (!(h->c16 & SREC_G16_C_BF16) && tm == 64 && t64x128 > 384) {
         const long r64 = cdiv((int)cdiv((int)t64x128, 8), 96), r128 = cdiv((int)cdiv((int)t128, 8), 64);
         // ... and when the rounds tie, the 128-row tiles win on BYTES: these launches run at what the L2s deliver to the CUs
         // (8 - 12 TB/s in every staging variant, profiles/r03_notes.md) and a 128 x 128 tile fetches 2/3 of the operand bytes of two
@@ -616,7 +616,7 @@ extern "C" int srec_gemm16_nt(const void* desc_, void* stream) {
     if (int rc = fill(g, desc_, tm, tn, false, blocks)) return rc;
     // fp32-output launches (backward-data: two column tiles share every dP row block): 38.7 -> 34.5 us at the bench shapes; the
     // bf16-output forward (sixteen column tiles per row block, all of x fits any L2) measured 1.5 us slower that way
-    if (!(h->c16 & 1)) {
+    if (!(h->c16 & SREC_G16_C_BF16)) {
         bool same_tn = true;
         const int tn0 = cdiv(h->N[0], tn);
         for (int p = 1; p < h->np; ++p) same_tn = same_tn && cdiv(h->N[p], tn) == tn0;
@@ -628,7 +628,7 @@ extern "C" int srec_gemm16_nt(const void* desc_, void* stream) {
         }
     }
     hipStream_t st = (hipStream_t)stream;
-    const bool c16 = h->c16 & 1;
+    const bool c16 = h->c16 & SREC_G16_C_BF16;
     static std::atomic<unsigned long long> optin_mask[8];
 #define SREC_G16(TMV, TNV, C16V, BKV, NSV, slot)                                                                       \
     do {                                                                                                               \

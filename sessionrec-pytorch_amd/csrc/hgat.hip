@@ -1519,10 +1519,10 @@ extern "C" int srec_hg_fwd(const void* desc_, const float* x, int ld_x, float* o
     if (bad_desc(d) || (ld_x & 3)) return SREC_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int H = d->H, D = d->D, HD = H * D;
-    const size_t esz = (d->p16 & 1) ? 2 : 4;
-    // (bit 3 of p16: V and the bias sums of this descriptor's weights were written since the optimizer last changed them - by
+    const size_t esz = (d->p16 & SREC_HG_P16_BF16) ? 2 : 4;
+    // (SREC_HG_FOLDED: V and the bias sums of this descriptor's weights were written since the optimizer last changed them - by
     // srec_hg_fold or, in a step that starts with srec_step_prep, by the prologue launch)
-    if (d->n_mods > 0 && !(d->p16 & 8))
+    if (d->n_mods > 0 && !(d->p16 & SREC_HG_FOLDED))
         if (int rc = srec_hg_fold(d, stream)) return rc;
     if (d->sess == nullptr || d->B <= 0) return SREC_BAD_ARG;
     for (int t = 0; t < d->n_types; ++t)
@@ -1579,9 +1579,9 @@ extern "C" int srec_hg_fwd(const void* desc_, const float* x, int ld_x, float* o
             node = al16(g.Ps[i]) && al16(g.eLs[i]) && al16(g.eRd[i]) && al16(g.A[i]) && al16(g.Mk[i]);
         if (node) {
             // (same box, rocprof: 1 edge in flight at 5 waves per SIMD 31.6 us; 2 edges at 4: 32.5; anything that spills: 38 - 97)
-            if (d->p16 & 1) hipLaunchKernelGGL((hg_agg_node_kernel<unsigned short, 1, 5>), dim3(cdiv(rows, WPB)), dim3(64 * WPB), 0, st, g);
+            if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL((hg_agg_node_kernel<unsigned short, 1, 5>), dim3(cdiv(rows, WPB)), dim3(64 * WPB), 0, st, g);
             else hipLaunchKernelGGL((hg_agg_node_kernel<float, 2, 3>), dim3(cdiv(rows, WPB)), dim3(64 * WPB), 0, st, g);
-        } else if (d->p16 & 1) hipLaunchKernelGGL(hg_agg_kernel<unsigned short>, dim3(rows), dim3(512), 0, st, g);
+        } else if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL(hg_agg_kernel<unsigned short>, dim3(rows), dim3(512), 0, st, g);
         else hipLaunchKernelGGL(hg_agg_kernel<float>, dim3(rows), dim3(512), 0, st, g);
     }
     SREC_LAUNCH_CHECK();
@@ -1605,7 +1605,7 @@ static int fill_pre(const srec_hg_desc* d, const float* g, int ld_g, float* dx, 
     return 0;
 }
 
-// the layer's d x in one pass, AFTER the backward-data GEMMs of a feature-dropout call (desc.p16 bit 2 made srec_hg_bwd leave
+// the layer's d x in one pass, AFTER the backward-data GEMMs of a feature-dropout call (SREC_HG_LATE_DX in desc.p16 made srec_hg_bwd leave
 // d x alone): dx [NT, D] = residual + session-mean terms of g (as srec_hg_bwd would have written) + the two convs' masked data
 // gradients t [2, S, NT, D] (as srec_hg_drop_merge would have added); masks from desc.rm_p / rm_seed / rm_counter / rm_salt.
 extern "C" int srec_hg_pre_merge(const void* desc_, const float* g, int ld_g, const float* t, int S, float* dx, int ld_dx,
@@ -1627,12 +1627,12 @@ extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const fl
     if (bad_desc(d) || (ld_g & 3) || (ld_dx & 3) || (ld_x & 3) || ws == nullptr) return SREC_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int H = d->H, D = d->D, HD = H * D;
-    const size_t esz = (d->p16 & 1) ? 2 : 4;
+    const size_t esz = (d->p16 & SREC_HG_P16_BF16) ? 2 : 4;
     int ninst_t[MAXT] = {0, 0, 0, 0};
     for (int i = 0; i < d->n_inst; ++i) ninst_t[d->blk_type[d->inst_dblk[i]]]++;
     int rows = 0;
     for (int t = 0; t < d->n_types; ++t) rows += d->ncap[t];
-    if (!(d->p16 & 4)) {                       // (bit 2: the caller finishes d x with srec_hg_pre_merge after its GEMMs)
+    if (!(d->p16 & SREC_HG_LATE_DX)) {                       // (the caller finishes d x with srec_hg_pre_merge after its GEMMs)
         PreArgs a{};
         if (int rc = fill_pre(d, g, ld_g, dx, ld_dx, a)) return rc;
         if (rows > 0) hipLaunchKernelGGL(hg_pre_kernel<false>, dim3(cdiv(rows, WPB)), dim3(256), 0, st, a, (const float*)nullptr, 0);
@@ -1670,17 +1670,17 @@ extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const fl
         }
         if (node && trows > 0) {
             // (same box, rocprof: 2 edges in flight at 4 waves per SIMD 28.2 us; 1 edge 30.2; 5 waves per SIMD spill: 32.7 / 36.1)
-            if (d->p16 & 1) hipLaunchKernelGGL((hg_bwd_dst_node_kernel<unsigned short, 2, 4>), dim3(cdiv(trows, WPB)), dim3(256), 0, st, a);
+            if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL((hg_bwd_dst_node_kernel<unsigned short, 2, 4>), dim3(cdiv(trows, WPB)), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((hg_bwd_dst_node_kernel<float, 1, 3>), dim3(cdiv(trows, WPB)), dim3(256), 0, st, a);
         } else if (blocks > 0) {
-            if (d->p16 & 1) hipLaunchKernelGGL(hg_bwd_dst_kernel<unsigned short>, dim3(blocks), dim3(256), 0, st, a);
+            if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL(hg_bwd_dst_kernel<unsigned short>, dim3(blocks), dim3(256), 0, st, a);
             else hipLaunchKernelGGL(hg_bwd_dst_kernel<float>, dim3(blocks), dim3(256), 0, st, a);
         }
     }
     if (d->n_blocks > 0) {
         SrcArgs a{};
         a.nb = d->n_blocks; a.H = H; a.D = D; a.g = g; a.ld_g = ld_g; a.arg = arg;
-        a.skip_dead = (d->p16 & 2) ? 1 : 0;
+        a.skip_dead = (d->p16 & SREC_HG_SKIP_DEAD_DP) ? 1 : 0;
         int blocks = 0;
         for (int b = 0; b < d->n_blocks; ++b) {
             const int m = d->blk_mod[b], t = d->blk_type[b];
@@ -1704,7 +1704,7 @@ extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const fl
         if (blocks > 0) {
             const size_t lds = (size_t)2 * HD * sizeof(float);
             // (same box, rocprof: 6 waves per SIMD 47.9 us; 5: 50.3; 7: 49.4; 8 (spills): 58.6; der loads first: +1 - 2 us)
-            if (d->p16 & 1) hipLaunchKernelGGL((hg_bwd_src_kernel<unsigned short, 6, false>), dim3(blocks), dim3(64 * WPB_SRC), lds, st, a);
+            if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL((hg_bwd_src_kernel<unsigned short, 6, false>), dim3(blocks), dim3(64 * WPB_SRC), lds, st, a);
             else hipLaunchKernelGGL((hg_bwd_src_kernel<float, 4, false>), dim3(blocks), dim3(64 * WPB_SRC), lds, st, a);
         }
     }

@@ -432,7 +432,7 @@ extern "C" int srec_copy_words_mailbox(const int* mailbox, int M, const int* cou
 }
 
 // the fold of an MSHGNN layer call on its own: V[m] and the per-type bias sums (Z[t][0 .. H D)) of desc (HOST srec_hg_desc);
-// srec_hg_fwd runs it itself unless desc.p16 bit 3 says it was done (here or by srec_step_prep) since the weights last changed
+// srec_hg_fwd runs it itself unless SREC_HG_FOLDED in desc.p16 says it was done (here or by srec_step_prep) since the weights last changed
 extern "C" int srec_hg_fold(const void* desc, void* stream) {
     PrepArgs a{};
     if (int rc = fold_fill((const srec_hg_desc*)desc, a.f)) return rc;

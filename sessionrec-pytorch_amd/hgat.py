@@ -1,0 +1,341 @@
+"""The batched MSHGNN layer (csrc/hgat.hip around the fc GEMMs): its static plan, the autograd node and the glue between them.
+ops.py keeps the GEMM wrappers and the tests' switches (reached through the module object at call time) and re-exports this."""
+import ctypes as _ct
+from collections import namedtuple
+
+import torch
+
+from . import ops                    # (ops.py imports this module at its end: import the package or ops first, never hgat alone)
+from ._lib import CONST, lib, ptr, stream
+from .ops import GemmProb, HgDesc, _ld, _rows
+
+# dropout state of one call.  xc [2, NT, D]: dropped inputs of conv1 / conv2;  xres [NT, D]: residual rows summed over the instances;
+# mk: attention masks per instance or None;  ms: feature masks, kept for the tests' tap only;  rng = (p, seed, counter, salt)
+DropState = namedtuple('DropState', 'xc xres mk ms rng cnt')
+
+
+class HgPlan:
+    """Static topology of one MSHGNN layer call (built by msgifsr.MSHGNN from the FlatBatch).
+    types:   [(row0, ncap, dyn_n, seg)]                          node types, stacked rows
+    modules: [(row_start, n_rows, dyn)]                          rows of x each GAT module projects (dyn or None)
+    blocks:  [(module, type)]                                    projection blocks
+    insts:   [(module, src_block, dst_block, (in_ptr, in_idx, out_ptr, out_idx, esrc, edst))]
+    mod_conv: per module 0 (conv1) or 1 (conv2, reversed graph);  layer_id: dropout-mask salt, distinct per MSHGNN layer of a
+    model;  live: {first stacked row of a type: host-side live row count} - hints for the GEMM tile heuristics only"""
+
+    def __init__(self, H, D, slope, B, dynB, types, modules, blocks, insts, mod_conv=None, layer_id=0, live=None):
+        self.mod_conv = mod_conv if mod_conv is not None else [0] * len(modules)
+        self.layer_id, self.live = layer_id, dict(live or {})
+        self.H, self.D, self.slope, self.B, self.dynB = H, D, slope, B, dynB
+        self.types, self.modules, self.blocks, self.insts, self._fold = types, modules, blocks, insts, None
+        assert (len(types) <= CONST['SREC_HG_MAXT'] and len(modules) <= CONST['SREC_HG_MAXM'] and
+                len(blocks) <= CONST['SREC_HG_MAXB'] and len(insts) <= CONST['SREC_HG_MAXI'])
+
+    def put_fold(self, small, lay):          # ops.step_prologue folded the weights into this scratch: the next forward takes it
+        self._fold = (small, lay)
+
+    def take_fold(self):
+        fold, self._fold = self._fold, None
+        return fold
+
+    def pieces(self, m):
+        """[(row offset inside module m's projection, first stacked row, rows, dyn)] per node type the module covers: GEMM problems
+        are cut at type boundaries, so every piece has its own live row count (the shared 'inter' module spans all types)"""
+        r0, nr, dyn = self.modules[m]
+        out = [(t0 - r0, t0, nc, dyn_t) for (t0, nc, dyn_t, _) in self.types if r0 <= t0 and t0 + nc <= r0 + nr]
+        assert sum(p[2] for p in out) == nr, 'a module projects whole node types'
+        return out
+
+    def projectors(self, cv, t):
+        """the modules of conv cv (None: either conv) that project node type t for some relation instance"""
+        t0, nc = self.types[t][:2]
+        return [m for m, (r0, nr, _) in enumerate(self.modules)
+                if (cv is None or self.mod_conv[m] == cv) and r0 <= t0 and t0 + nc <= r0 + nr
+                and any(bm == m and bt == t for bm, bt in self.blocks)]
+
+    def scratch(self, dev):
+        """-> (fp32 tensor, offsets) of the small per-call scratch: eL,eR,wL,wR per block; V,Z per module; A,DP,der per instance"""
+        H, ncap = self.H, [tp[1] for tp in self.types]
+        sizes = [((nm, b), ncap[t] * H) for b, (m, t) in enumerate(self.blocks) for nm in ('eL', 'eR', 'wL', 'wR')]
+        # (Z slot t < n_types also holds the summed bias row of node type t during the forward: slots for max(modules, types))
+        sizes += [((nm, m), 2 * self.D * H) for m in range(max(len(self.modules), len(ncap))) for nm in ('V', 'Z')]
+        for i, (m, sb, db, gr) in enumerate(self.insts):
+            E = max(gr[4].numel(), 1) * H
+            sizes += [(('A', i), E), (('DP', i), E), (('der', i), ncap[self.blocks[db][1]] * H)]
+        sizes += [(('smean', t), self.B * self.D) for t in range(len(ncap))]       # session means of the input rows per type [B, D]
+        sizes.append((('sess', 0), sum(ncap)))                                     # session of every stacked row (int32)
+        off, lay = 0, {}
+        for key, n in sizes:
+            lay[key] = off
+            off += n
+        return torch.empty(max(off, 1), device=dev, dtype=torch.float32), lay
+
+    def fill(self, d, small, lay, P, dP, params, grads, drop=None):
+        if drop is not None:                               # (d.rm stays NULL: srec_hg_bwd recomputes it from the masks' hash)
+            for m in range(len(self.modules)):
+                d.xin[m] = ptr(drop.xc[self.mod_conv[m]])
+            d.xres, d.rm_cnt = ptr(drop.xres), ptr(drop.cnt)
+            d.rm_p, d.rm_seed, d.rm_counter, d.rm_salt = drop.rng
+            for i in range(len(self.insts)):
+                d.Mk[i] = ptr(drop.mk[i]) if drop.mk is not None else None
+        d.H, d.D, d.slope, d.B, d.dynB = self.H, self.D, self.slope, self.B, ptr(self.dynB)
+        d.p16 = CONST['SREC_HG_P16_BF16'] if P and P[0].dtype == torch.bfloat16 else 0      # (P = None: the view srec_hg_fold reads)
+        d.n_types, d.n_mods, d.n_blocks, d.n_inst = len(self.types), len(self.modules), len(self.blocks), len(self.insts)
+        base = small.data_ptr()
+        for t, (r0, nc, dyn, seg) in enumerate(self.types):
+            d.row0[t], d.ncap[t], d.dyn_n[t], d.seg[t] = r0, nc, ptr(dyn), ptr(seg)
+            d.smean[t], d.Z[t] = base + 4 * lay[('smean', t)], base + 4 * lay[('Z', t)]
+        for m in range(len(self.modules)):
+            W, al, ar, bias = params[4 * m:4 * m + 4]
+            d.P[m], d.W[m] = ptr(P[m]) if P else None, ptr(W)
+            d.V[m], d.Z[m] = base + 4 * lay[('V', m)], base + 4 * lay[('Z', m)]
+            d.attn_l[m], d.attn_r[m], d.bias[m] = ptr(al), ptr(ar), ptr(bias)
+            if dP is not None:
+                d.dP[m] = ptr(dP[m])
+                d.d_attn_l[m], d.d_attn_r[m], d.d_bias[m] = (grads[m][j].data_ptr() for j in range(3))
+        d.sess = base + 4 * lay[('sess', 0)]
+        for b, (m, t) in enumerate(self.blocks):
+            d.blk_mod[b], d.blk_type[b] = m, t
+            d.blk_row[b] = self.types[t][0] - self.modules[m][0]
+            for nm in ('eL', 'eR', 'wL', 'wR'):
+                getattr(d, nm)[b] = base + 4 * lay[(nm, b)]
+        for i, (m, sb, db, gr) in enumerate(self.insts):
+            d.inst_mod[i], d.inst_sblk[i], d.inst_dblk[i] = m, sb, db
+            for nm, g in zip(('in_ptr', 'in_idx', 'out_ptr', 'out_idx', 'esrc', 'edst'), gr):
+                getattr(d, nm)[i] = ptr(g)
+            for nm in ('A', 'DP', 'der'):
+                getattr(d, nm)[i] = base + 4 * lay[(nm, i)]
+        return d
+
+
+_HG_WS = {}
+_CNT_CACHE = {}
+
+
+def _inst_counts(plan, NT, dev):
+    """[2, NT, 1]: how many relation instances of conv1 / conv2 use each stacked row as a DESTINATION (identity residual
+    count, gatconv.py:306-308) - a function of the plan's static topology"""
+    key = (str(dev), NT, tuple(plan.mod_conv), tuple((m, tuple(plan.types[plan.blocks[db][1]][:2])) for (m, sb, db, gr) in plan.insts))
+    cnt = _CNT_CACHE.get(key)
+    if cnt is None:
+        host = torch.zeros(2, NT, 1)
+        for (m, sb, db, gr) in plan.insts:
+            t0, nc = plan.types[plan.blocks[db][1]][:2]
+            host[plan.mod_conv[m], t0:t0 + nc] += 1.0
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('instance counts must be cached by an eager warm-up step before graph capture')
+        cnt = _CNT_CACHE[key] = host.to(dev)
+    return cnt
+
+
+def gemm_strategy(mode, D, ldx, n_mods, w_contiguous):
+    """which GEMMs compute the projections and their gradients, decided once per layer call.  'g16': every operand bf16 in HBM
+    (ops.gemm16);  'grouped': fp32 operands converted on the way, one launch per product kind (ops.gemm_group) - both STORE the
+    projections as bf16;  'plain': one fp32-in / fp32-out product per module (ops.gemm_nt / gemm_nn / gemm_tn)."""
+    if mode != 'bf16' or D % 8 or ldx != D or not 0 < n_mods <= 8:          # (no module: no GEMM)
+        return 'plain'
+    return 'g16' if D % 64 == 0 and w_contiguous else 'grouped'
+
+
+def _drop_prep(x, plan, drop, strategy):
+    """-> (DropState, x16 or None): both convs' feature masks and every instance's attention mask in ONE launch (counter-based
+    hash: no generator state, replay-safe); the 'g16' strategy reads bf16(xc), written by the same pass"""
+    (pf, pa), (NT, D), dev, tap = drop, x.shape, x.device, ops.DROP_TAP
+    cnt = _inst_counts(plan, NT, dev)                     # (depends on the plan only: cached)
+    ms = torch.empty(2, NT, D, device=dev, dtype=torch.float32) if tap is not None else None
+    xcs, xres = torch.empty(2, NT, D, device=dev, dtype=torch.float32), torch.empty(NT, D, device=dev)
+    sizes = [max(gr[4].numel(), 1) * plan.H for (_, _, _, gr) in plan.insts] if pa > 0 else []
+    na = sum(sizes)
+    allm = torch.empty(na, device=dev, dtype=torch.float32) if pa > 0 else None
+    mk = list(torch.split(allm, sizes)) if pa > 0 else None
+    seed, rc = ops.rng_args(dev)
+    salt = 101 + 2 * plan.layer_id                        # (rm = cnt0 m0 + cnt1 m1 is never stored: NULL, the backward recomputes it)
+    args = (ptr(x), ptr(cnt), NT, D, float(pf), seed, rc, salt, ptr(ms), ptr(xcs), None, ptr(xres), float(pa), na, ptr(allm))
+    x16 = torch.empty(2, NT, D, device=dev, dtype=torch.bfloat16) if strategy == 'g16' else None
+    if x16 is not None:
+        lib.srec_hg_drop_prep16(*args, ptr(x16), stream())
+    else:
+        lib.srec_hg_drop_prep(*args, stream())
+    if tap is not None:
+        tap.append(dict(ms=ms.clone(), mk=[m.clone() for m in mk] if mk is not None else None))
+    return DropState([xcs[0], xcs[1]], xres, mk, ms, (float(pf), seed, rc, salt), cnt), x16
+
+
+def _project(xin, x16, plan, params, strategy, dev):
+    """P[m] = xin[m][rows of m] fc_m^T for every module -> (P, (bf16 inputs per module, wt16): what the 'g16' backward reads, or None)"""
+    D, HD, nm = plan.D, plan.H * plan.D, len(plan.modules)
+    # bf16 strategies: the projections (and their gradients) are STORED as bf16 too - every pass over them is HBM bound
+    P = [torch.empty(nr, HD, device=dev, dtype=torch.float32 if strategy == 'plain' else torch.bfloat16)
+         for (r0, nr, dyn) in plan.modules]
+    if strategy == 'g16':
+        # the small weights as bf16 once per call (+ transposed copies for the backward-data product)
+        w16, wt16 = ops.weights_bf16([params[4 * m] for m in range(nm)])
+        xin16 = [x16[cv] for cv in plan.mod_conv] if x16 is not None else [ops.rows_bf16(xin[0])] * nm
+        probs = [GemmProb(nc, HD, D, [(xin16[m][t0:t0 + nc], w16[m])], P[m][o:o + nc], dyn_t, mhint=plan.live.get(t0, 0))
+                 for m in range(nm) for (o, t0, nc, dyn_t) in plan.pieces(m)]
+        for i in range(0, len(probs), ops.G16_MAXP):
+            # rows past a type's live count are never read (every hgat.hip kernel walks the live prefix only)
+            ops.gemm16('nt', probs[i:i + ops.G16_MAXP], D, D, HD, c16=True, keep_dead=True)
+        return P, (xin16, wt16)
+    if strategy == 'grouped':
+        ops.gemm_group(0, [(nr, HD, D, [(xin[m][r0:r0 + nr], params[4 * m])], P[m], dyn)
+                           for m, (r0, nr, dyn) in enumerate(plan.modules)], D, D, HD, c16=True)
+    else:
+        for m, (r0, nr, dyn) in enumerate(plan.modules):
+            ops.gemm_nt(xin[m][r0:r0 + nr], _rows(params[4 * m]), P[m], None, dyn, 1 if dyn is not None else 0)
+    return P, None
+
+
+def _backward_graph(ctx, x, g, small, arg, P, params, late_dx):
+    """srec_hg_bwd: the graph kernels' half of the backward -> (desc, dP, [attn_l, attn_r, bias gradients per module], dx)"""
+    plan, nm = ctx.plan, len(ctx.plan.modules)
+    # rows of a module's projection that no relation instance touches (a type without live 'inter' edges) get no
+    # gradient from the kernels: those buffers start from zero
+    cov = [sum(plan.types[bt][1] for bm, bt in plan.blocks if bm == m) for m in range(nm)]
+    dP = [torch.empty_like(p) if cov[m] == p.shape[0] else torch.zeros_like(p) for m, p in enumerate(P)]
+    # (attn_l, attn_r, bias gradients: [HD] each - the parameters' bucket slots when the table is row-sharded, ops.grad_buf)
+    grads = [[ops.grad_buf(params[4 * m + 1 + j]).view(-1) for j in range(3)] for m in range(nm)]
+    dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    flat = [p.reshape(-1) if i % 4 else p for i, p in enumerate(params)]
+    desc = plan.fill(HgDesc(), small, ctx.lay, P, dP, flat, grads, ctx.drop)
+    # (both gemm16 consumers of dP stop at the live rows)
+    desc.p16 |= (CONST['SREC_HG_SKIP_DEAD_DP'] if ctx.strategy == 'g16' else 0) | (CONST['SREC_HG_LATE_DX'] if late_dx else 0)
+    n = _ct.c_long()
+    lib.srec_hg_ws_floats(_ct.addressof(desc), _ct.addressof(n))
+    key = (x.device.index, n.value)
+    ws = _HG_WS.get(key)
+    if ws is None:
+        ws = _HG_WS[key] = torch.empty(max(n.value, 1), device=x.device, dtype=torch.float32)
+    lib.srec_hg_bwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(g), _ld(g), ptr(arg), ptr(dx), x.shape[1], ptr(ws), stream())
+    return desc, dP, grads, dx
+
+
+def _backward_data(ctx, dP, params, dx):
+    """d x of a node type += sum over the modules that project it of dP fc (the module sum is the K loop: segments).  With feature
+    dropout the convs see differently masked inputs: one term per conv in tgts [2, S, NT, D] for the merge kernel -> (tgts, S)"""
+    plan, strategy, drop = ctx.plan, ctx.strategy, ctx.drop
+    NT, D = dx.shape
+    HD, nt = plan.H * D, len(plan.types)
+    tgts, S, full = None, 1, False
+    if drop is not None:
+        # every node type is projected by some module of each conv in the usual plans: the grouped GEMM then writes all
+        # rows (beta = 0 zeroes rows past the live count) and the buffers need no fill
+        nproj = {len(plan.projectors(cv, t)) for cv in (0, 1) for t in range(nt)}
+        full = strategy != 'plain' and min(nproj) > 0
+        # gemm16: when every (conv, type) is projected by the same number S of modules (intra_k + the shared 'inter'), each
+        # module's product goes to its own partial buffer (S x more, S x shorter reduction loops); the merge kernel sums them
+        if strategy == 'g16' and full and len(nproj) == 1 and 1 < min(nproj) <= 4:
+            S = min(nproj)
+        tgts = (torch.empty if full else torch.zeros)(2, S, NT, D, device=dx.device, dtype=torch.float32)
+    beta, convs = 0.0 if full else 1.0, (0, 1) if drop is not None else (None,)
+    tgt = lambda cv, j=0: dx if cv is None else tgts[cv, j]
+    if strategy == 'plain':
+        for cv in convs:
+            for m, (r0, nr, dyn) in enumerate(plan.modules):
+                if cv is None or plan.mod_conv[m] == cv:
+                    ops.gemm_nn(dP[m], _rows(params[4 * m]), tgt(cv)[r0:r0 + nr], dyn, 1 if dyn is not None else 0, beta=1.0)
+        return tgts, S
+    W = ctx.g16[1] if strategy == 'g16' else params[::4]
+
+    def problems(cv):
+        """conv cv: one problem per node type, or (S > 1) per node type and projecting module"""
+        out = []
+        for t, (t0, nc, dyn_t, _) in enumerate(plan.types):
+            mods = plan.projectors(cv, t)
+            for j, grp in enumerate([[m] for m in mods] if S > 1 else [mods] if mods else []):
+                segs = [(dP[m][t0 - plan.modules[m][0]:][:nc], W[m]) for m in grp]
+                out.append(GemmProb(nc, D, HD, segs, tgt(cv, j)[t0:t0 + nc], dyn_t, mhint=plan.live.get(t0, 0)))
+        return out
+    if strategy == 'grouped':                    # one launch per conv
+        for probs in filter(None, map(problems, convs)):
+            ops.gemm_group(1, probs, HD, D, D, beta=beta, a16=True)
+    else:                                        # 'g16': the two convs' problems share the launches
+        probs = [q for cv in convs for q in problems(cv)]
+        for i in range(0, len(probs), ops.G16_MAXP):
+            ops.gemm16('nt', probs[i:i + ops.G16_MAXP], HD, HD, D, beta=beta)
+    return tgts, S
+
+
+def _weight_grads(ctx, x, dP, gWs):
+    """gWs[m] = dP[m]^T (dropped) x[rows of m]"""
+    plan, D, HD, nm = ctx.plan, x.shape[1], ctx.plan.H * x.shape[1], len(ctx.plan.modules)
+    xin = [ctx.drop.xc[cv] for cv in plan.mod_conv] if ctx.drop is not None else [x] * nm
+    if ctx.strategy == 'g16':
+        # one balanced problem per (module, node type): a module that spans several types (the shared 'inter' one) writes
+        # one slab per type, summed in fixed order afterwards
+        xin16 = ctx.g16[0]
+        pcs = [plan.pieces(m) for m in range(nm)]
+        slabs = {m: torch.empty(len(pcs[m]), HD, D, device=x.device, dtype=torch.float32) for m in range(nm) if len(pcs[m]) > 1}
+        probs = [GemmProb(HD, D, nc, [(dP[m][o:o + nc], xin16[m][t0:t0 + nc])], slabs[m][pi:pi + 1] if m in slabs else gWs[m], dyn_t)
+                 for m in range(nm) for pi, (o, t0, nc, dyn_t) in enumerate(pcs[m])]
+        for i in range(0, len(probs), ops.G16_MAXP):
+            ops.gemm16('tn', probs[i:i + ops.G16_MAXP], HD, D, D)
+        if slabs and ops.can_defer(ctx.defer, [ctx.wparams[m] for m in slabs]):
+            for m, sl in slabs.items():
+                ops.defer_slab_sum(sl, gWs[m])
+        elif slabs:
+            ops._launch_slab_sums([(sl, gWs[m]) for m, sl in slabs.items()])
+    elif ctx.strategy == 'grouped':
+        ops.gemm_group(2, [(HD, D, nr, [(dP[m], xin[m][r0:r0 + nr])], gWs[m], dyn)
+                           for m, (r0, nr, dyn) in enumerate(plan.modules)], HD, D, D, a16=True)
+    else:
+        for m, (r0, nr, dyn) in enumerate(plan.modules):
+            ops.gemm_tn(dP[m], xin[m][r0:r0 + nr], gWs[m], dyn)
+
+
+class HGATLayer(torch.autograd.Function):
+    """out = MSHGNN(x): all relation instances of conv1 / conv2 in one batched pass (csrc/hgat.hip) around the fc
+    GEMMs.  params = (fc.weight, attn_l, attn_r, bias) per module, in plan.modules order.
+    drop = (p_feat, p_attn) in training: feature dropout with ONE mask per (conv, node type) on the inputs of that
+    conv's GATConv modules (projection, logits and identity residual all see the dropped rows, gatconv.py:268-308;
+    the reference draws one mask per (relation, role) - documented deviation) and attention dropout on the edge
+    soft-max (gatconv.py:300)."""
+
+    @staticmethod
+    def forward(ctx, x, plan, drop, *params):
+        x = _rows(x)
+        (NT, D), dev, nm = x.shape, x.device, len(plan.modules)
+        strategy = gemm_strategy(ops.PRECISION['matmul'], D, _ld(x), nm, all(params[4 * m].is_contiguous() for m in range(nm)))
+        dstate, x16 = None, None
+        if drop is not None and (drop[0] > 0 or drop[1] > 0):
+            x = x.contiguous()          # srec_hg_fwd / srec_hg_bwd read the dropped copies (xin, xres: [NT, D]) with x's row stride
+            dstate, x16 = _drop_prep(x, plan, drop, strategy)
+        xin = [dstate.xc[cv] for cv in plan.mod_conv] if dstate is not None else [x] * nm      # what each module projects
+        P, g16 = _project(xin, x16, plan, params, strategy, dev)
+        fold = plan.take_fold()                      # the prologue launch of this forward already folded the weights (step_prologue)
+        small, lay = fold or plan.scratch(dev)
+        out = torch.empty(NT, D, device=dev, dtype=torch.float32)
+        arg = torch.empty(NT, D, device=dev, dtype=torch.uint8)
+        flat = [p.reshape(-1) if i % 4 else p for i, p in enumerate(params)]
+        desc = plan.fill(HgDesc(), small, lay, P, None, flat, None, dstate)
+        if fold is not None:
+            desc.p16 |= CONST['SREC_HG_FOLDED']
+        lib.srec_hg_fwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(out), D, ptr(arg), stream())
+        ctx.save_for_backward(x, small, arg, *P, *params)
+        ctx.plan, ctx.lay, ctx.strategy, ctx.drop, ctx.g16 = plan, lay, strategy, dstate, g16
+        ctx.defer, ctx.wparams = ops.defer_scope(), [params[4 * m] for m in range(nm)]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        plan, drop, nm = ctx.plan, ctx.drop, len(ctx.plan.modules)
+        x, small, arg, *rest = ctx.saved_tensors
+        P, params = rest[:nm], rest[nm:]
+        g = _rows(g)
+        NT, D = x.shape
+        # feature dropout with recomputed masks (the tap is off): d x is written once, after the backward-data GEMMs
+        late_dx = drop is not None and drop.ms is None and _ld(g) % 4 == 0
+        desc, dP, grads, dx = _backward_graph(ctx, x, g, small, arg, P, params, late_dx)
+        gWs = [ops.grad_buf(params[4 * m]) for m in range(nm)]
+        tgts, S = _backward_data(ctx, dP, params, dx)
+        if late_dx:
+            lib.srec_hg_pre_merge(_ct.addressof(desc), ptr(g), _ld(g), ptr(tgts), S, ptr(dx), D, stream())
+        elif drop is not None:
+            lib.srec_hg_drop_merge(ptr(tgts), S, ptr(drop.ms), NT * D, ptr(dx), *drop.rng, stream())
+        _weight_grads(ctx, x, dP, gWs)
+        outs = [o for m in range(nm) for o in [gWs[m]] + [grads[m][j].view(params[4 * m + 1 + j].shape) for j in range(3)]]
+        return (dx, None, None) + tuple(outs)
+
+
+def hgat_layer(x, plan, params, drop=None):
+    return HGATLayer.apply(x, plan, drop, *params)

@@ -143,11 +143,11 @@ class MSHGNN(nn.Module):
                         blocks.append((m, k - 1))
                 insts.append((m, blk_id[(m, src_t)], blk_id[(m, dst_t)], self._graph(mg, name, ci == 1)))
         slope = self.conv1.mods['intra1'].negative_slope
-        plan = ops.HgPlan(8, D, slope, mg.B, mg.dynp('B'), types, mods, blocks, insts, mod_conv)
-        plan.layer_id = getattr(self, '_layer_id', 0)
         # host-side live node counts of THIS batch per type (first stacked row -> count): hints for the GEMM tile heuristics -
         # a captured step keeps the choice of the batch it was captured on, the kernels themselves read the device counts
-        plan.live = {t[0]: mg.count('N%d' % (k + 1)) for k, t in enumerate(types)}
+        nlive = {t[0]: mg.count('N%d' % (k + 1)) for k, t in enumerate(types)}
+        plan = ops.HgPlan(8, D, slope, mg.B, mg.dynp('B'), types, mods, blocks, insts, mod_conv,
+                          layer_id=getattr(self, '_layer_id', 0), live=nlive)
         return plan, params
 
     def forward_stacked(self, mg, x, all_rels=False):

@@ -9,6 +9,7 @@ extent of a capacity-padded dimension (see batch.FlatBatch.dyn).
 """
 import ctypes as _ct
 import os
+from collections import namedtuple
 
 import torch
 
@@ -2182,13 +2183,13 @@ class GRUExpandAll(torch.autograd.Function):
         for p in range(P):
             nsp = max(1, (rows[p] + 511) // 512)
             sl = torch.empty(nsp, d3, d, device=dev, dtype=torch.float32) if nsp > 1 else gWih[p].unsqueeze(0)
-            probs.append((d3, d, rows[p], [(dGI16[p], x16[p])], sl, dyn_rows[p], 0, nsp))
+            probs.append(GemmProb(d3, d, rows[p], [(dGI16[p], x16[p])], sl, dyn_rows[p], nsplit=nsp))
             if nsp > 1:
                 slabs.append((sl, gWih[p]))
             nsp = max(1, (ns[p] + 511) // 512)
             sl = torch.empty(nsp, d3, d, device=dev, dtype=torch.float32) if nsp > 1 else gWhh[p].unsqueeze(0)
             segs = [(dGH16[p][t - 1], H16[p][t - 1]) for t in range(1, ks[p])]
-            probs.append((d3, d, ns[p], segs, sl, dyn_ns[p], 0, nsp))
+            probs.append(GemmProb(d3, d, ns[p], segs, sl, dyn_ns[p], nsplit=nsp))
             if nsp > 1:
                 slabs.append((sl, gWhh[p]))
         for i in range(0, len(probs), G16_MAXP):
@@ -2555,37 +2556,43 @@ def edge_agg(x, coef, fwd_csr, bwd_csr, dyn=None):
 
 
 # ------------------------------------------------------------------------------------------ MSHGNN layer (batched)
+# one problem of a grouped GEMM launch: C [M, N] from the segments [(A, B), ...], dyn = device live count; a plain 6-tuple is the
+# same problem.  gemm16 only: koff (tn: first reduction row of this piece of a row-split product), nsplit (tn: in-kernel row
+# split, C = [nsplit, M, N] slabs), ld = per-problem (lda, ldb, ldc), mhint (nt: expected live rows of a capacity-padded problem)
+GemmProb = namedtuple('GemmProb', 'M N K segs C dyn koff nsplit ld mhint', defaults=(0, 1, None, 0))
 
 
 def gemm_group(mode, probs, lda, ldb, ldc, beta=0.0, a16=False, c16=False):
-    """probs: [(M, N, K, [(A, B), ...] segments, C, dyn)] tensors -> one srec_gemm_group_bf16 launch"""
+    """probs: [GemmProb or (M, N, K, [(A, B), ...] segments, C, dyn)] tensors -> one srec_gemm_group_bf16 launch"""
     g = GemmGroup()
     g.np, g.lda, g.ldb, g.ldc, g.beta, g.a16, g.c16 = len(probs), lda, ldb, ldc, beta, int(a16), int(c16)
-    for p, (M, N, K, segs, C, dyn) in enumerate(probs):
-        g.M[p], g.N[p], g.K[p], g.nseg[p], g.C[p], g.dyn[p] = M, N, K, len(segs), ptr(C), ptr(dyn)
-        for si, (A, B) in enumerate(segs):
+    for p, q in enumerate(GemmProb(*q) for q in probs):
+        g.M[p], g.N[p], g.K[p], g.nseg[p], g.C[p], g.dyn[p] = q.M, q.N, q.K, len(q.segs), ptr(q.C), ptr(q.dyn)
+        for si, (A, B) in enumerate(q.segs):
             g.A[p][si], g.B[p][si] = ptr(A), ptr(B)
     lib.srec_gemm_group_bf16(_ct.addressof(g), mode, stream())
 
 
-def gemm16(kind, probs, lda, ldb, ldc, beta=0.0, c16=False, keep_dead=False):
-    """one grouped launch of the bf16-in-HBM GEMMs (csrc/gemm16.hip).  probs: [(M, N, K, [(A16, B16), ...], C, dyn)].
-    kind 'nt': C [M, N] (+)= sum_s A_s [M, K] B_s [N, K]^T (c16: bf16 output);  'tn': C [M, N] = sum_s A_s [K, M]^T B_s [K, N]
-    (reduction over the K rows, clamped by dyn)."""
+def gemm16_desc(probs, lda, ldb, ldc, beta=0.0, c16=False, keep_dead=False):
+    """the srec_gemm16_group of one gemm16 launch (host struct; its pointers are the tensors' device pointers)"""
     assert 0 < len(probs) <= G16_MAXP
     g = GemmGroup16()
-    g.np, g.lda, g.ldb, g.ldc, g.beta, g.c16 = len(probs), lda, ldb, ldc, beta, int(c16) | (2 if keep_dead else 0)
-    for p, pr in enumerate(probs):
-        M, N, K, segs, C, dyn = pr[:6]
-        g.M[p], g.N[p], g.K[p], g.nseg[p], g.C[p], g.dyn[p] = M, N, K, len(segs), ptr(C), ptr(dyn)
-        g.koff[p] = pr[6] if len(pr) > 6 else 0          # tn: first reduction row of this piece of a row-split product
-        g.nsplit[p] = pr[7] if len(pr) > 7 else 1        # tn: in-kernel row split, C = [nsplit, M, N] slabs
-        if len(pr) > 8 and pr[8] is not None:            # per-problem (lda, ldb, ldc); 0 = the group's
-            g.lda_p[p], g.ldb_p[p], g.ldc_p[p] = pr[8]
-        if len(pr) > 9 and pr[9]:                        # nt: expected live rows of a capacity-padded problem
-            g.mhint[p] = int(pr[9])
-        for si, (A, B) in enumerate(segs):
+    g.np, g.lda, g.ldb, g.ldc, g.beta = len(probs), lda, ldb, ldc, beta
+    g.c16 = (CONST['SREC_G16_C_BF16'] if c16 else 0) | (CONST['SREC_G16_KEEP_DEAD'] if keep_dead else 0)
+    for p, q in enumerate(GemmProb(*q) for q in probs):
+        g.M[p], g.N[p], g.K[p], g.nseg[p], g.C[p], g.dyn[p] = q.M, q.N, q.K, len(q.segs), ptr(q.C), ptr(q.dyn)
+        g.koff[p], g.nsplit[p], g.mhint[p] = q.koff, q.nsplit, int(q.mhint or 0)
+        if q.ld is not None:                             # (0 = the group's)
+            g.lda_p[p], g.ldb_p[p], g.ldc_p[p] = q.ld
+        for si, (A, B) in enumerate(q.segs):
             g.A[p][si], g.B[p][si] = ptr(A), ptr(B)
+    return g
+
+
+def gemm16(kind, probs, lda, ldb, ldc, beta=0.0, c16=False, keep_dead=False):
+    """one grouped launch of the bf16-in-HBM GEMMs (csrc/gemm16.hip) over probs.  kind 'nt': C [M, N] (+)= sum_s A_s [M, K] B_s [N, K]^T
+    (c16: bf16 output);  'tn': C [M, N] = sum_s A_s [K, M]^T B_s [K, N] (reduction over the K rows, clamped by dyn)."""
+    g = gemm16_desc(probs, lda, ldb, ldc, beta, c16, keep_dead)
     (lib.srec_gemm16_nt if kind == 'nt' else lib.srec_gemm16_tn)(_ct.addressof(g), stream())
 
 
@@ -2619,106 +2626,6 @@ def weights_bf16(ws, transposed=True):
     return w16, wt16
 
 
-class HgPlan:
-    """Static topology of one MSHGNN layer call (built by msgifsr.MSHGNN from the FlatBatch).
-    types:   [(row0, ncap, dyn_n, seg)]                          node types, stacked rows
-    modules: [(row_start, n_rows, dyn)]                          rows of x each GAT module projects (dyn or None)
-    blocks:  [(module, type)]                                    projection blocks
-    insts:   [(module, src_block, dst_block, (in_ptr, in_idx, out_ptr, out_idx, esrc, edst))]"""
-
-    def __init__(self, H, D, slope, B, dynB, types, modules, blocks, insts, mod_conv=None):
-        self.mod_conv = mod_conv if mod_conv is not None else [0] * len(modules)      # 0: conv1, 1: conv2 (reversed graph)
-        self.layer_id = 0                                 # dropout-mask salt: distinct per MSHGNN layer of a model
-        self.H, self.D, self.slope, self.B, self.dynB = H, D, slope, B, dynB
-        self.types, self.modules, self.blocks, self.insts = types, modules, blocks, insts
-        assert (len(types) <= CONST['SREC_HG_MAXT'] and len(modules) <= CONST['SREC_HG_MAXM'] and
-                len(blocks) <= CONST['SREC_HG_MAXB'] and len(insts) <= CONST['SREC_HG_MAXI'])
-
-    def pieces(self, m):
-        """[(row offset inside module m's projection, first stacked row, rows, dyn)] - one piece per node type the module
-        covers: GEMM problems are cut at type boundaries so that every piece carries its own live row count (the shared
-        'inter' module spans all types; as ONE problem it would multiply the capacity padding between them too)"""
-        r0, nr, dyn = self.modules[m]
-        out = [(t0 - r0, t0, nc, dyn_t) for (t0, nc, dyn_t, _) in self.types if r0 <= t0 and t0 + nc <= r0 + nr]
-        assert sum(p[2] for p in out) == nr, 'a module projects whole node types'
-        return out
-
-    def scratch_layout(self):
-        """-> (n_floats, offsets) of the small per-call scratch: eL,eR,wL,wR per block; A,DP,der per instance"""
-        H, off, lay = self.H, 0, {}
-        for b, (m, t) in enumerate(self.blocks):
-            n = self.types[t][1] * H
-            for nm in ('eL', 'eR', 'wL', 'wR'):
-                lay[(nm, b)] = off
-                off += n
-        # (Z slot t < n_types also holds the summed bias row of node type t during the forward: slots for max(modules, types))
-        for m in range(max(len(self.modules), len(self.types))):
-            for nm in ('V', 'Z'):
-                lay[(nm, m)] = off
-                off += 2 * self.D * H
-        for i, (m, sb, db, gr) in enumerate(self.insts):
-            E = max(gr[4].numel(), 1) * H
-            nd = self.types[self.blocks[db][1]][1] * H
-            for nm, n in (('A', E), ('DP', E), ('der', nd)):
-                lay[(nm, i)] = off
-                off += n
-        for t in range(len(self.types)):                   # session means of the input rows per node type [B, D]
-            lay[('smean', t)] = off
-            off += self.B * self.D
-        lay[('sess', 0)] = off                             # session of every stacked row (int32)
-        off += sum(tp[1] for tp in self.types)
-        return off, lay
-
-    def fill(self, desc, small, lay, P, dP, params, grads, drop=None):
-        d = desc
-        if drop is not None:
-            xc, xres, rm, mk = drop[:4]
-            for m in range(len(self.modules)):
-                d.xin[m] = ptr(xc[self.mod_conv[m]])
-            d.xres, d.rm = ptr(xres), ptr(rm)
-            if rm is None and len(drop) > 6:               # rm recomputed in the backward from the masks' hash
-                pf_, seed_, rc_, salt_ = drop[5]
-                d.rm_cnt, d.rm_counter, d.rm_p, d.rm_seed, d.rm_salt = ptr(drop[6]), rc_, pf_, seed_, salt_
-            for i in range(len(self.insts)):
-                d.Mk[i] = ptr(mk[i]) if mk is not None else None
-        d.H, d.D, d.slope, d.B = self.H, self.D, self.slope, self.B
-        d.p16 = int(P[0].dtype == torch.bfloat16) if P else 0          # (P = None: the weight-only view srec_hg_fold reads)
-        d.n_types, d.n_mods, d.n_blocks, d.n_inst = len(self.types), len(self.modules), len(self.blocks), len(self.insts)
-        d.dynB = ptr(self.dynB)
-        for t, (r0, nc, dyn, seg) in enumerate(self.types):
-            d.row0[t], d.ncap[t], d.dyn_n[t], d.seg[t] = r0, nc, ptr(dyn), ptr(seg)
-        base = small.data_ptr()
-        for m in range(len(self.modules)):
-            W, al, ar, bias = params[4 * m:4 * m + 4]
-            d.P[m] = ptr(P[m]) if P else None
-            d.W[m] = ptr(W)
-            d.V[m], d.Z[m] = base + 4 * lay[('V', m)], base + 4 * lay[('Z', m)]
-            d.attn_l[m], d.attn_r[m], d.bias[m] = ptr(al), ptr(ar), ptr(bias)
-            if dP is not None:
-                d.dP[m] = ptr(dP[m])
-                d.d_attn_l[m], d.d_attn_r[m], d.d_bias[m] = (grads[m][j].data_ptr() for j in range(3))
-        for m in range(len(self.modules), len(self.types)):
-            d.Z[m] = base + 4 * lay[('Z', m)]
-        for t in range(len(self.types)):
-            d.smean[t] = base + 4 * lay[('smean', t)]
-        d.sess = base + 4 * lay[('sess', 0)]
-        for b, (m, t) in enumerate(self.blocks):
-            d.blk_mod[b], d.blk_type[b] = m, t
-            d.blk_row[b] = self.types[t][0] - self.modules[m][0]
-            for nm in ('eL', 'eR', 'wL', 'wR'):
-                getattr(d, nm)[b] = base + 4 * lay[(nm, b)]
-        for i, (m, sb, db, gr) in enumerate(self.insts):
-            d.inst_mod[i], d.inst_sblk[i], d.inst_dblk[i] = m, sb, db
-            for nm, g in zip(('in_ptr', 'in_idx', 'out_ptr', 'out_idx', 'esrc', 'edst'), gr):
-                getattr(d, nm)[i] = ptr(g)
-            for nm in ('A', 'DP', 'der'):
-                getattr(d, nm)[i] = base + 4 * lay[(nm, i)]
-        return d
-
-
-_HG_WS = {}
-
-
 # ---- the step's prologue launch (csrc/prep.hip) ----------------------------------------------------------------------------
 STEP_PROLOGUE = os.environ.get('SREC_STEP_PROLOGUE', '1') != '0'     # (tests / A-B runs: 0 = the one-launch-per-reader sequence)
 
@@ -2729,7 +2636,7 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
       w16:  fp32 matrices (<= 8) -> bf16 + transposed bf16 copies, taken by weights_bf16 (HGATLayer);
       gru:  GRU weights [3 d, d] (<= 2 SREC_GRU_MAXP) -> both fragment-major layouts, taken by gru_wfrag_both / gru_wfrag (GRUExpandAll);
       head: [(W, trans)] (<= SREC_HEAD_MAXW) -> hi / lo fragment-major copies, found by head_wfrag (ReadoutHeadFused) in its per-step cache;
-      fold: (plan, params) of an MSHGNN layer call -> plan.pre = its scratch with V / the bias sums written (HGATLayer).
+      fold: (plan, params) of an MSHGNN layer call -> its scratch with V / the bias sums written, handed to plan.put_fold (HGATLayer).
     Purely an optimisation: a reader that does not find its copies makes them itself."""
     q, keep = StepPrepDesc(), []
     w16 = [w for i, w in enumerate(w16) if all(w is not v for v in w16[:i])][:8]
@@ -2752,8 +2659,7 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
         keep.append(args)
     if fold is not None:
         plan, params = fold
-        nfl, lay = plan.scratch_layout()
-        small = torch.empty(max(nfl, 1), device=params[0].device, dtype=torch.float32)
+        small, lay = plan.scratch(params[0].device)
         flat = [p_.reshape(-1) if i % 4 else p_ for i, p_ in enumerate(params)]
         hd = plan.fill(HgDesc(), small, lay, None, None, flat, None, None)
         q.hg = _ct.addressof(hd)
@@ -2769,256 +2675,9 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
     for (w, t), b_ in zip(head, hb if head else ()):
         _HEAD_WF_CACHE[(w.data_ptr(), tuple(w.shape), t)] = b_
     if fold is not None:
-        plan.pre = (small, lay)
-
-
-_CNT_CACHE = {}
-
-
-def _inst_counts(plan, NT, dev):
-    """[2, NT, 1]: how many relation instances of conv1 / conv2 use each stacked row as a DESTINATION (identity residual
-    count, gatconv.py:306-308) - a function of the plan's static topology"""
-    key = (str(dev), NT, tuple(plan.mod_conv), tuple((m, tuple(plan.types[plan.blocks[db][1]][:2])) for (m, sb, db, gr) in plan.insts))
-    cnt = _CNT_CACHE.get(key)
-    if cnt is None:
-        host = torch.zeros(2, NT, 1)
-        for (m, sb, db, gr) in plan.insts:
-            t0, nc = plan.types[plan.blocks[db][1]][:2]
-            host[plan.mod_conv[m], t0:t0 + nc] += 1.0
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('instance counts must be cached by an eager warm-up step before graph capture')
-        cnt = _CNT_CACHE[key] = host.to(dev)
-    return cnt
+        plan.put_fold(small, lay)
 
 
 DROP_TAP = None      # tests: set to a list to receive {'ms': [2, NT, D], 'mk': [per instance (E*H,)]} of every dropout layer call
 
-
-class HGATLayer(torch.autograd.Function):
-    """out = MSHGNN(x): all relation instances of conv1 / conv2 in one batched pass (csrc/hgat.hip) around the fc
-    GEMMs.  params = (fc.weight, attn_l, attn_r, bias) per module, in plan.modules order.
-    drop = (p_feat, p_attn) in training: feature dropout with ONE mask per (conv, node type) on the inputs of that
-    conv's GATConv modules (projection, logits and identity residual all see the dropped rows, gatconv.py:268-308;
-    the reference draws one mask per (relation, role) - documented deviation) and attention dropout on the edge
-    soft-max (gatconv.py:300)."""
-
-    @staticmethod
-    def forward(ctx, x, plan, drop, *params):
-        x = _rows(x)
-        NT, D = x.shape
-        H = plan.H
-        HD = H * D
-        dev = x.device
-        nm = len(plan.modules)
-        dstate = None
-        if drop is not None and (drop[0] > 0 or drop[1] > 0):
-            pf, pa = drop
-            # both convs' feature masks and every instance's attention mask in ONE launch (counter-based hash: no generator
-            # state, replay-safe); the per-row instance counts depend on the plan only (cached)
-            cnt = _inst_counts(plan, NT, dev)
-            # (the mask tensor itself is written only for the tests' tap: the backward recomputes the masks from the hash)
-            ms = torch.empty(2, NT, D, device=dev, dtype=torch.float32) if DROP_TAP is not None else None
-            xcs = torch.empty(2, NT, D, device=dev, dtype=torch.float32)
-            rm, xres = None, torch.empty(NT, D, device=dev)     # (rm = cnt0 m0 + cnt1 m1 is recomputed by the backward)
-            xcont = x.contiguous()
-            mk, allm, na = None, None, 0
-            if pa > 0:
-                sizes = [max(gr[4].numel(), 1) * H for (_, _, _, gr) in plan.insts]
-                na = sum(sizes)
-                allm = torch.empty(na, device=dev, dtype=torch.float32)
-                mk = list(torch.split(allm, sizes))
-            seed, rc = rng_args(dev)
-            # the bf16 GEMM path reads bf16(xcs): written by the same pass
-            x16_pre = None
-            if PRECISION['matmul'] == 'bf16' and D % 64 == 0 and nm <= 8 and all(params[4 * m].is_contiguous() for m in range(nm)):
-                x16_pre = torch.empty(2, NT, D, device=dev, dtype=torch.bfloat16)
-                lib.srec_hg_drop_prep16(ptr(xcont), ptr(cnt), NT, D, float(pf), seed, rc, 101 + 2 * plan.layer_id, ptr(ms),
-                                        ptr(xcs), ptr(rm), ptr(xres), float(pa), na, ptr(allm), ptr(x16_pre), stream())
-            else:
-                lib.srec_hg_drop_prep(ptr(xcont), ptr(cnt), NT, D, float(pf), seed, rc, 101 + 2 * plan.layer_id, ptr(ms),
-                                      ptr(xcs), ptr(rm), ptr(xres), float(pa), na, ptr(allm), stream())
-            xc = [xcs[0], xcs[1]]
-            dstate = (xc, xres, rm, mk, ms, (float(pf), seed, rc, 101 + 2 * plan.layer_id), cnt)
-            if DROP_TAP is not None:
-                DROP_TAP.append(dict(ms=ms.clone(), mk=[m.clone() for m in mk] if mk is not None else None))
-        xin = (lambda m: dstate[0][plan.mod_conv[m]]) if dstate is not None else (lambda m: x)
-        grouped = PRECISION['matmul'] == 'bf16' and D % 8 == 0 and _ld(x) == D and nm <= 8
-        # bf16 GEMM path: the projections (and their gradients) are STORED as bf16 too - every pass over them is HBM bound
-        P = [torch.empty(nr, HD, device=dev, dtype=torch.bfloat16 if grouped else torch.float32)
-             for (r0, nr, dyn) in plan.modules]
-        g16 = None
-        if grouped and D % 64 == 0 and all(params[4 * m].is_contiguous() for m in range(nm)):
-            # every GEMM operand as bf16 in HBM (csrc/gemm16.hip): the small weights once per call (+ transposed copies for
-            # the backward-data product), the module inputs in one pass
-            w16, wt16 = weights_bf16([params[4 * m] for m in range(nm)])
-            if dstate is not None:
-                x16 = x16_pre if x16_pre is not None else rows_bf16(xcs.view(2 * NT, D)).view(2, NT, D)
-                xin16 = lambda m: x16[plan.mod_conv[m]]
-            else:
-                x16 = rows_bf16(x)
-                xin16 = lambda m: x16
-            live = getattr(plan, 'live', {})             # host-side live row counts per type start (tile heuristics only)
-            probs = [(nc, HD, D, [(xin16(m)[t0:t0 + nc], w16[m])], P[m][o:o + nc], dyn_t, 0, 1, None, live.get(t0, 0))
-                     for m in range(nm) for (o, t0, nc, dyn_t) in plan.pieces(m)]
-            for i in range(0, len(probs), G16_MAXP):
-                # rows past a type's live count are never read (every hgat.hip kernel walks the live prefix only)
-                gemm16('nt', probs[i:i + G16_MAXP], D, D, HD, c16=True, keep_dead=True)
-            g16 = (x16, wt16)
-        elif grouped:
-            gemm_group(0, [(nr, HD, D, [(xin(m)[r0:r0 + nr], params[4 * m])], P[m], dyn)
-                           for m, (r0, nr, dyn) in enumerate(plan.modules)], D, D, HD, c16=True)
-        else:
-            for m, (r0, nr, dyn) in enumerate(plan.modules):
-                gemm_nt(xin(m)[r0:r0 + nr], _rows(params[4 * m]), P[m], None, dyn, 1 if dyn is not None else 0)
-        pre = plan.__dict__.pop('pre', None)         # the prologue launch of this forward already folded the weights (step_prologue)
-        if pre is not None:
-            small, lay = pre
-        else:
-            nfl, lay = plan.scratch_layout()
-            small = torch.empty(max(nfl, 1), device=dev, dtype=torch.float32)
-        out = torch.empty(NT, D, device=dev, dtype=torch.float32)
-        arg = torch.empty(NT, D, device=dev, dtype=torch.uint8)
-        flat = [p.reshape(-1) if i % 4 else p for i, p in enumerate(params)]
-        desc = plan.fill(HgDesc(), small, lay, P, None, flat, None, dstate)
-        if pre is not None:
-            desc.p16 |= 8
-        lib.srec_hg_fwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(out), D, ptr(arg), stream())
-        ctx.save_for_backward(x, small, arg, *P, *params)
-        ctx.plan, ctx.lay, ctx.grouped, ctx.dstate, ctx.g16 = plan, lay, grouped, dstate, g16
-        ctx.defer, ctx.wparams = defer_scope(), [params[4 * m] for m in range(len(plan.modules))]
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        plan, lay, dstate = ctx.plan, ctx.lay, ctx.dstate
-        nm = len(plan.modules)
-        x, small, arg = ctx.saved_tensors[:3]
-        P = ctx.saved_tensors[3:3 + nm]
-        params = ctx.saved_tensors[3 + nm:]
-        g = _rows(g)
-        NT, D = x.shape
-        HD = plan.H * D
-        dev = x.device
-        # rows of a module's projection that no relation instance touches (a type without live 'inter' edges) get no
-        # gradient from the kernels: those buffers start from zero
-        cov = [sum(plan.types[bt][1] for bm, bt in plan.blocks if bm == m) for m in range(nm)]
-        dP = [torch.empty_like(p) if cov[m] == p.shape[0] else torch.zeros_like(p) for m, p in enumerate(P)]
-        # (attn_l, attn_r, bias gradients: [HD] each - the parameters' bucket slots when the table is row-sharded, ops.grad_buf)
-        grads = [[grad_buf(params[4 * m + 1 + j]).view(-1) for j in range(3)] for m in range(nm)]
-        dx = torch.empty(NT, D, device=dev, dtype=torch.float32)
-        flat = [p.reshape(-1) if i % 4 else p for i, p in enumerate(params)]
-        desc = plan.fill(HgDesc(), small, lay, P, dP, flat, grads, dstate)
-        if ctx.g16 is not None and desc.p16:
-            desc.p16 |= 2           # both gemm16 consumers of dP stop at the live rows: srec_hg_bwd leaves capacity-padding rows unwritten
-        # feature dropout with recomputed masks: d x is written once, after the backward-data GEMMs (srec_hg_pre_merge)
-        late_dx = dstate is not None and dstate[2] is None and len(dstate) > 6 and dstate[4] is None and _ld(g) % 4 == 0
-        if late_dx:
-            desc.p16 |= 4
-        n = _ct.c_long()
-        lib.srec_hg_ws_floats(_ct.addressof(desc), _ct.addressof(n))
-        key = (dev.index, n.value)
-        ws = _HG_WS.get(key)
-        if ws is None:
-            ws = _HG_WS[key] = torch.empty(max(n.value, 1), device=dev, dtype=torch.float32)
-        lib.srec_hg_bwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(g), _ld(g), ptr(arg), ptr(dx), D, ptr(ws), stream())
-        xin = (lambda m: dstate[0][plan.mod_conv[m]]) if dstate is not None else (lambda m: x)
-        gWs = [grad_buf(params[4 * m]) for m in range(nm)]
-        convs = (0, 1) if dstate is not None else (None,)
-        tgts = None
-        S = 1
-        if dstate is not None:
-            # every node type is projected by some module of each conv in the usual plans: the grouped GEMM then writes all
-            # rows (beta = 0 zeroes rows past the live count) and the buffers need no fill
-            full = ctx.grouped and all(any(plan.mod_conv[bm] == cv and bt == t for bm, bt in plan.blocks)
-                                       for cv in (0, 1) for t in range(len(plan.types)))
-            # gemm16: when every (conv, type) is projected by the same number S of modules (intra_k + the shared 'inter'),
-            # each module's product goes to its own partial buffer (S x more, S x shorter reduction loops in flight) and
-            # the merge kernel sums them
-            nsegs = {sum(1 for m in range(nm) if plan.mod_conv[m] == cv and any(bm == m and bt == t for bm, bt in plan.blocks))
-                     for cv in (0, 1) for t in range(len(plan.types))}
-            if ctx.g16 is not None and full and len(nsegs) == 1 and 1 < min(nsegs) <= 4:
-                S = min(nsegs)
-            tgts = (torch.empty if full else torch.zeros)(2, S, NT, D, device=dev, dtype=torch.float32)
-        pend = []                                    # gemm16: the two convs' backward-data problems share ONE launch
-        for cv in convs:
-            # d x of one node type = sum over the modules that project it: the module sum is the K loop (segments).
-            # With feature dropout the two convs see differently masked inputs: one masked contribution per conv.
-            tgt = dx if cv is None else tgts[cv, 0]
-            mods = [m for m in range(nm) if cv is None or plan.mod_conv[m] == cv]
-            if ctx.grouped:
-                probs = []
-                for t, (t0, nc, dyn_t, _) in enumerate(plan.types):
-                    segs = [(dP[m][t0 - plan.modules[m][0]:t0 - plan.modules[m][0] + nc], m) for m in mods
-                            if plan.modules[m][0] <= t0 and t0 + nc <= plan.modules[m][0] + plan.modules[m][1]
-                            and any(bm == m and bt == t for bm, bt in plan.blocks)]
-                    if segs:
-                        probs.append((nc, D, HD, segs, tgt[t0:t0 + nc], dyn_t, t0))
-                beta = 0.0 if (cv is not None and full) else 1.0
-                if probs and ctx.g16 is not None and S > 1:
-                    wt16 = ctx.g16[1]
-                    live = getattr(plan, 'live', {})
-                    for (M_, N_, K_, segs_, C_, dyn_, t0) in probs:
-                        for j, (A_, m_) in enumerate(segs_):
-                            pend.append(((M_, N_, K_, [(A_, wt16[m_])], tgts[cv, j, t0:t0 + M_], dyn_, 0, 1, None, live.get(t0, 0)), 0.0))
-                elif probs and ctx.g16 is not None:
-                    wt16 = ctx.g16[1]
-                    live = getattr(plan, 'live', {})
-                    pend += [((M_, N_, K_, [(A_, wt16[m_]) for A_, m_ in segs_], C_, dyn_, 0, 1, None, live.get(_t0, 0)), beta)
-                             for (M_, N_, K_, segs_, C_, dyn_, _t0) in probs]
-                elif probs:
-                    probs = [(M_, N_, K_, [(A_, params[4 * m_]) for A_, m_ in segs_], C_, dyn_)
-                             for (M_, N_, K_, segs_, C_, dyn_, _t0) in probs]
-                    gemm_group(1, probs, HD, D, D, beta=beta, a16=True)
-            else:
-                for m in mods:
-                    r0, nr, dyn = plan.modules[m]
-                    gemm_nn(dP[m], _rows(params[4 * m]), tgt[r0:r0 + nr], dyn, 1 if dyn is not None else 0, beta=1.0)
-        while pend:
-            beta = pend[0][1]
-            batch = [pr for pr, b in pend if b == beta][:G16_MAXP]
-            pend = [(pr, b) for pr, b in pend if not any(pr is q for q in batch)]
-            gemm16('nt', batch, HD, HD, D, beta=beta)
-        if late_dx:
-            lib.srec_hg_pre_merge(_ct.addressof(desc), ptr(g), _ld(g), ptr(tgts), S, ptr(dx), D, stream())
-        elif dstate is not None:
-            pf_, seed_, rc_, salt_ = dstate[5]
-            lib.srec_hg_drop_merge(ptr(tgts), S, ptr(dstate[4]), NT * D, ptr(dx), pf_, seed_, rc_, salt_, stream())
-        if ctx.g16 is not None:
-            # weight gradients, one balanced problem per (module, node type): a module that spans several types (the shared
-            # 'inter' one) writes one slab per type, summed in fixed order afterwards
-            x16 = ctx.g16[0]
-            xin16 = (lambda m: x16[plan.mod_conv[m]]) if dstate is not None else (lambda m: x16)
-            pcs = [plan.pieces(m) for m in range(nm)]
-            multi = [m for m in range(nm) if len(pcs[m]) > 1]
-            slabs = {}
-            if multi:
-                gWm = [gWs[m] for m in multi]
-                for i, m in enumerate(multi):
-                    slabs[m] = torch.empty(len(pcs[m]), HD, D, device=dev, dtype=torch.float32)
-            probs = []
-            for m in range(nm):
-                for pi, (o, t0, nc, dyn_t) in enumerate(pcs[m]):
-                    tgt = gWs[m] if m not in slabs else slabs[m][pi:pi + 1]
-                    probs.append((HD, D, nc, [(dP[m][o:o + nc], xin16(m)[t0:t0 + nc])], tgt, dyn_t, 0, 1))
-            for i in range(0, len(probs), G16_MAXP):
-                gemm16('tn', probs[i:i + G16_MAXP], HD, D, D)
-            if multi and can_defer(ctx.defer, [ctx.wparams[m] for m in multi]):
-                for i, m in enumerate(multi):
-                    defer_slab_sum(slabs[m], gWm[i])
-            elif multi:
-                _launch_slab_sums([(slabs[m], gWm[i]) for i, m in enumerate(multi)])
-        elif ctx.grouped:
-            gemm_group(2, [(HD, D, nr, [(dP[m], xin(m)[r0:r0 + nr])], gWs[m], dyn)
-                           for m, (r0, nr, dyn) in enumerate(plan.modules)], HD, D, D, a16=True)
-        outs = []
-        for m, (r0, nr, dyn) in enumerate(plan.modules):
-            gW = gWs[m]
-            if not ctx.grouped:
-                gemm_tn(dP[m], xin(m)[r0:r0 + nr], gW, dyn)
-            outs += [gW, grads[m][0].view(params[4 * m + 1].shape), grads[m][1].view(params[4 * m + 2].shape),
-                     grads[m][2].view(params[4 * m + 3].shape)]
-        return (dx, None, None) + tuple(outs)
-
-
-def hgat_layer(x, plan, params, drop=None):
-    return HGATLayer.apply(x, plan, drop, *params)
+from .hgat import HgPlan, HGATLayer, hgat_layer  # noqa: E402,F401  (the MSHGNN layer: hgat.py imports this module)

@@ -52,12 +52,15 @@ ATTN_SCALE = 6.0          # attn_l / attn_r = their U(-1/sqrt d, 1/sqrt d) initi
 
 
 # ------------------------------------------------------------------------------------------------------------ inputs
-_SHORT = {'short2212': (2, 2, 1, 2), 'short231': (2, 3, 1)}     # lens of test_msgifsr_batches_with_missing_relations
+_SHORT = {'short2212': (2, 2, 1, 2), 'short231': (2, 3, 1), 'single111': (1, 1, 1)}     # lens of test_msgifsr_batches_with_missing_relations
+ROWS532 = [([11, 12, 13], 15), ([16, 17], 18)]                  # 5 / 3 / 2 nodes of order 1 / 2 / 3
 
 
 def _samples(batch):
     if batch in ('s32', 'edge'):
         return load_golden('msgifsr_K3_' + batch)[1]
+    if batch == 'rows532':
+        return ROWS532
     if batch == 'big':
         from dist_gpu_worker import synth_samples
         return synth_samples(512, V, 11)
@@ -433,14 +436,19 @@ def param_names(layer, params):
     return [ids[id(p)] for p in params]
 
 
-def run_layer(dev, layer, mg, x, cot, drop, all_rels, tap, seed=21):
+def run_layer(dev, layer, mg, x, cot, drop, all_rels, tap, seed=21, strided=False):
     """one forward + backward of ops.hgat_layer -> (out, dx, {param name: grad}, tapped masks or None).  cot: callable
-    (out, tap) -> stacked cotangent (the reference needs the masks of THIS call first) or a tensor"""
+    (out, tap) -> stacked cotangent (the reference needs the masks of THIS call first) or a tensor.  strided: the same rows
+    as a column slice of a [NT, 2 d] matrix (unit inner stride, row stride 2 d)"""
     ops = pkg('ops')
     plan, params = layer.plan(mg, x.shape[1], all_rels)
     names = param_names(layer, params)
     ps = [p.detach().clone().requires_grad_() for p in params]
-    xr = x.to(dev).requires_grad_()
+    xr = x.to(dev)
+    if strided:
+        xr = torch.cat([torch.zeros_like(xr), xr], 1)[:, x.shape[1]:].detach()
+        assert xr.stride() == (2 * x.shape[1], 1)
+    xr.requires_grad_()
     ops.DROP_TAP = [] if tap else None
     try:
         reseed(seed)
@@ -613,3 +621,75 @@ def test_padded_rows_are_never_read_and_stay_zero(dev, route, d, batch, drop, mo
         assert set(zero[2]) == set(exact[2])
         for nm, a, b in pairs:
             close(a, b, rtol=1e-4, atol=1e-7, what='padded vs exact ' + nm)
+
+
+def test_row_strided_input_equals_the_contiguous_call(dev):
+    """bf16 mode, D = 64, node types of 5 / 3 / 2 rows, dropout (0.3, 0.3): x given as a column slice of a [10, 128] matrix
+    (_ld(x) != D) against the same call on x.contiguous().  The GEMM strategy is chosen once per call (hgat.gemm_strategy): the
+    contiguous call takes gemm16, the strided one the per-module products, and the dropout prep writes its bf16 operand copy
+    only for the former - same masks (same nonce, keyed by the element's position), same kernels around the GEMMs.  Both calls
+    are bf16-route evaluations of the same function, so they must agree as closely as this file asks a bf16-route result to agree
+    with the float64 oracle: err_of against the contiguous call <= bound_of of the gemm16 route (MARGIN x the rounding-emulated
+    oracle run's own error), out, d x and every parameter gradient; contested arg-max cells carry no cotangent, as in the
+    oracle test.  Both calls run untapped (the production path: masks recomputed, d x finished by srec_hg_pre_merge)."""
+    ops = pkg('ops')
+    d, drop = 64, (0.3, 0.3)
+    model, layer64, samples, og = make_case(d, 'rows532', rounded=True)
+    layer = model.to(dev).layers[0]
+    mg = collate(samples, False).to(dev)
+    assert [n for _, n, _ in type_rows(mg)[0]] == [5, 3, 2]
+    xt = make_x(og, d, rounded=True)
+    x = stack(mg, xt)
+    box = {}
+
+    def cot(out, tap):
+        if 'ref' not in box:
+            box['ref'] = Reference(layer64, og, xt, oracle_masks(mg, tap, d, False), False, 'gemm16')
+        return stack(mg, box['ref'].cot)
+
+    ops.set_precision('bf16')
+    try:
+        run_layer(dev, layer, mg, x, cot, drop, False, tap=True)            # (the masks of this seed, for the cotangent)
+        runs = [run_layer(dev, layer, mg, x, cot, drop, False, tap=False, strided=st) for st in (False, True)]
+    finally:
+        ops.set_precision('fp32')
+    ref = box['ref']
+    want, yard = tensors_of(ref.r64), [tensors_of(r) for r in ref.yard]
+    scales = kind_scales(want)
+    cont, strd = [dict({'out': out, 'dx': dx}, **{'/'.join(n): g for n, g in grads.items()}) for out, dx, grads, _ in runs]
+    assert set(cont) == set(strd) == set(want)
+    failures = []
+    for n in sorted(want):
+        e, bound = err_of(n, strd[n].reshape(want[n].shape), cont[n].reshape(want[n].shape), scales), bound_of(n, yard, want, scales)
+        print('HGAT strided vs contiguous %s: %.3e / %.3e' % (n, e, bound))
+        if not e <= bound:
+            failures.append('%s: strided vs contiguous %.3e > bound %.3e' % (n, e, bound))
+    assert not failures, '\n'.join(failures)
+
+
+def test_a_plan_without_modules_in_bf16_mode(dev, monkeypatch):
+    """Sessions of one click: no relation has an edge, so the plan has no GAT module and the layer is out = x's session mean per
+    row (msgifsr.py:86-89).  D = 64 in bf16 mode is where the gemm16 route would be taken if there were anything to multiply:
+    hgat.gemm_strategy answers 'plain' for a module-less plan and no GEMM wrapper is called.  out and d x against the float64
+    oracle at the file's bf16-route bound (no product is involved: the errors are fp32 summation order)."""
+    ops, d = pkg('ops'), 64
+    model, layer64, samples, og = make_case(d, 'single111', rounded=True)
+    layer = model.to(dev).layers[0]
+    mg = collate(samples, False).to(dev)
+    plan, params = layer.plan(mg, d, False)
+    assert len(plan.modules) == 0 and len(params) == 0
+    xt = make_x(og, d, rounded=True)
+    ref = Reference(layer64, og, xt, None, False, 'gemm16')
+    spy = Spy(monkeypatch)
+    ops.set_precision('bf16')
+    try:
+        out, dx, grads, _ = run_layer(dev, layer, mg, stack(mg, xt), stack(mg, ref.cot), None, False, tap=False)
+    finally:
+        ops.set_precision('fp32')
+    assert spy.route() == 'none' and grads == {}
+    want, yard = tensors_of(ref.r64), [tensors_of(r) for r in ref.yard]
+    assert set(want) == {'out', 'dx'}
+    for n, got in (('out', out), ('dx', dx)):
+        e, bound = err_of(n, got, want[n], {}), bound_of(n, yard, want, {})
+        print('HGAT no modules %s: %.3e / %.3e' % (n, e, bound))
+        assert e <= bound, '%s: error %.3e > bound %.3e' % (n, e, bound)
