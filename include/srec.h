@@ -495,6 +495,26 @@ int srec_score_rank(const float* sr, int ld_sr, long comp_stride, const float* E
                     const float* off_ex, const float* off_in, const int* listed, int L, const int* labels, long id_lo,
                     int B, int V, int d, int C, float* target, int target_given, int* rank, void* ws, void* stream);
 
+/* ---- serving: the K best items per session under the score of srec_score_rank (recommend.hip) --------------------------
+ * The score is EXACTLY that of srec_score_rank, with the same layouts and limits (sr: C blocks [B, d]; off_ex / off_in [C, B],
+ * NULL = 0; listed [B, L] global ids, -1 = empty slot; cs / off_* / listed nullable; 1 <= C <= 4, d % 4 == 0, d <= 1024,
+ * L <= 64; fp32 MFMA, no (B, V) tensor):
+ *   s[b,v] = logsumexp_{c<C}( cs[v] * <sr_c[b], E_v> + off[c,b] )      (C == 1: z + off, no exp / log)
+ * listed_mode SREC_LISTED_SCORE: an item of listed[b,:] scores with off_in, as in srec_score_rank; SREC_LISTED_DROP: an item
+ * of listed[b,:] is never returned for session b and off_in is ignored.
+ * out_val [B, K] fp32 descending, out_idx [B, K] int32 global ids id_lo + row; ties towards the lower id (srec_score_topk,
+ * srec_score_rank); a session with fewer than K eligible rows gets (-INFINITY, -1) in the remaining slots, so K > V is
+ * allowed.  1 <= K <= SREC_SELECT_MAXK.  The output is a pure function of the inputs (no atomics; lists are ordered by
+ * (value, id), never by arrival).  ws: srec_score_select_ws() bytes (per-range partial lists). */
+#define SREC_SELECT_MAXK 128
+#define SREC_LISTED_SCORE 0
+#define SREC_LISTED_DROP 1
+int srec_score_select_ws(int B, int V, int d, int C, int L, int K, long* bytes);
+int srec_score_select(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                      long id_lo, int B, int V, int d, int C, int K,
+                      float* out_val, int* out_idx, void* ws, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

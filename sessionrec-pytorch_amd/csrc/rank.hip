@@ -10,7 +10,8 @@
 //
 // Target pass (rank_target_kernel): one wavefront per session scores the label's row (off_in if the label is listed);
 //   it also initialises rank[b] (0, or -1 for a label < 0).
-// Count pass (rank_count_kernel, the hot path): workgroup = 32 sessions x one item range, 4 wavefronts.  The C session
+// Count pass (rank_count_kernel, the hot path; its tile product is score_tile.h, shared with recommend.hip): workgroup = 32
+//   sessions x one item range, 4 wavefronts.  The C session
 //   tiles sit in LDS for the lifetime of the workgroup (C = 3, d = 256: 98 KB); each wavefront owns 32 items of a
 //   128-item chunk whose rows stream straight from HBM into the B operand of v_mfma_f32_32x32x2_f32 (exact fp32): lane
 //   (item r, half h) loads the float4 at columns 8j + 4h, the A lane reads the same columns of its session from LDS, so the
@@ -27,14 +28,11 @@
 // Session tiles that do not fit the 160 KB of LDS (896 B of per-session scalars + C * 32 * (d + 4) floats, d rounded up to
 // 32: C * (d + 4) > 1273) are read through the cache instead - same code.
 #include "common.h"
+#include "score_tile.h"
 
 namespace {
 
-constexpr int SB = 32;          // sessions per workgroup (one MFMA tile edge)
-constexpr int CHUNK = 128;      // items per step: 32 per wavefront
-constexpr int MAXCOMP = 4;
-constexpr int MAXL = 64;
-constexpr int LDS_BYTES = 160 * 1024;
+using namespace score_tile;      // SB sessions x CHUNK items per step, mix<C>, the MFMA tile product (score_tile.h)
 
 struct RankArgs {
     const float* sr; int ld_sr; long comp_stride;
@@ -50,22 +48,6 @@ struct RankArgs {
 };
 
 __device__ __forceinline__ bool ahead(float s, long id, float t, long lab) { return s > t || (s == t && id < lab); }
-
-template <int C>
-__device__ __forceinline__ float mix(const float (&z)[C]) {
-    if constexpr (C == 1) {
-        return z[0];
-    } else {
-        float m = z[0];
-#pragma unroll
-        for (int c = 1; c < C; ++c) m = fmaxf(m, z[c]);
-        if (m == -INFINITY) return m;
-        float l = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) l += expf(z[c] - m);
-        return m + logf(l);
-    }
-}
 
 // one wavefront: raw dot products <sr_c[b], E_v>, c < C, the same value in every lane
 template <int C>
@@ -142,8 +124,6 @@ template <int C, bool SR_LDS>
 __global__ __launch_bounds__(256) void rank_count_kernel(RankArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int d = a.d;
-    const int dp = (d + 31) & ~31;                       // the k loop runs in groups of 32 columns
-    const int LD = dp + 4;                               // 16-byte aligned rows, row stride = 4 banks mod 32
     float* tgt = smem;                                   // [SB]
     float* offs = tgt + SB;                              // [MAXCOMP][SB]
     int* labs = reinterpret_cast<int*>(offs + MAXCOMP * SB);   // [SB] label - id_lo (clamped), or a value no row has
@@ -169,25 +149,12 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankArgs a) {
         const int c = i / SB, b = b0 + i % SB;
         offs[c * SB + i % SB] = (a.off_ex != nullptr && b < a.B) ? a.off_ex[(size_t)c * a.B + b] : 0.f;
     }
-    if (SR_LDS) {
-        const int q = dp / 4;
-        for (int i = tid; i < C * SB * q; i += 256) {
-            const int row = i / q, k = (i % q) * 4;
-            const int c = row / SB, b = b0 + row % SB;
-            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (b < a.B && k < d) x = *reinterpret_cast<const float4*>(a.sr + (size_t)c * a.comp_stride + (size_t)b * a.ld_sr + k);
-            *reinterpret_cast<float4*>(Ss + (size_t)row * LD + k) = x;
-        }
-    }
+    if (SR_LDS) stage_tiles<C>(Ss, a.sr, a.ld_sr, a.comp_stride, b0, a.B, d, tid);
     __syncthreads();
 
     // A operand rows: this lane's session (clamped when read through the cache; such sessions count nothing)
     const float* arow[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        if (SR_LDS) arow[c] = Ss + (size_t)(c * SB + l31) * LD + 4 * half;
-        else arow[c] = a.sr + (size_t)c * a.comp_stride + (size_t)min(b0 + l31, a.B - 1) * a.ld_sr + 4 * half;
-    }
+    a_rows<C, SR_LDS>(arow, Ss, a.sr, a.ld_sr, a.comp_stride, b0, a.B, d, l31, half);
 
     int clo[16], chi[16];                                // wave-uniform counts: session (r&3)+8(r>>2) and the one 4 above
 #pragma unroll
@@ -199,50 +166,12 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankArgs a) {
         const float* brow = a.E + (size_t)min(v, a.V - 1) * a.ld_e + 4 * half;
         const float csv = (a.cs != nullptr && vok) ? a.cs[v] : 1.f;
         f32x16 acc[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-
-        // 32 columns per group: 4 float4 of the item row per lane, loaded one group AHEAD of the MFMAs that consume them
-        float4 bq[4], bn[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = 8 * j + 4 * half;
-            bq[j] = k < d ? *reinterpret_cast<const float4*>(brow + 8 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        for (int g = 0; g < dp; g += 32) {
-            if (g + 32 < dp) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k = g + 32 + 8 * j + 4 * half;
-                    bn[j] = k < d ? *reinterpret_cast<const float4*>(brow + g + 32 + 8 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float4 aq[C];
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    if (SR_LDS || g + 8 * j + 4 * half < d) aq[c] = *reinterpret_cast<const float4*>(arow[c] + g + 8 * j);
-                    else aq[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[c].x, bq[j].x, acc[c], 0, 0, 0);
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[c].y, bq[j].y, acc[c], 0, 0, 0);
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[c].z, bq[j].z, acc[c], 0, 0, 0);
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[c].w, bq[j].w, acc[c], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bq[j] = bn[j];
-        }
+        dots<C, SR_LDS>(arow, brow, d, half, acc);
 
         // per-lane epilogue: item v (this lane's column) against 16 sessions
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int sl = (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int sl = session_of(r, half);
             float z[C];
 #pragma unroll
             for (int c = 0; c < C; ++c) z[c] = csv * acc[c][r] + offs[c * SB + sl];
@@ -279,7 +208,7 @@ inline int pick_ranges(int B, int V) {
 
 inline size_t count_lds(int C, int d, bool sr_lds) {
     const size_t head = (size_t)(SB + MAXCOMP * SB + SB + SB) * 4;
-    return head + (sr_lds ? (size_t)C * SB * (((d + 31) & ~31) + 4) * 4 : 0);
+    return head + (sr_lds ? tile_bytes(C, d) : 0);
 }
 
 template <int C, bool SR_LDS>

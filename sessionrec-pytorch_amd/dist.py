@@ -423,6 +423,11 @@ class HipLocal:
         from . import ops
         return ops.score_rank(srs, table, cs, labels, off_ex, off_in, listed, id_lo, target, target_only)
 
+    def select(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo):
+        """this shard's k best rows (values, global ids) of ops.score_select: rows [id_lo, id_lo + n) of the catalog"""
+        from . import ops
+        return ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo)
+
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
 
@@ -835,6 +840,45 @@ class VocabParallel:
         if data_parallel:
             rank = rank[self.rank * n_loc:(self.rank + 1) * n_loc]
         return rank
+
+    def select(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False):
+        """the k best items of every session over the sharded table (ops.score_select's contract; srs: list of C [B, d]
+        session vectors, off_ex / off_in [C, B], listed [B, L] global ids): every rank selects among its own LIVE rows with
+        its id_lo (padding rows are never scored), ONE all-gather carries the (value, id) pairs of all ranks, and the lists
+        are merged by (value descending, id ascending) - the order of one device.  data_parallel as in topk()."""
+        n_loc = srs[0].shape[0]
+        if data_parallel:
+            srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
+            gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
+            off_ex, off_in = gat(off_ex), gat(off_in)
+            if listed is not None:           # lists of different widths on the ranks: pad to the widest
+                w = torch.tensor([listed.shape[1]], dtype=torch.int64, device=listed.device)
+                if _active(self.group):
+                    all_reduce_(w, dist.ReduceOp.MAX, self.group)
+                pad = listed.new_full((listed.shape[0], int(w.item())), -1)
+                pad[:, :listed.shape[1]] = listed
+                listed = all_gather_cat(pad, self.group)
+        B, dev = srs[0].shape[0], srs[0].device
+        if self.n_live > 0:
+            csl = None if cs is None else cs[:self.n_live]
+            val, idx = self.local.select(srs, table[:self.n_live], csl, k, off_ex, off_in, listed, drop_listed, self.lo)
+        else:
+            val = torch.full((B, k), float('-inf'), device=dev)
+            idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
+        if _active(self.group):
+            w = self.world
+            pair = all_gather_cat(torch.stack([val.view(torch.int32), idx], 0), self.group).view(w, 2, B, k)
+            val = pair[:, 0].permute(1, 0, 2).reshape(B, w * k).view(torch.float32)
+            idx = pair[:, 1].permute(1, 0, 2).reshape(B, w * k)
+            # merge: descending value, ties towards the lower item id, unfilled slots (-inf, -1) last (two stable sorts)
+            key = torch.where(idx < 0, torch.full_like(idx, 2 ** 31 - 1), idx)
+            o = torch.argsort(key, dim=1, stable=True)
+            val, idx = val.gather(1, o), idx.gather(1, o)
+            o = torch.argsort(val, dim=1, descending=True, stable=True)[:, :k]
+            val, idx = val.gather(1, o).contiguous(), idx.gather(1, o).contiguous()
+        if data_parallel:
+            val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
+        return val, idx
 
     # ---- replicated-parameter gradients: bucketed all-reduce, launched in backward order ----------------------------------
     N_BUCKETS = 3

@@ -566,35 +566,50 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             return super().target_rank(*inputs, labels=labels)
         (mg,) = inputs
         with torch.no_grad():
-            srs = self.session_repr(mg)
-            if not isinstance(srs, (list, tuple)):
-                srs = [srs]
-            B = srs[0].shape[0]
-            st = self._state(B)
-            cs, inv_scale = self._col_scale(st)
-            la = torch.log_softmax(self.alpha, 0) if len(srs) > 1 else srs[0].new_zeros(1)
-            lab32 = labels.to(torch.int32)
-            listed = None
+            srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg, labels)
+            return self._rank_of(srs, cs, labels, off_ex, off_in, listed)
+
+    def _mixture_offsets(self, mg, labels=None):
+        """(session vectors per order, column scale, off_ex [C, B], off_in [C, B] or None, listed [B, L] or None): the
+        per-session offsets under which logsumexp_c(z_c[b,v] + off_c[b]) is the score forward() returns (target_rank)"""
+        srs = self.session_repr(mg)
+        if not isinstance(srs, (list, tuple)):
+            srs = [srs]
+        st = self._state(srs[0].shape[0])
+        cs, inv_scale = self._col_scale(st)
+        la = torch.log_softmax(self.alpha, 0) if len(srs) > 1 else srs[0].new_zeros(1)
+        listed = None
+        if self.extra:
+            posc, valid, items, _ = self._in_session(mg)
+            listed = torch.where(valid, items, torch.full_like(items, -1)).to(torch.int32)
+        off_ex, off_in = [], []
+        for c, sr in enumerate(srs):
+            lse = self._lse(sr, cs, inv_scale, st, labels)
             if self.extra:
-                posc, valid, items, _ = self._in_session(mg)
-                listed = torch.where(valid, items, torch.full_like(items, -1)).to(torch.int32)
-            off_ex, off_in = [], []
-            for c, sr in enumerate(srs):
-                if self.shard is not None:
-                    lse, _ = self.shard.stats(sr, self._table(), cs, labels, inv_scale)
-                else:
-                    lse, _ = ops.score_stats(sr, self._table(), cs, lab32, st['ws'][B], st['tgrad'], None, inv_scale, None)
-                if self.extra:
-                    zin = 12.0 * (self._s1_feat[posc] * sr[:, None, :]).sum(-1)
-                    lse_in = torch.logsumexp(zin.masked_fill(~valid, float('-inf')), dim=1)
-                    lse_ex = lse + torch.log1p(-torch.exp(lse_in - lse).clamp(max=1.0 - 1e-7))
-                    lphi = self._log_phi(sr, None)
-                    off_in.append(la[c] + lphi[:, 0] - lse_in)
-                    off_ex.append(la[c] + lphi[:, 1] - lse_ex)
-                else:
-                    off_ex.append(la[c] - lse)
-            return self._rank_of(srs, cs, labels, torch.stack(off_ex, 0), torch.stack(off_in, 0) if self.extra else None,
-                                 listed)
+                zin = 12.0 * (self._s1_feat[posc] * sr[:, None, :]).sum(-1)
+                lse_in = torch.logsumexp(zin.masked_fill(~valid, float('-inf')), dim=1)
+                lse_ex = lse + torch.log1p(-torch.exp(lse_in - lse).clamp(max=1.0 - 1e-7))
+                lphi = self._log_phi(sr, None)
+                off_in.append(la[c] + lphi[:, 0] - lse_in)
+                off_ex.append(la[c] + lphi[:, 1] - lse_ex)
+            else:
+                off_ex.append(la[c] - lse)
+        return srs, cs, torch.stack(off_ex, 0), torch.stack(off_in, 0) if self.extra else None, listed
+
+    def _recommend(self, *inputs, k, exclude_seen):
+        """the mixture of target_rank: forward()'s log scores WITHOUT its (B, V) matrices (one per order, plus the
+        in-session mask).  With `extra` the session's own items are `listed` and score through the repeat branch (off_in);
+        exclude_seen drops them instead, so only the explore branch (off_ex) matters."""
+        if not (self.extra or (self.fusion and self.order > 1)):
+            return super()._recommend(*inputs, k=k, exclude_seen=exclude_seen)
+        (mg,) = inputs
+        srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg)
+        if self.extra or exclude_seen:
+            # (the tight [B, L] view: _in_session's is as wide as the longest read-out over all orders)
+            listed = self._session_items(mg)
+        if exclude_seen:
+            off_in = None
+        return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen)
 
     def forward(self, mg):
         sr = self.session_repr(mg)

@@ -1723,6 +1723,66 @@ def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id
     return rank, target
 
 
+_SELECT_WS = {}
+
+
+def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0):
+    """(values fp32 [B,k] descending, item ids int32 [B,k]): the k best rows of `table` per session under the score of
+    score_rank, s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) - no (B, V) tensor, k <= 128 (csrc/recommend.hip).
+    Argument conventions as score_rank: srs [B, d], [C, B, d] or a list of C [B, d] tensors, C <= 4; off_ex / off_in [C, B]
+    or None (= 0); listed [B, L] global item ids, -1 = empty slot; id_lo: global id of table row 0 (a row shard).
+    drop_listed=False: listed items score with off_in; True: listed items are never returned (off_in is ignored).  Ties go
+    towards the lower id; a session with fewer than k eligible rows ends in (-inf, -1) slots."""
+    k = int(k)
+    if k < 1 or k > CONST['SREC_SELECT_MAXK']:
+        raise ValueError('score_select: k = %d; the selection kernel of csrc/recommend.hip keeps between 1 and %d items per '
+                         'session' % (k, CONST['SREC_SELECT_MAXK']))
+    if listed is not None and listed.numel() > 0 and listed.reshape(listed.shape[0], -1).shape[1] > 64:
+        raise ValueError('score_select: %d listed items per session; csrc/recommend.hip takes at most 64'
+                         % listed.reshape(listed.shape[0], -1).shape[1])
+    if isinstance(srs, (list, tuple)):
+        srs = srs[0] if len(srs) == 1 else torch.stack([s.detach() for s in srs], 0)
+    srs = srs.detach()
+    if srs.dim() == 3 and srs.shape[0] == 1:
+        srs = srs[0]
+    if srs.dim() == 2:
+        srs = _rows(srs)
+        C, (B, d) = 1, srs.shape
+        ld_sr, comp = _ld(srs), 0
+    else:
+        assert srs.dim() == 3 and srs.dtype == torch.float32, (srs.shape, srs.dtype)
+        srs = srs.contiguous()
+        C, B, d = srs.shape
+        ld_sr, comp = d, B * d
+    table = _rows(table.detach())
+    V = table.shape[0]
+    dev = srs.device
+    val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(B, k, device=dev, dtype=torch.int32)
+    if B == 0:
+        return val, idx
+
+    def offs(o):
+        return None if o is None else o.detach().to(torch.float32).reshape(C, B).contiguous()
+    off_ex, off_in = offs(off_ex), (None if drop_listed else offs(off_in))
+    L = 0
+    if listed is not None and listed.numel() > 0:
+        listed = listed.detach().to(torch.int32).reshape(B, -1).contiguous()
+        L = listed.shape[1]
+    else:
+        listed = None
+    n = _ct.c_long()
+    lib.srec_score_select_ws(B, V, d, C, L, k, _ct.addressof(n))
+    key = (dev.index, n.value)
+    ws = _SELECT_WS.get(key)
+    if ws is None:
+        ws = _SELECT_WS[key] = torch.empty(n.value, device=dev, dtype=torch.uint8)
+    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
+    lib.srec_score_select(ptr(srs), ld_sr, comp, ptr(table), table.stride(0), ptr(cs), ptr(off_ex), ptr(off_in), ptr(listed), L,
+                          mode, int(id_lo), B, V, d, C, k, ptr(val), ptr(idx), ptr(ws), stream())
+    return val, idx
+
+
 class ScoreLogProb(torch.autograd.Function):
     """(B,V) log-probabilities - the tensor the reference models' forward() returns (compat /
     evaluation path).  Backward materialises d z (B,V) and runs two MFMA GEMMs."""

@@ -220,6 +220,56 @@ class _ScoringMixin:
             rank = torch.where(labels >= 0, rank.clamp(min=0), rank)
         return rank
 
+    def recommend(self, *inputs, k=20, exclude_seen=False):
+        """(log_probs fp32 [B,k] descending, item_ids int32 [B,k]): the k most probable next items of every session, k <= 128.
+        The values are the numbers forward() returns at those items (log-probabilities); ties go towards the lower item
+        id.  One fused selection pass over the table (csrc/recommend.hip): no (B, V) score matrix, sharded table included.
+        exclude_seen=True never returns an item of the session itself (at most 64 distinct items per session); the remaining
+        items keep forward()'s log-probabilities - there is NO renormalisation over the remaining items.  A session with
+        fewer than k eligible items ends in (-inf, -1) slots.  Runs in eval mode under torch.no_grad()."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                return self._recommend(*inputs, k=k, exclude_seen=exclude_seen)
+        finally:
+            self.train(was_training)
+
+    def _recommend(self, *inputs, k, exclude_seen):
+        sr = self.session_repr(*inputs)
+        st = self._state(sr.shape[0])
+        cs, inv_scale = self._col_scale(st)
+        off_ex = -self._lse(sr, cs, inv_scale, st).unsqueeze(0)      # log softmax = z - lse
+        listed = self._session_items(inputs[0]) if exclude_seen else None
+        return self._select_of([sr], cs, k, off_ex, None, listed, exclude_seen)
+
+    def _lse(self, sr, cs, inv_scale, st, labels=None):
+        """log-sum-exp of every session's logits over the whole catalog: the fused statistics pass (no gradient kept)"""
+        B = sr.shape[0]
+        if labels is None:
+            labels = torch.zeros(B, dtype=torch.int64, device=sr.device)
+        if self.shard is not None:
+            return self.shard.stats(sr, self._table(), cs, labels, inv_scale)[0]
+        return ops.score_stats(sr, self._table(), cs, labels.to(torch.int32), st['ws'][B], st['tgrad'], None, inv_scale, None)[0]
+
+    @staticmethod
+    def _session_items(mg):
+        """dense int32 [B, L] view of every session's distinct items (-1 = empty slot), from the batch's segment offsets
+        and item ids (the order-1 nodes of a k-gram batch); L = the longest session of the batch"""
+        ccs = mg.meta.get('kind') == 'ccs'
+        seg = mg.field('seg1' if ccs else 'seg').long()[:mg.B + 1]
+        iid = mg.field('iid1' if ccs else 'iid').long()
+        L = max(1, int((seg[1:] - seg[:-1]).max())) if seg.numel() > 1 else 1
+        pos = seg[:-1, None] + torch.arange(L, device=seg.device)[None, :]
+        items = iid[pos.clamp(max=iid.numel() - 1)]
+        return torch.where(pos < seg[1:, None], items, torch.full_like(items, -1)).to(torch.int32)
+
+    def _select_of(self, srs, cs, k, off_ex, off_in, listed, drop_listed):
+        if self.shard is not None:       # every shard selects among its rows: one all-gather of [B, k] pairs, one merge
+            return self.shard.select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed,
+                                     data_parallel=self.shard.eval_data_parallel)
+        return ops.score_select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed)
+
     def _log_probs(self, sr):
         B = sr.shape[0]
         st = self._state(B)

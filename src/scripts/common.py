@@ -32,13 +32,53 @@ def eval_options(args):
     return dict(eval_method=args.eval_method, eval_cutoffs=args.eval_cutoffs)
 
 
-def parse(model):
+def model_flags(p, model):
+    """the flags every model is built from (shared with scripts/recommend.py)"""
     d = DEFAULTS[model]
-    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--dataset-dir', default='../datasets/sample', help='the dataset directory')
     p.add_argument('--embedding-dim', type=int, default=d['embedding_dim'], help='the embedding size')
     p.add_argument('--num-layers', type=int, default=d['num_layers'], help='the number of layers')
     p.add_argument('--feat-drop', type=float, default=d['feat_drop'], help='the dropout ratio for features')
+
+
+def variant_flags(p, model):
+    """... and the ones only MSGIFSR has"""
+    if model == 'MSGIFSR':
+        p.add_argument('--order', type=int, default=3, help='order of msg')
+        p.add_argument('--reducer', type=str, default='mean', help='method for reducer')
+        p.add_argument('--norm', type=bool, default=True, help='whether use l2 norm')
+        p.add_argument('--extra', action='store_true', help='whether use REnorm.')
+        p.add_argument('--fusion', action='store_true', help='whether use IFR.')
+
+
+def build_model(model_name, args, num_items, device, caps=None):
+    """(model on the CPU, evaluation collate_fn, training collate_fn) of a launcher's flags (run, scripts/recommend.py)"""
+    from src.models import LESSR, MSGIFSR, NISER, SRGNN
+    from src.utils.data.collate import (collate_fn_factory, collate_fn_factory_ccs, seq_to_ccs_graph,
+                                        seq_to_eop_multigraph, seq_to_session_graph, seq_to_shortcut_graph)
+    if model_name == 'LESSR':
+        fns = (seq_to_eop_multigraph, seq_to_shortcut_graph) if args.num_layers > 1 else (seq_to_eop_multigraph,)
+        collate_fn = collate_fn_factory(*fns)
+        train_collate_fn = collate_fn_factory(*fns, caps=caps)
+        model = LESSR(num_items, args.embedding_dim, args.num_layers, feat_drop=args.feat_drop)
+    elif model_name == 'MSGIFSR':
+        collate_fn = collate_fn_factory_ccs((seq_to_ccs_graph,), order=args.order)
+        train_collate_fn = collate_fn_factory_ccs((seq_to_ccs_graph,), order=args.order, caps=caps)
+        model = MSGIFSR(num_items, args.dataset_dir, args.embedding_dim, args.num_layers, dropout=args.feat_drop,
+                        reducer=args.reducer, order=args.order, norm=args.norm, extra=args.extra, fusion=args.fusion,
+                        device=device)
+    else:
+        collate_fn = collate_fn_factory(seq_to_session_graph)
+        train_collate_fn = collate_fn_factory(seq_to_session_graph, caps=caps)
+        cls = NISER if model_name == 'NISER' else SRGNN
+        model = cls(num_items, args.embedding_dim, args.num_layers, feat_drop=args.feat_drop)
+    return model, collate_fn, train_collate_fn
+
+
+def parse(model):
+    d = DEFAULTS[model]
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    model_flags(p, model)
     p.add_argument('--lr', type=float, default=1e-3, help='the learning rate')
     p.add_argument('--batch-size', type=int, default=d['batch_size'], help='the batch size for training')
     p.add_argument('--epochs', type=int, default=30, help='the number of training epochs')
@@ -69,12 +109,7 @@ def parse(model):
                         '--fusion either (with --extra: sessions of at most 64 distinct items)')
     p.add_argument('--eval-cutoffs', type=_cutoffs, default=None, metavar='K1,K2,...',
                    help='(not in the reference) also report HR / MRR / NDCG at these cutoffs after every epoch, e.g. 5,10,20')
-    if model == 'MSGIFSR':
-        p.add_argument('--order', type=int, default=3, help='order of msg')
-        p.add_argument('--reducer', type=str, default='mean', help='method for reducer')
-        p.add_argument('--norm', type=bool, default=True, help='whether use l2 norm')
-        p.add_argument('--extra', action='store_true', help='whether use REnorm.')
-        p.add_argument('--fusion', action='store_true', help='whether use IFR.')
+    variant_flags(p, model)
     args = p.parse_args()
     if args.eval_method == 'topk' and args.eval_cutoffs and max(args.eval_cutoffs) > 32:
         p.error('--eval-cutoffs above 32 need --eval-method rank (the top-K evaluation keeps at most 32 items per session)')
@@ -125,9 +160,6 @@ def run(model_name):
     seed_all(123)
     import torch as th
     from torch.utils.data import DataLoader, SequentialSampler
-    from src.models import LESSR, MSGIFSR, NISER, SRGNN
-    from src.utils.data.collate import (collate_fn_factory, collate_fn_factory_ccs, seq_to_ccs_graph,
-                                        seq_to_eop_multigraph, seq_to_session_graph, seq_to_shortcut_graph)
     from src.utils.data.dataset import AugmentedDataset, read_dataset
     from src.utils.train import TrainRunner
 
@@ -179,22 +211,7 @@ def run(model_name):
                                 getattr(args, 'order', 1), shuffled=shuffled)
     print(len(train_set))
     print(len(test_set))
-    if model_name == 'LESSR':
-        fns = (seq_to_eop_multigraph, seq_to_shortcut_graph) if args.num_layers > 1 else (seq_to_eop_multigraph,)
-        collate_fn = collate_fn_factory(*fns)
-        train_collate_fn = collate_fn_factory(*fns, caps=caps)
-        model = LESSR(num_items, args.embedding_dim, args.num_layers, feat_drop=args.feat_drop)
-    elif model_name == 'MSGIFSR':
-        collate_fn = collate_fn_factory_ccs((seq_to_ccs_graph,), order=args.order)
-        train_collate_fn = collate_fn_factory_ccs((seq_to_ccs_graph,), order=args.order, caps=caps)
-        model = MSGIFSR(num_items, args.dataset_dir, args.embedding_dim, args.num_layers, dropout=args.feat_drop,
-                        reducer=args.reducer, order=args.order, norm=args.norm, extra=args.extra, fusion=args.fusion,
-                        device=device)
-    else:
-        collate_fn = collate_fn_factory(seq_to_session_graph)
-        train_collate_fn = collate_fn_factory(seq_to_session_graph, caps=caps)
-        cls = NISER if model_name == 'NISER' else SRGNN
-        model = cls(num_items, args.embedding_dim, args.num_layers, feat_drop=args.feat_drop)
+    model, collate_fn, train_collate_fn = build_model(model_name, args, num_items, device, caps)
     pin = device.type == 'cuda'          # pinned batches: asynchronous H2D copies
 
     def ring(batch_sampler):

@@ -1,0 +1,120 @@
+"""(not in the reference) top-N recommendations of a trained model for a file of sessions:
+
+    python scripts/recommend.py --model SRGNN --checkpoint run.pt --sessions sessions.txt --top 50 --exclude-seen
+
+--checkpoint is what `--checkpoint` of the training launchers writes (TrainRunner: its `model` entry is read); the model
+flags must be those of the training run.  --sessions holds one session per line in the format of datasets/*/test.txt
+(item ids separated by commas); the WHOLE line is the prefix whose next item is wanted.  Output: one line per input
+session, in input order - `id:logprob` pairs separated by tabs, best first (model.recommend: one fused selection pass over
+the item table, no (B, V) score matrix)."""
+import argparse
+import sys
+
+from common import DEFAULTS, build_model, model_flags, variant_flags
+
+MAX_TOP = 128           # SREC_SELECT_MAXK (include/srec.h)
+
+
+def read_session_file(path):
+    """[[item id, ...], ...]: one session per non-empty line, ids separated by commas (datasets/*/test.txt)"""
+    out = []
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if line:
+                out.append([int(x) for x in line.split(',')])
+    return out
+
+
+def format_sessions(sessions):
+    """the text read_session_file reads back"""
+    return ''.join(','.join(str(i) for i in s) + '\n' for s in sessions)
+
+
+def format_line(ids, vals):
+    """`id:logprob` pairs separated by tabs; unfilled slots (id -1: fewer eligible items than --top) are left out"""
+    return '\t'.join('%d:%.7f' % (i, v) for i, v in zip(ids, vals) if i >= 0)
+
+
+def parse_line(line):
+    """-> ([ids], [log-probabilities]) of one output line"""
+    pairs = [p.split(':') for p in line.rstrip('\n').split('\t') if p]
+    return [int(i) for i, _ in pairs], [float(v) for _, v in pairs]
+
+
+def session_capacity(limits, order=1, listed=False):
+    """the longest session (in clicks) that fits the per-session kernels whatever it holds: at most limits['nodes'] read-out
+    nodes (all n-gram orders together: <= order * clicks), node degrees <= limits['deg'] (<= clicks), and - where the
+    session's own items travel as a list (--exclude-seen, --extra) - at most 64 distinct items"""
+    cap = min(limits['nodes'] // max(order, 1), limits['deg'])
+    return min(cap, 64) if listed else cap
+
+
+def parser(model):
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter, description=__doc__.split('\n\n')[0])
+    p.add_argument('--model', default=model, choices=sorted(DEFAULTS), help='the model class of the checkpoint')
+    model_flags(p, model)
+    variant_flags(p, model)
+    p.add_argument('--checkpoint', required=True, help='a checkpoint of the training launchers (its `model` entry is read)')
+    p.add_argument('--sessions', required=True, help='one session per line, item ids separated by commas')
+    p.add_argument('--top', type=int, default=20, help='items per session (at most %d)' % MAX_TOP)
+    p.add_argument('--exclude-seen', action='store_true', help="never recommend an item of the session itself")
+    p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
+    p.add_argument('--output', default=None, help='write here instead of the standard output')
+    p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
+    return p
+
+
+def parse(argv=None):
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument('--model', default='SRGNN', choices=sorted(DEFAULTS))
+    model = pre.parse_known_args(argv)[0].model
+    p = parser(model)
+    args = p.parse_args(argv)
+    if not 1 <= args.top <= MAX_TOP:
+        p.error('--top must be between 1 and %d (the selection kernel keeps at most %d items per session)' % (MAX_TOP, MAX_TOP))
+    if args.batch_size < 1:
+        p.error('--batch-size must be positive')
+    return args
+
+
+def main(argv=None):
+    args = parse(argv)
+    import torch as th
+    from importlib import import_module
+    from pathlib import Path
+    if not th.cuda.is_available():
+        sys.exit('recommend.py needs a GPU: the models run on HIP kernels only')
+    device = th.device('cuda', th.cuda.current_device())
+    ops = import_module('sessionrec-pytorch_amd.ops')
+    ops.set_precision(args.precision)
+    with open(Path(args.dataset_dir) / 'num_items.txt') as f:
+        num_items = int(f.readline())
+    model, collate_fn, _ = build_model(args.model, args, num_items, device)
+    state = th.load(args.checkpoint, map_location='cpu', weights_only=True)
+    model.load_state_dict(state['model'])
+    model = model.to(device).eval()
+    ops.weights_changed()
+    model.table_written()
+
+    sessions = read_session_file(args.sessions)
+    cap = session_capacity(ops.limits(), getattr(args, 'order', 1), args.exclude_seen or getattr(args, 'extra', False))
+    cut = sum(len(s) > cap for s in sessions)
+    if cut:
+        print('warning: %d sessions are longer than %d clicks (the per-session capacity of the kernels) and were cut to '
+              'their last %d clicks' % (cut, cap, cap), file=sys.stderr)
+        sessions = [s[-cap:] for s in sessions]
+    out = open(args.output, 'w') if args.output else sys.stdout
+    try:
+        for b in range(0, len(sessions), args.batch_size):
+            inputs, _ = collate_fn([(s, 0) for s in sessions[b:b + args.batch_size]])
+            val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen)
+            for ids, vals in zip(idx.cpu().tolist(), val.cpu().tolist()):
+                out.write(format_line(ids, vals) + '\n')
+    finally:
+        if out is not sys.stdout:
+            out.close()
+
+
+if __name__ == '__main__':
+    main()
