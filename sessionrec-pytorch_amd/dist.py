@@ -374,59 +374,39 @@ class HipLocal:
         return pair[0], pair[1]
 
     def ce_bwd(self, sr, table, cs, labels_local, lse, gscale, dE, ws, cs_inv_scale, defer_tg=None):
-        from ._lib import lib, ptr, stream
         B, d = sr.shape
         dsr = torch.empty(B, d, device=sr.device, dtype=torch.float32)
         self.ops._ce_bwd(sr, table, cs, labels_local, lse, gscale, None, None, ws, None, self._tb(table, False), dE, dsr, 3)
-        if cs is not None and defer_tg is not None:
-            defer_tg.pending = (table, cs, cs_inv_scale)      # applied by the optimizer's row pass (ops.TableGrad)
-        elif cs is not None:
-            lib.srec_rownorm_project(ptr(table), table.stride(0), ptr(cs), cs_inv_scale, ptr(dE), dE.stride(0),
-                                     table.shape[0], d, stream())
+        self.ops.finish_table_grad(table, cs, cs_inv_scale, dE, defer_tg)
         return dsr
 
     def stats_bwd(self, sr, table, cs, labels_local, lse, ga, gc, dE, ws, cs_inv_scale, accumulate, defer_tg=None, gl=None):
         """d z[b, v] = ga[b] * softmax(z_b)[v] - gc[b] * [v == label_b] through this rank's rows: dE (+)= dz^T sr,
         returns the partial d sr = dz E_local"""
-        from ._lib import lib, ptr, stream
         B, d = sr.shape
         dsr = torch.empty(B, d, device=sr.device, dtype=torch.float32)
         if defer_tg is not None and not accumulate:
             defer_tg.overwritten()                     # stale pending / radial of a backward no optimizer step consumed
         self.ops._ce_bwd(sr, table, cs, labels_local, lse, gl, ga, gc, ws, None, self._tb(table, False), dE, dsr,
                          3 | (4 if accumulate else 0))
-        if cs is not None and defer_tg is not None:
-            defer_tg.pending = (table, cs, cs_inv_scale)      # linear: once, over the sum of the heads' contributions
-        elif cs is not None:
-            lib.srec_rownorm_project(ptr(table), table.stride(0), ptr(cs), cs_inv_scale, ptr(dE), dE.stride(0),
-                                     table.shape[0], d, stream())
+        self.ops.finish_table_grad(table, cs, cs_inv_scale, dE, defer_tg)
         return dsr
 
     def logp_cols(self, sr, table, cs, lse):
         """this rank's columns of the (B, V) log-probabilities: z[b, v] - lse[b] for the local rows v (fp32)"""
-        from ._lib import lib, ptr, stream
-        B, d = sr.shape
-        n = table.shape[0]
-        ld = (n + 3) & ~3
-        out = torch.empty(B, ld, device=sr.device, dtype=torch.float32)
         sr = sr.contiguous()
-        lib.srec_score_logp(ptr(sr), sr.stride(0), ptr(table), table.stride(0), ptr(cs), ptr(lse), B, n, d, None,
-                            ptr(out), ld, stream())
-        return out[:, :n]
+        return self.ops._logp_cols(sr, sr.stride(0), table, cs, lse)
 
     def topk(self, sr, table, cs, k):
-        from . import ops
-        return ops.score_topk(sr, table, cs, k)
+        return self.ops.score_topk(sr, table, cs, k)
 
     def rank(self, srs, table, cs, labels, off_ex, off_in, listed, id_lo, target=None, target_only=False):
         """this shard's share of (rank, target) of ops.score_rank: rows [id_lo, id_lo + n) of the catalog"""
-        from . import ops
-        return ops.score_rank(srs, table, cs, labels, off_ex, off_in, listed, id_lo, target, target_only)
+        return self.ops.score_rank(srs, table, cs, labels, off_ex, off_in, listed, id_lo, target, target_only)
 
     def select(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo):
         """this shard's k best rows (values, global ids) of ops.score_select: rows [id_lo, id_lo + n) of the catalog"""
-        from . import ops
-        return ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo)
+        return self.ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo)
 
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)

@@ -6,6 +6,12 @@ launched through libsrec_hip.so.  CPU tensors raise (no fallback).
 
 `dyn` arguments are optional 1-element int32 device tensors holding the live
 extent of a capacity-padded dimension (see batch.FlatBatch.dyn).
+
+Re-exported from the modules imported at the end of this file (ops.X stays the way to reach them):
+  hgat.py   the batched MSHGNN layer: HgPlan, HGATLayer, hgat_layer
+  score.py  full-catalog scoring: CEWorkspace, TableBF16, ScoreCE, ScoreStats, ScoreLogProb, score_ce, score_stats, score_logp,
+            score_topk, score_rank, score_select, use_bf16_scoring, sr16_written, sr16_claim, finish_table_grad, MixtureArgs,
+            _bf16_dim_ok, _prepare_sr, _ce_fwd, _ce_bwd, _mixture_args, _byte_ws, _logp_cols, _pad_rows
 """
 import ctypes as _ct
 import os
@@ -917,7 +923,7 @@ class Normalize(torch.autograd.Function):
             # ws: the scoring workspace this session vector is headed for - its bf16 operand copy is written here
             lib.srec_normalize_fwd_bf16(ptr(x), _ld(x), ptr(y), d, ptr(inv), n, ptr(dyn), d, eps_mode, 1e-12, ptr(sr16),
                                         sr16.shape[1], stream())
-            ws.sr_fresh = (y.data_ptr(), n, d)
+            sr16_written(ws, y, n, d)
         else:
             lib.srec_normalize_fwd(ptr(x), _ld(x), ptr(y), d, ptr(inv), n, ptr(dyn), d, eps_mode, 1e-12, stream())
         ctx.save_for_backward(y, inv)
@@ -1296,7 +1302,7 @@ class ReadoutHeadFused(torch.autograd.Function):
             ys.append(y)
         lib.srec_head_fwd(_ct.addressof(q), stream())
         if sr16 is not None:
-            ws.sr_fresh = (ys[0].data_ptr(), B, D)
+            sr16_written(ws, ys[0], B, D)
         ctx.save_for_backward(allf, seg, *keep)
         ctx.n, ctx.dT, ctx.dB = n, dT, dB
         ctx.has_bu = [po[2] is not None for po in per]
@@ -1426,417 +1432,6 @@ class SegMeanAdd(torch.autograd.Function):
 
 def seg_mean_add(H, F, seg, B, dynB=None):
     return SegMeanAdd.apply(H, F, seg, B, dynB)
-
-
-# ------------------------------------------------------------------------------------------ scoring
-def _bf16_dim_ok(d):
-    return d <= 256 and d % 4 == 0
-
-
-class CEWorkspace:
-    """Reusable scratch of the fused scoring/CE kernels for one (B, V, d) (sized for the fp32 and bf16 plans)."""
-
-    def __init__(self, B, V, d, device):
-        import ctypes
-        nt, nr, dp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        lib.srec_ce_plan(B, V, d, ctypes.addressof(nt), ctypes.addressof(nr))
-        nrange, nstat = nr.value, nt.value
-        if _bf16_dim_ok(d):
-            lib.srec_ce_plan_bf16(B, V, d, ctypes.addressof(nt), ctypes.addressof(nr), ctypes.addressof(dp))
-            nrange, nstat = max(nrange, nr.value), max(nstat, nt.value)
-        self.B, self.V, self.d = B, V, d
-        self.stats = torch.empty(2 * nstat * B, device=device, dtype=torch.float32)
-        self.dsr_part = torch.empty(nrange * B * d, device=device, dtype=torch.float32)
-        self.lab_logit = torch.zeros(B, device=device, dtype=torch.float32)
-        # bf16 operand copies of the session vectors (row-major + transposed), zero padded to 128 rows / d_pad columns
-        self.Bp = (B + 127) // 128 * 128
-        self.sr16 = self.srT16 = None
-        self.sr_key = None
-        self._de = {}
-        if _bf16_dim_ok(d):
-            self.sr16 = torch.zeros(self.Bp, dp.value, device=device, dtype=torch.bfloat16)
-
-
-def _ce_de_slabs(self, B, V, d):
-    """(split, workspace) of the session-split scoring backward at this shape (allocated by an eager step: a captured step
-    finds it in the cache)"""
-    ent = self._de.get((B, V))
-    if ent is None:
-        sp = _ct.c_int(1)
-        lib.srec_ce_de_split(B, V, d, _ct.addressof(sp))
-        split = int(sp.value)
-        if split > 1 and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('the scoring workspace must be sized by an eager warm-up step before graph capture')
-        buf = torch.empty(split * V * d, device=self.stats.device, dtype=torch.float32) if split > 1 else None
-        ent = self._de[(B, V)] = (split, buf)
-    return ent
-
-
-CEWorkspace.de_slabs = _ce_de_slabs
-
-
-class TableBF16:
-    """bf16 copy of the item table for the bf16 scoring kernels: E16 [Vp, d_pad] (row-major only: the backward takes its
-    transposed fragments with transposing LDS reads), refreshed once per step (one pass over the table)."""
-
-    def __init__(self, table):
-        import ctypes
-        V, d = table.shape
-        nt, nr, dp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        lib.srec_ce_plan_bf16(1, V, d, ctypes.addressof(nt), ctypes.addressof(nr), ctypes.addressof(dp))
-        self.Vp = (V + 127) // 128 * 128
-        self.E16 = torch.zeros(self.Vp, dp.value, device=table.device, dtype=torch.bfloat16)
-
-    def refresh(self, table, max_norm=0.0):
-        """one streaming pass: bf16 copy of every row; max_norm > 0: Embedding(max_norm)'s in-place renorm of the fp32 rows
-        in the same pass (msgifsr.py:162 / lessr.py:126)"""
-        V, d = table.shape
-        if d <= 1024:
-            with torch.no_grad():
-                lib.srec_renorm_rows_bf16(ptr(table), table.stride(0), V, d, float(max_norm), ptr(self.E16), self.E16.shape[1],
-                                          stream())
-        else:
-            assert max_norm <= 0
-            lib.srec_bf16_prepare(ptr(table), table.stride(0), V, None, d, ptr(self.E16), None, self.Vp, stream())
-        return self
-
-
-def use_bf16_scoring(d):
-    return PRECISION['matmul'] == 'bf16' and _bf16_dim_ok(d)
-
-
-def _prepare_sr(sr, ws, dynB):
-    """bf16 copies of the session vectors; skipped when the workspace still holds exactly this tensor (the backward
-    of the head whose forward ran last)."""
-    key = (sr.data_ptr(), sr._version, tuple(sr.shape))
-    if ws.sr_key != key:
-        B, d = sr.shape
-        lib.srec_bf16_prepare(ptr(sr), _ld(sr), B, ptr(dynB), d, ptr(ws.sr16), None, ws.Bp, stream())
-        ws.sr_key = key
-
-
-def _ce_fwd(sr, table, cs, labels, ws, dynB, tb, lab, lse, lossvec, loss):
-    B, d = sr.shape
-    V = table.shape[0]
-    if tb is not None:
-        if getattr(ws, 'sr_fresh', None) == (sr.data_ptr(), sr.shape[0], sr.shape[1]):
-            ws.sr_key = (sr.data_ptr(), sr._version, tuple(sr.shape))     # written by the normalisation that produced sr
-        else:
-            ws.sr_key = None
-            _prepare_sr(sr, ws, dynB)
-        ws.sr_fresh = None
-        lib.srec_score_ce_fwd_bf16(ptr(ws.sr16), ws.Bp, ptr(tb.E16), tb.Vp, ptr(cs), ptr(labels), B, V, d, ptr(dynB),
-                                   ptr(ws.stats), ptr(lab), ptr(lse), ptr(lossvec), ptr(loss), stream())
-    else:
-        lib.srec_score_ce_fwd(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), ptr(labels), B, V, d, ptr(dynB),
-                              ptr(ws.stats), ptr(lab), ptr(lse), ptr(lossvec), ptr(loss), stream())
-
-
-def _ce_bwd(sr, table, cs, labels, lse, gl, ga, gc, ws, dynB, tb, dE, dsr, parts):
-    B, d = sr.shape
-    V = table.shape[0]
-    if tb is not None:
-        _prepare_sr(sr, ws, dynB)
-        # many sessions against few table rows (a rank's shard scored for the sessions of ALL ranks): the item tiles of the
-        # backward are split over the sessions, slabs in a workspace the split decides the size of (srec_ce_de_split)
-        split, slabs = ws.de_slabs(B, V, d) if (parts & 1) and dE.stride(0) == d else (1, None)
-        lib.srec_score_ce_bwd_bf16(ptr(ws.sr16), ptr(slabs), ws.Bp, ptr(tb.E16), None, tb.Vp, ptr(cs),
-                                   ptr(labels), ptr(lse), ptr(gl), ptr(ga), ptr(gc), B, V, d, ptr(dynB), ptr(dE),
-                                   dE.stride(0), ptr(ws.dsr_part), ptr(dsr), parts | (split << 8), stream())
-    else:
-        lib.srec_score_ce_bwd(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), ptr(labels), ptr(lse), ptr(gl),
-                              ptr(ga), ptr(gc), B, V, d, ptr(dynB), ptr(dE), dE.stride(0), ptr(ws.dsr_part), ptr(dsr),
-                              parts, stream())
-
-
-class ScoreCE(torch.autograd.Function):
-    """loss = mean_b CE(cs * sr_b E^T, label_b), logits never materialised.  Writes the dense
-    table gradient into `tgrad.buf` (all rows) instead of returning it."""
-
-    @staticmethod
-    def forward(ctx, sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb=None):
-        sr = _rows(sr)
-        B, d = sr.shape
-        V = table.shape[0]
-        lse = torch.empty(B, device=sr.device, dtype=torch.float32)
-        lossvec = torch.empty(B, device=sr.device, dtype=torch.float32)
-        loss = torch.empty((), device=sr.device, dtype=torch.float32)
-        _ce_fwd(sr, table, cs, labels, ws, dynB, tb, ws.lab_logit, lse, lossvec, loss)
-        ctx.save_for_backward(sr, table, cs, labels, lse)
-        ctx.ws, ctx.tgrad, ctx.dynB, ctx.cs_inv_scale, ctx.tb = ws, tgrad, dynB, cs_inv_scale, tb
-        ctx.mark_non_differentiable(lse)
-        ctx.set_materialize_grads(False)       # no zero-filled [B] gradient for the unused lse output (a fill kernel per step)
-        return loss, lse
-
-    @staticmethod
-    def backward(ctx, gloss, _glse):
-        sr, table, cs, labels, lse = ctx.saved_tensors
-        B, d = sr.shape
-        V = table.shape[0]
-        tg, ws = ctx.tgrad, ctx.ws
-        gl = gloss.reshape(1).to(torch.float32).contiguous()
-        dsr = torch.empty(B, d, device=sr.device, dtype=torch.float32)
-        tg.overwritten()
-        _ce_bwd(sr, table, cs, labels, lse, gl, None, None, ws, ctx.dynB, ctx.tb, tg.buf, dsr, 3)
-        if cs is not None and tg.defer:
-            tg.pending = (table, cs, ctx.cs_inv_scale)     # applied by the optimizer's row pass (or TableGrad.materialize)
-        elif cs is not None:    # rows were L2-normalised before scoring: project out the radial part
-            lib.srec_rownorm_project(ptr(table), table.stride(0), ptr(cs), ctx.cs_inv_scale, ptr(tg.buf),
-                                     tg.buf.stride(0), V, d, stream())
-        tg.fresh = True
-        return dsr, None, None, None, None, None, None, None, None
-
-
-class ScoreStats(torch.autograd.Function):
-    """(lse_b, z[b,label_b]) of the full-catalog logits, logits never materialised; differentiable in both
-    outputs, so any loss built from them (mixtures of soft-maxes: msgifsr.py:311-317) trains through the
-    fused kernels.  Several heads may share one table: the first backward of a step overwrites the dense
-    table gradient, later ones accumulate."""
-
-    @staticmethod
-    def forward(ctx, sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb=None):
-        sr = _rows(sr)
-        B, d = sr.shape
-        V = table.shape[0]
-        dev = sr.device
-        lse = torch.empty(B, device=dev, dtype=torch.float32)
-        lossvec = torch.empty(B, device=dev, dtype=torch.float32)
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        lab = torch.zeros(B, device=dev, dtype=torch.float32)
-        _ce_fwd(sr, table, cs, labels, ws, dynB, tb, lab, lse, lossvec, loss)
-        ctx.save_for_backward(sr, table, cs, labels, lse)
-        ctx.ws, ctx.tgrad, ctx.dynB, ctx.cs_inv_scale, ctx.tb = ws, tgrad, dynB, cs_inv_scale, tb
-        return lse, lab
-
-    @staticmethod
-    def backward(ctx, dlse, dlab):
-        sr, table, cs, labels, lse = ctx.saved_tensors
-        B, d = sr.shape
-        V = table.shape[0]
-        tg, ws = ctx.tgrad, ctx.ws
-        ga = dlse.contiguous().float()
-        gc = (-dlab).contiguous().float()
-        dsr = torch.empty(B, d, device=sr.device, dtype=torch.float32)
-        parts = 3 | (4 if tg.fresh else 0)
-        if not tg.fresh:
-            tg.overwritten()
-        _ce_bwd(sr, table, cs, labels, lse, None, ga, gc, ws, ctx.dynB, ctx.tb, tg.buf, dsr, parts)
-        if cs is not None and tg.defer:
-            tg.pending = (table, cs, ctx.cs_inv_scale)     # linear: once, over the sum of the heads' contributions
-        elif cs is not None:    # projection is linear and idempotent: safe after every accumulation
-            lib.srec_rownorm_project(ptr(table), table.stride(0), ptr(cs), ctx.cs_inv_scale, ptr(tg.buf),
-                                     tg.buf.stride(0), V, d, stream())
-        tg.fresh = True
-        return dsr, None, None, None, None, None, None, None, None
-
-
-def score_stats(sr, table, cs, labels, ws, tgrad, dynB=None, cs_inv_scale=1.0, tb=None):
-    return ScoreStats.apply(sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb)
-
-
-def score_ce(sr, table, cs, labels, ws, tgrad, dynB=None, cs_inv_scale=1.0, tb=None):
-    return ScoreCE.apply(sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb)
-
-
-_TOPK_WS = {}
-
-
-def score_topk(sr, table, cs, k):
-    """(values [B,k], item ids [B,k]) of the k largest z[b,v] = cs[v] <sr_b, E_v> - no (B, V) tensor (evaluation)"""
-    sr = _rows(sr.detach())
-    B, d = sr.shape
-    V = table.shape[0]
-    n = _ct.c_long()
-    lib.srec_score_topk_ws(B, V, k, _ct.addressof(n))
-    key = (sr.device.index, n.value)
-    ws = _TOPK_WS.get(key)
-    if ws is None:
-        ws = _TOPK_WS[key] = torch.empty(n.value, device=sr.device, dtype=torch.uint8)
-    val = torch.empty(B, k, device=sr.device, dtype=torch.float32)
-    idx = torch.empty(B, k, device=sr.device, dtype=torch.int32)
-    lib.srec_score_topk(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), B, V, d, k, ptr(val), ptr(idx), ptr(ws),
-                        stream())
-    return val, idx
-
-
-_RANK_WS = {}
-
-
-def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id_lo=0, target=None, target_only=False):
-    """(rank int32 [B], target fp32 [B]): the number of rows of `table` that score ahead of each session's label under
-    s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) (off_in for the items of listed[b,:], off_ex elsewhere; ties
-    towards the lower item id) - no (B, V) tensor, no cutoff (csrc/rank.hip).  srs: [B, d], [C, B, d] or a list of C
-    [B, d] tensors, C <= 4; off_ex / off_in: [C, B] or None (= 0); listed: [B, L] item ids, -1 = empty slot; labels:
-    global item ids (< 0: rank -1); id_lo: global id of table row 0 (a row shard).  target: the labels' scores when they
-    are already known (the sharded case: summed over the shards) - else computed here, 0 for labels other shards own.
-    target_only: (None, target) from the target pass alone - a shard's share ahead of that sum."""
-    if isinstance(srs, (list, tuple)):
-        srs = srs[0] if len(srs) == 1 else torch.stack([s.detach() for s in srs], 0)
-    srs = srs.detach()
-    if srs.dim() == 3 and srs.shape[0] == 1:
-        srs = srs[0]
-    if srs.dim() == 2:
-        srs = _rows(srs)
-        C, (B, d) = 1, srs.shape
-        ld_sr, comp = _ld(srs), 0
-    else:
-        assert srs.dim() == 3 and srs.dtype == torch.float32, (srs.shape, srs.dtype)
-        srs = srs.contiguous()
-        C, B, d = srs.shape
-        ld_sr, comp = d, B * d
-    table = _rows(table.detach())
-    V = table.shape[0]
-    dev = srs.device
-    if B == 0:
-        return torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.float32)
-
-    def offs(o):
-        if o is None:
-            return None
-        o = o.detach().to(torch.float32).reshape(C, B).contiguous()
-        return o
-    off_ex, off_in = offs(off_ex), offs(off_in)
-    L = 0
-    if listed is not None and listed.numel() > 0:
-        listed = listed.detach().to(torch.int32).reshape(B, -1).contiguous()
-        L = listed.shape[1]
-        if L > 64:
-            raise ValueError('score_rank: %d listed items per session; the fix-up pass of csrc/rank.hip takes at most 64 '
-                             '(evaluate such sessions with method="topk")' % L)
-    else:
-        listed = None
-    labels = labels.detach().to(torch.int32).contiguous()
-    assert labels.numel() == B, (labels.shape, B)
-    # the C ABI carries a workspace (partial counts per range are one legal implementation); the current kernels meet in
-    # integer atomics and ask for a token size only - the call still validates the shape contract up front
-    n = _ct.c_long()
-    lib.srec_score_rank_ws(B, V, d, C, L, _ct.addressof(n))
-    key = (dev.index, n.value)
-    ws = _RANK_WS.get(key)
-    if ws is None:
-        ws = _RANK_WS[key] = torch.empty(n.value, device=dev, dtype=torch.uint8)
-    given = target is not None
-    target = target.detach().to(torch.float32).contiguous() if given else torch.empty(B, device=dev, dtype=torch.float32)
-    rank = None if target_only else torch.empty(B, device=dev, dtype=torch.int32)
-    lib.srec_score_rank(ptr(srs), ld_sr, comp, ptr(table), table.stride(0), ptr(cs), ptr(off_ex), ptr(off_in), ptr(listed), L,
-                        ptr(labels), int(id_lo), B, V, d, C, ptr(target), int(given), ptr(rank), ptr(ws), stream())
-    return rank, target
-
-
-_SELECT_WS = {}
-
-
-def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0):
-    """(values fp32 [B,k] descending, item ids int32 [B,k]): the k best rows of `table` per session under the score of
-    score_rank, s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) - no (B, V) tensor, k <= 128 (csrc/recommend.hip).
-    Argument conventions as score_rank: srs [B, d], [C, B, d] or a list of C [B, d] tensors, C <= 4; off_ex / off_in [C, B]
-    or None (= 0); listed [B, L] global item ids, -1 = empty slot; id_lo: global id of table row 0 (a row shard).
-    drop_listed=False: listed items score with off_in; True: listed items are never returned (off_in is ignored).  Ties go
-    towards the lower id; a session with fewer than k eligible rows ends in (-inf, -1) slots."""
-    k = int(k)
-    if k < 1 or k > CONST['SREC_SELECT_MAXK']:
-        raise ValueError('score_select: k = %d; the selection kernel of csrc/recommend.hip keeps between 1 and %d items per '
-                         'session' % (k, CONST['SREC_SELECT_MAXK']))
-    if listed is not None and listed.numel() > 0 and listed.reshape(listed.shape[0], -1).shape[1] > 64:
-        raise ValueError('score_select: %d listed items per session; csrc/recommend.hip takes at most 64'
-                         % listed.reshape(listed.shape[0], -1).shape[1])
-    if isinstance(srs, (list, tuple)):
-        srs = srs[0] if len(srs) == 1 else torch.stack([s.detach() for s in srs], 0)
-    srs = srs.detach()
-    if srs.dim() == 3 and srs.shape[0] == 1:
-        srs = srs[0]
-    if srs.dim() == 2:
-        srs = _rows(srs)
-        C, (B, d) = 1, srs.shape
-        ld_sr, comp = _ld(srs), 0
-    else:
-        assert srs.dim() == 3 and srs.dtype == torch.float32, (srs.shape, srs.dtype)
-        srs = srs.contiguous()
-        C, B, d = srs.shape
-        ld_sr, comp = d, B * d
-    table = _rows(table.detach())
-    V = table.shape[0]
-    dev = srs.device
-    val = torch.empty(B, k, device=dev, dtype=torch.float32)
-    idx = torch.empty(B, k, device=dev, dtype=torch.int32)
-    if B == 0:
-        return val, idx
-
-    def offs(o):
-        return None if o is None else o.detach().to(torch.float32).reshape(C, B).contiguous()
-    off_ex, off_in = offs(off_ex), (None if drop_listed else offs(off_in))
-    L = 0
-    if listed is not None and listed.numel() > 0:
-        listed = listed.detach().to(torch.int32).reshape(B, -1).contiguous()
-        L = listed.shape[1]
-    else:
-        listed = None
-    n = _ct.c_long()
-    lib.srec_score_select_ws(B, V, d, C, L, k, _ct.addressof(n))
-    key = (dev.index, n.value)
-    ws = _SELECT_WS.get(key)
-    if ws is None:
-        ws = _SELECT_WS[key] = torch.empty(n.value, device=dev, dtype=torch.uint8)
-    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
-    lib.srec_score_select(ptr(srs), ld_sr, comp, ptr(table), table.stride(0), ptr(cs), ptr(off_ex), ptr(off_in), ptr(listed), L,
-                          mode, int(id_lo), B, V, d, C, k, ptr(val), ptr(idx), ptr(ws), stream())
-    return val, idx
-
-
-class ScoreLogProb(torch.autograd.Function):
-    """(B,V) log-probabilities - the tensor the reference models' forward() returns (compat /
-    evaluation path).  Backward materialises d z (B,V) and runs two MFMA GEMMs."""
-
-    @staticmethod
-    def forward(ctx, sr, table, cs, ws, cs_inv_scale):
-        sr = _rows(sr)
-        B, d = sr.shape
-        V = table.shape[0]
-        dev = sr.device
-        lse = torch.empty(B, device=dev, dtype=torch.float32)
-        lossvec = torch.empty(B, device=dev, dtype=torch.float32)
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        zeros = torch.zeros(B, device=dev, dtype=torch.int32)
-        lib.srec_score_ce_fwd(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), ptr(zeros), B, V, d, None,
-                              ptr(ws.stats), ptr(ws.lab_logit), ptr(lse), ptr(lossvec), ptr(loss), stream())
-        ldp = (V + 3) & ~3
-        logp = torch.empty(B, ldp, device=dev, dtype=torch.float32)[:, :V]
-        lib.srec_score_logp(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), ptr(lse), B, V, d, None, ptr(logp),
-                            ldp, stream())
-        ctx.save_for_backward(sr, table, cs, logp)
-        ctx.cs_inv_scale = cs_inv_scale
-        return logp
-
-    @staticmethod
-    def backward(ctx, g):
-        sr, table, cs, logp = ctx.saved_tensors
-        dz = g - torch.exp(logp) * g.sum(dim=1, keepdim=True)
-        if cs is not None:
-            dz = dz * cs.unsqueeze(0)
-        V, d = table.shape
-        ldp = (V + 3) & ~3
-        dzp = torch.zeros(dz.shape[0], ldp, device=dz.device, dtype=torch.float32)
-        dzp[:, :V] = dz
-        tablep = table if ldp == V else _pad_rows(table, ldp)
-        dsr = torch.empty_like(sr)
-        gemm_nn(dzp, tablep, dsr)
-        dEp = torch.empty(ldp, d, device=dz.device, dtype=torch.float32)
-        gemm_tn(dzp, sr, dEp)
-        dE = dEp[:V]
-        if cs is not None:
-            lib.srec_rownorm_project(ptr(table), table.stride(0), ptr(cs), ctx.cs_inv_scale, ptr(dE), dE.stride(0), V,
-                                     d, stream())
-        return dsr, dE, None, None, None
-
-
-def _pad_rows(t, n):
-    out = torch.zeros(n, t.shape[1], device=t.device, dtype=t.dtype)
-    out[:t.shape[0]] = t
-    return out
-
-
-def score_logp(sr, table, cs, ws, cs_inv_scale=1.0):
-    return ScoreLogProb.apply(sr, table, cs, ws, cs_inv_scale)
 
 
 # ------------------------------------------------------------------------------------------ GRU
@@ -2741,3 +2336,7 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
 DROP_TAP = None      # tests: set to a list to receive {'ms': [2, NT, D], 'mk': [per instance (E*H,)]} of every dropout layer call
 
 from .hgat import HgPlan, HGATLayer, hgat_layer  # noqa: E402,F401  (the MSHGNN layer: hgat.py imports this module)
+from .score import (  # noqa: E402,F401  (full-catalog scoring: score.py imports this module)
+    CEWorkspace, MixtureArgs, ScoreCE, ScoreLogProb, ScoreStats, TableBF16, _bf16_dim_ok, _byte_ws, _ce_bwd, _ce_fwd, _logp_cols,
+    _mixture_args, _pad_rows, _prepare_sr, finish_table_grad, score_ce, score_logp, score_rank, score_select, score_stats,
+    score_topk, sr16_claim, sr16_written, use_bf16_scoring)

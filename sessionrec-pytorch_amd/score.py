@@ -1,0 +1,416 @@
+"""Full-catalog scoring (csrc/score_ce*.hip, rank.hip, recommend.hip): the fused CE / statistics nodes, top-K, target rank,
+top-N select and the (B, V) log-probabilities, with the workspaces and argument conventions they share.
+ops.py keeps the GEMM wrappers and the tests' switches (reached through the module object at call time) and re-exports this."""
+import ctypes as _ct
+from collections import namedtuple
+
+import torch
+
+from . import ops                    # (ops.py imports this module at its end: import the package or ops first, never score alone)
+from ._lib import CONST, lib, ptr, stream
+from .ops import _ld, _rows, gemm_nn, gemm_tn
+
+
+def _bf16_dim_ok(d):
+    return d <= 256 and d % 4 == 0
+
+
+class CEWorkspace:
+    """Reusable scratch of the fused scoring/CE kernels for one (B, V, d) (sized for the fp32 and bf16 plans).
+
+    sr16 (bf16 scoring only) is the bf16 operand copy of the session vectors the kernels read.  Two parties write it:
+      * the normalisation that PRODUCES the session vectors (ops.Normalize, ops.ReadoutHeadFused), in its own launch; it
+        then calls sr16_written(ws, y, n, d), which records sr_fresh = (data_ptr, rows, columns) of what it wrote;
+      * _prepare_sr, one conversion launch, which records sr_key = (data_ptr, version, shape) of what it converted.
+    _ce_fwd asks sr16_claim(ws, sr): when sr is exactly the tensor announced in sr_fresh it skips _prepare_sr and only
+    sets sr_key; otherwise it drops sr_key and converts.  Either way the claim clears sr_fresh, so an announcement serves
+    one forward.  _ce_bwd calls _prepare_sr, which is free while sr_key still names its sr (the backward of the head whose
+    forward ran last) and converts again when another forward has taken the buffer since."""
+
+    def __init__(self, B, V, d, device):
+        nt, nr, dp = _ct.c_int(), _ct.c_int(), _ct.c_int()
+        lib.srec_ce_plan(B, V, d, _ct.addressof(nt), _ct.addressof(nr))
+        nrange, nstat = nr.value, nt.value
+        if _bf16_dim_ok(d):
+            lib.srec_ce_plan_bf16(B, V, d, _ct.addressof(nt), _ct.addressof(nr), _ct.addressof(dp))
+            nrange, nstat = max(nrange, nr.value), max(nstat, nt.value)
+        self.B, self.V, self.d = B, V, d
+        self.stats = torch.empty(2 * nstat * B, device=device, dtype=torch.float32)
+        self.dsr_part = torch.empty(nrange * B * d, device=device, dtype=torch.float32)
+        self.lab_logit = torch.zeros(B, device=device, dtype=torch.float32)
+        # bf16 operand copies of the session vectors (row-major + transposed), zero padded to 128 rows / d_pad columns
+        self.Bp = (B + 127) // 128 * 128
+        self.sr16 = self.srT16 = None
+        self.sr_key = self.sr_fresh = None
+        self._de = {}
+        if _bf16_dim_ok(d):
+            self.sr16 = torch.zeros(self.Bp, dp.value, device=device, dtype=torch.bfloat16)
+
+    def de_slabs(self, B, V, d):
+        """(split, workspace) of the session-split scoring backward at this shape (allocated by an eager step: a captured step
+        finds it in the cache)"""
+        ent = self._de.get((B, V))
+        if ent is None:
+            sp = _ct.c_int(1)
+            lib.srec_ce_de_split(B, V, d, _ct.addressof(sp))
+            split = int(sp.value)
+            if split > 1 and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('the scoring workspace must be sized by an eager warm-up step before graph capture')
+            buf = torch.empty(split * V * d, device=self.stats.device, dtype=torch.float32) if split > 1 else None
+            ent = self._de[(B, V)] = (split, buf)
+        return ent
+
+
+def sr16_written(ws, y, n, d):
+    """the launch that produced the session vectors y [n, d] also wrote their bf16 copy into ws.sr16 (see CEWorkspace)"""
+    ws.sr_fresh = (y.data_ptr(), n, d)
+
+
+def sr16_claim(ws, sr):
+    """True when ws.sr16 was announced (sr16_written) as the copy of exactly sr; the announcement is spent either way"""
+    fresh = getattr(ws, 'sr_fresh', None) == (sr.data_ptr(), sr.shape[0], sr.shape[1])
+    ws.sr_fresh = None
+    return fresh
+
+
+class TableBF16:
+    """bf16 copy of the item table for the bf16 scoring kernels: E16 [Vp, d_pad] (row-major only: the backward takes its
+    transposed fragments with transposing LDS reads), refreshed once per step (one pass over the table)."""
+
+    def __init__(self, table):
+        V, d = table.shape
+        nt, nr, dp = _ct.c_int(), _ct.c_int(), _ct.c_int()
+        lib.srec_ce_plan_bf16(1, V, d, _ct.addressof(nt), _ct.addressof(nr), _ct.addressof(dp))
+        self.Vp = (V + 127) // 128 * 128
+        self.E16 = torch.zeros(self.Vp, dp.value, device=table.device, dtype=torch.bfloat16)
+
+    def refresh(self, table, max_norm=0.0):
+        """one streaming pass: bf16 copy of every row; max_norm > 0: Embedding(max_norm)'s in-place renorm of the fp32 rows
+        in the same pass (msgifsr.py:162 / lessr.py:126)"""
+        V, d = table.shape
+        if d <= 1024:
+            with torch.no_grad():
+                lib.srec_renorm_rows_bf16(ptr(table), table.stride(0), V, d, float(max_norm), ptr(self.E16), self.E16.shape[1],
+                                          stream())
+        else:
+            assert max_norm <= 0
+            lib.srec_bf16_prepare(ptr(table), table.stride(0), V, None, d, ptr(self.E16), None, self.Vp, stream())
+        return self
+
+
+def use_bf16_scoring(d):
+    return ops.PRECISION['matmul'] == 'bf16' and _bf16_dim_ok(d)
+
+
+def _prepare_sr(sr, ws, dynB):
+    """bf16 copies of the session vectors; skipped when the workspace still holds exactly this tensor (the backward
+    of the head whose forward ran last)."""
+    key = (sr.data_ptr(), sr._version, tuple(sr.shape))
+    if ws.sr_key != key:
+        B, d = sr.shape
+        lib.srec_bf16_prepare(ptr(sr), _ld(sr), B, ptr(dynB), d, ptr(ws.sr16), None, ws.Bp, stream())
+        ws.sr_key = key
+
+
+def _ce_fwd(sr, table, cs, labels, ws, dynB, tb, lab, lse, lossvec, loss):
+    B, d = sr.shape
+    V = table.shape[0]
+    if tb is not None:
+        if sr16_claim(ws, sr):
+            ws.sr_key = (sr.data_ptr(), sr._version, tuple(sr.shape))     # written by the normalisation that produced sr
+        else:
+            ws.sr_key = None
+            _prepare_sr(sr, ws, dynB)
+        lib.srec_score_ce_fwd_bf16(ptr(ws.sr16), ws.Bp, ptr(tb.E16), tb.Vp, ptr(cs), ptr(labels), B, V, d, ptr(dynB),
+                                   ptr(ws.stats), ptr(lab), ptr(lse), ptr(lossvec), ptr(loss), stream())
+    else:
+        lib.srec_score_ce_fwd(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), ptr(labels), B, V, d, ptr(dynB),
+                              ptr(ws.stats), ptr(lab), ptr(lse), ptr(lossvec), ptr(loss), stream())
+
+
+def _ce_bwd(sr, table, cs, labels, lse, gl, ga, gc, ws, dynB, tb, dE, dsr, parts):
+    B, d = sr.shape
+    V = table.shape[0]
+    if tb is not None:
+        _prepare_sr(sr, ws, dynB)
+        # many sessions against few table rows (a rank's shard scored for the sessions of ALL ranks): the item tiles of the
+        # backward are split over the sessions, slabs in a workspace the split decides the size of (srec_ce_de_split)
+        split, slabs = ws.de_slabs(B, V, d) if (parts & 1) and dE.stride(0) == d else (1, None)
+        lib.srec_score_ce_bwd_bf16(ptr(ws.sr16), ptr(slabs), ws.Bp, ptr(tb.E16), None, tb.Vp, ptr(cs),
+                                   ptr(labels), ptr(lse), ptr(gl), ptr(ga), ptr(gc), B, V, d, ptr(dynB), ptr(dE),
+                                   dE.stride(0), ptr(ws.dsr_part), ptr(dsr), parts | (split << 8), stream())
+    else:
+        lib.srec_score_ce_bwd(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), ptr(labels), ptr(lse), ptr(gl),
+                              ptr(ga), ptr(gc), B, V, d, ptr(dynB), ptr(dE), dE.stride(0), ptr(ws.dsr_part), ptr(dsr),
+                              parts, stream())
+
+
+def finish_table_grad(table, cs, cs_inv_scale, dE, tg):
+    """the chain rule of the row normalisation on a table gradient dE the scoring backward has just written (cs None: the
+    rows were scored as they are, nothing to do).  tg (an ops.TableGrad or None) with tg.defer: recorded in tg.pending and
+    applied by the optimizer's row pass or TableGrad.materialize - linear, so once over the sum of several heads'
+    contributions.  Otherwise projected out here, one row pass; the projection is idempotent, so safe after every
+    accumulation."""
+    if cs is None:
+        return
+    if tg is not None and tg.defer:
+        tg.pending = (table, cs, cs_inv_scale)
+    else:
+        lib.srec_rownorm_project(ptr(table), table.stride(0), ptr(cs), cs_inv_scale, ptr(dE), dE.stride(0), table.shape[0],
+                                 table.shape[1], stream())
+
+
+def _ce_outputs(B, device):
+    """(lse [B], lossvec [B], loss []) the forward kernels write"""
+    return (torch.empty(B, device=device, dtype=torch.float32), torch.empty(B, device=device, dtype=torch.float32),
+            torch.empty((), device=device, dtype=torch.float32))
+
+
+def _ce_backward(ctx, gl, ga, gc, accumulate):
+    """the backward both scoring nodes share: d sr returned, the dense table gradient overwritten in (or, accumulate, added to)
+    ctx.tgrad.buf.  gl: the upstream scalar; ga / gc: per-session coefficients of softmax / label one-hot (None = 1)"""
+    sr, table, cs, labels, lse = ctx.saved_tensors
+    tg = ctx.tgrad
+    dsr = torch.empty(sr.shape, device=sr.device, dtype=torch.float32)
+    if not accumulate:
+        tg.overwritten()
+    _ce_bwd(sr, table, cs, labels, lse, gl, ga, gc, ctx.ws, ctx.dynB, ctx.tb, tg.buf, dsr, 3 | (4 if accumulate else 0))
+    finish_table_grad(table, cs, ctx.cs_inv_scale, tg.buf, tg)
+    tg.fresh = True
+    return (dsr,) + (None,) * 8
+
+
+class ScoreCE(torch.autograd.Function):
+    """loss = mean_b CE(cs * sr_b E^T, label_b), logits never materialised.  Writes the dense
+    table gradient into `tgrad.buf` (all rows) instead of returning it."""
+
+    @staticmethod
+    def forward(ctx, sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb=None):
+        sr = _rows(sr)
+        lse, lossvec, loss = _ce_outputs(sr.shape[0], sr.device)
+        _ce_fwd(sr, table, cs, labels, ws, dynB, tb, ws.lab_logit, lse, lossvec, loss)
+        ctx.save_for_backward(sr, table, cs, labels, lse)
+        ctx.ws, ctx.tgrad, ctx.dynB, ctx.cs_inv_scale, ctx.tb = ws, tgrad, dynB, cs_inv_scale, tb
+        ctx.mark_non_differentiable(lse)
+        ctx.set_materialize_grads(False)       # no zero-filled [B] gradient for the unused lse output (a fill kernel per step)
+        return loss, lse
+
+    @staticmethod
+    def backward(ctx, gloss, _glse):
+        return _ce_backward(ctx, gloss.reshape(1).to(torch.float32).contiguous(), None, None, False)
+
+
+class ScoreStats(torch.autograd.Function):
+    """(lse_b, z[b,label_b]) of the full-catalog logits, logits never materialised; differentiable in both
+    outputs, so any loss built from them (mixtures of soft-maxes: msgifsr.py:311-317) trains through the
+    fused kernels.  Several heads may share one table: the first backward of a step overwrites the dense
+    table gradient, later ones accumulate."""
+
+    @staticmethod
+    def forward(ctx, sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb=None):
+        sr = _rows(sr)
+        B, dev = sr.shape[0], sr.device
+        lse, lossvec, loss = _ce_outputs(B, dev)
+        lab = torch.zeros(B, device=dev, dtype=torch.float32)
+        _ce_fwd(sr, table, cs, labels, ws, dynB, tb, lab, lse, lossvec, loss)
+        ctx.save_for_backward(sr, table, cs, labels, lse)
+        ctx.ws, ctx.tgrad, ctx.dynB, ctx.cs_inv_scale, ctx.tb = ws, tgrad, dynB, cs_inv_scale, tb
+        return lse, lab
+
+    @staticmethod
+    def backward(ctx, dlse, dlab):
+        return _ce_backward(ctx, None, dlse.contiguous().float(), (-dlab).contiguous().float(), ctx.tgrad.fresh)
+
+
+def score_stats(sr, table, cs, labels, ws, tgrad, dynB=None, cs_inv_scale=1.0, tb=None):
+    return ScoreStats.apply(sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb)
+
+
+def score_ce(sr, table, cs, labels, ws, tgrad, dynB=None, cs_inv_scale=1.0, tb=None):
+    return ScoreCE.apply(sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb)
+
+
+_BYTE_WS = {}
+
+
+def _byte_ws(kind, device, nbytes):
+    """never-resized byte scratch of the evaluation kernels, one per (kind, device, size): the kinds ('topk', 'rank',
+    'select') never share a buffer, so no two of their launches alias scratch that the separate caches kept apart"""
+    key = (kind, device.index, nbytes)
+    ws = _BYTE_WS.get(key)
+    if ws is None:
+        ws = _BYTE_WS[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return ws
+
+
+def score_topk(sr, table, cs, k):
+    """(values [B,k], item ids [B,k]) of the k largest z[b,v] = cs[v] <sr_b, E_v> - no (B, V) tensor (evaluation)"""
+    sr = _rows(sr.detach())
+    B, d = sr.shape
+    V = table.shape[0]
+    n = _ct.c_long()
+    lib.srec_score_topk_ws(B, V, k, _ct.addressof(n))
+    ws = _byte_ws('topk', sr.device, n.value)
+    val = torch.empty(B, k, device=sr.device, dtype=torch.float32)
+    idx = torch.empty(B, k, device=sr.device, dtype=torch.int32)
+    lib.srec_score_topk(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), B, V, d, k, ptr(val), ptr(idx), ptr(ws),
+                        stream())
+    return val, idx
+
+
+# what score_rank / score_select launch with: srs as (pointer, row stride, component stride), C components of [B, d];
+# table [V, d] as rows; off_ex / off_in fp32 [C, B] or None; listed int32 [B, L] or None with L = 0
+MixtureArgs = namedtuple('MixtureArgs', 'srs ld_sr comp C B d table V off_ex off_in listed L')
+_LISTED_MAX = 64
+_LISTED_TOO_MANY = {
+    'score_rank': 'score_rank: %d listed items per session; the fix-up pass of csrc/rank.hip takes at most 64 '
+                  '(evaluate such sessions with method="topk")',
+    'score_select': 'score_select: %d listed items per session; csrc/recommend.hip takes at most 64',
+}
+
+
+def _mixture_args(who, srs, table, off_ex, off_in, listed):
+    """The argument conventions score_rank and score_select share, as one MixtureArgs.  srs: [B, d] (row-strided views are
+    taken as they are), [C, B, d], [1, B, d] or a list of C [B, d] tensors; off_ex / off_in: anything of C * B numbers or
+    None; listed: [B, L] item ids, empty or None = no list.  More than 64 listed items per session raise ValueError in the
+    words of `who`.  Pure torch (no launch, no library call): it checks CPU tensors as well."""
+    if isinstance(srs, (list, tuple)):
+        srs = srs[0] if len(srs) == 1 else torch.stack([s.detach() for s in srs], 0)
+    srs = srs.detach()
+    if srs.dim() == 3 and srs.shape[0] == 1:
+        srs = srs[0]
+    if srs.dim() == 2:
+        srs = _rows(srs)
+        C, (B, d) = 1, srs.shape
+        ld_sr, comp = _ld(srs), 0
+    else:
+        assert srs.dim() == 3 and srs.dtype == torch.float32, (srs.shape, srs.dtype)
+        srs = srs.contiguous()
+        C, B, d = srs.shape
+        ld_sr, comp = d, B * d
+    table = _rows(table.detach())
+
+    def offs(o):
+        return None if o is None else o.detach().to(torch.float32).reshape(C, B).contiguous()
+    L = 0
+    if listed is not None and listed.numel() > 0:
+        listed = listed.detach().to(torch.int32).reshape(B, -1).contiguous()
+        L = listed.shape[1]
+        if L > _LISTED_MAX:
+            raise ValueError(_LISTED_TOO_MANY[who] % L)
+    else:
+        listed = None
+    return MixtureArgs(srs, ld_sr, comp, C, B, d, table, table.shape[0], offs(off_ex), offs(off_in), listed, L)
+
+
+def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id_lo=0, target=None, target_only=False):
+    """(rank int32 [B], target fp32 [B]): the number of rows of `table` that score ahead of each session's label under
+    s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) (off_in for the items of listed[b,:], off_ex elsewhere; ties
+    towards the lower item id) - no (B, V) tensor, no cutoff (csrc/rank.hip).  srs: [B, d], [C, B, d] or a list of C
+    [B, d] tensors, C <= 4; off_ex / off_in: [C, B] or None (= 0); listed: [B, L] item ids, -1 = empty slot; labels:
+    global item ids (< 0: rank -1); id_lo: global id of table row 0 (a row shard).  target: the labels' scores when they
+    are already known (the sharded case: summed over the shards) - else computed here, 0 for labels other shards own.
+    target_only: (None, target) from the target pass alone - a shard's share ahead of that sum."""
+    a = _mixture_args('score_rank', srs, table, off_ex, off_in, listed)
+    B, dev = a.B, a.srs.device
+    if B == 0:
+        return torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.float32)
+    labels = labels.detach().to(torch.int32).contiguous()
+    assert labels.numel() == B, (labels.shape, B)
+    # the C ABI carries a workspace (partial counts per range are one legal implementation); the current kernels meet in
+    # integer atomics and ask for a token size only - the call still validates the shape contract up front
+    n = _ct.c_long()
+    lib.srec_score_rank_ws(B, a.V, a.d, a.C, a.L, _ct.addressof(n))
+    ws = _byte_ws('rank', dev, n.value)
+    given = target is not None
+    target = target.detach().to(torch.float32).contiguous() if given else torch.empty(B, device=dev, dtype=torch.float32)
+    rank = None if target_only else torch.empty(B, device=dev, dtype=torch.int32)
+    lib.srec_score_rank(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
+                        ptr(a.listed), a.L, ptr(labels), int(id_lo), B, a.V, a.d, a.C, ptr(target), int(given), ptr(rank),
+                        ptr(ws), stream())
+    return rank, target
+
+
+def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0):
+    """(values fp32 [B,k] descending, item ids int32 [B,k]): the k best rows of `table` per session under the score of
+    score_rank, s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) - no (B, V) tensor, k <= 128 (csrc/recommend.hip).
+    Argument conventions as score_rank: srs [B, d], [C, B, d] or a list of C [B, d] tensors, C <= 4; off_ex / off_in [C, B]
+    or None (= 0); listed [B, L] global item ids, -1 = empty slot; id_lo: global id of table row 0 (a row shard).
+    drop_listed=False: listed items score with off_in; True: listed items are never returned (off_in is ignored).  Ties go
+    towards the lower id; a session with fewer than k eligible rows ends in (-inf, -1) slots."""
+    k = int(k)
+    if k < 1 or k > CONST['SREC_SELECT_MAXK']:
+        raise ValueError('score_select: k = %d; the selection kernel of csrc/recommend.hip keeps between 1 and %d items per '
+                         'session' % (k, CONST['SREC_SELECT_MAXK']))
+    a = _mixture_args('score_select', srs, table, off_ex, None if drop_listed else off_in, listed)
+    B, dev = a.B, a.srs.device
+    val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(B, k, device=dev, dtype=torch.int32)
+    if B == 0:
+        return val, idx
+    n = _ct.c_long()
+    lib.srec_score_select_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
+    ws = _byte_ws('select', dev, n.value)
+    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
+    lib.srec_score_select(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
+                          ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, k, ptr(val), ptr(idx), ptr(ws), stream())
+    return val, idx
+
+
+def _logp_cols(sr, ld_sr, table, cs, lse):
+    """[B, V] log-probabilities z[b, v] - lse[b] of the rows of `table` (fp32): a view of a buffer whose rows are padded to
+    a multiple of 4 columns"""
+    B, d = sr.shape
+    V = table.shape[0]
+    ldp = (V + 3) & ~3
+    out = torch.empty(B, ldp, device=sr.device, dtype=torch.float32)
+    lib.srec_score_logp(ptr(sr), ld_sr, ptr(table), table.stride(0), ptr(cs), ptr(lse), B, V, d, None, ptr(out), ldp, stream())
+    return out[:, :V]
+
+
+class ScoreLogProb(torch.autograd.Function):
+    """(B,V) log-probabilities - the tensor the reference models' forward() returns (compat /
+    evaluation path).  Backward materialises d z (B,V) and runs two MFMA GEMMs."""
+
+    @staticmethod
+    def forward(ctx, sr, table, cs, ws, cs_inv_scale):
+        sr = _rows(sr)
+        B, d = sr.shape
+        V = table.shape[0]
+        lse, lossvec, loss = _ce_outputs(B, sr.device)
+        zeros = torch.zeros(B, device=sr.device, dtype=torch.int32)
+        lib.srec_score_ce_fwd(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), ptr(zeros), B, V, d, None,
+                              ptr(ws.stats), ptr(ws.lab_logit), ptr(lse), ptr(lossvec), ptr(loss), stream())
+        logp = _logp_cols(sr, _ld(sr), table, cs, lse)
+        ctx.save_for_backward(sr, table, cs, logp)
+        ctx.cs_inv_scale = cs_inv_scale
+        return logp
+
+    @staticmethod
+    def backward(ctx, g):
+        sr, table, cs, logp = ctx.saved_tensors
+        dz = g - torch.exp(logp) * g.sum(dim=1, keepdim=True)
+        if cs is not None:
+            dz = dz * cs.unsqueeze(0)
+        V, d = table.shape
+        ldp = (V + 3) & ~3
+        dzp = torch.zeros(dz.shape[0], ldp, device=dz.device, dtype=torch.float32)
+        dzp[:, :V] = dz
+        tablep = table if ldp == V else _pad_rows(table, ldp)
+        dsr = torch.empty_like(sr)
+        gemm_nn(dzp, tablep, dsr)
+        dEp = torch.empty(ldp, d, device=dz.device, dtype=torch.float32)
+        gemm_tn(dzp, sr, dEp)
+        dE = dEp[:V]
+        finish_table_grad(table, cs, ctx.cs_inv_scale, dE, None)
+        return dsr, dE, None, None, None
+
+
+def _pad_rows(t, n):
+    out = torch.zeros(n, t.shape[1], device=t.device, dtype=t.dtype)
+    out[:t.shape[0]] = t
+    return out
+
+
+def score_logp(sr, table, cs, ws, cs_inv_scale=1.0):
+    return ScoreLogProb.apply(sr, table, cs, ws, cs_inv_scale)

@@ -343,3 +343,31 @@ def test_recommend_launcher_equals_in_process_recommend(dev, tmp_path):
         assert ids == idx[b].tolist(), b
         assert not set(ids) & set(sessions[b]), b
         assert max(abs(a - c) for a, c in zip(vals, val[b].tolist())) <= 1e-6, b
+
+
+# ------------------------------------------------------------------------------------------- workspace cache of the three users
+def test_topk_rank_select_interleaved_at_two_shapes_keep_their_own_scratch(dev):
+    """score_topk, score_rank and score_select draw their byte scratch from one cache keyed (kind, device, size): shape A,
+    shape B, then A again must repeat A's results bit for bit, and - random fp32 inputs, no ties - select must name the
+    items top-K names"""
+    ops = _ops()
+    g = torch.Generator().manual_seed(11)
+
+    def case(B, V, d):
+        return (torch.randn(B, d, generator=g).to(dev), torch.randn(V, d, generator=g).to(dev),
+                torch.randint(0, V, (B,), generator=g).to(dev))
+
+    def run(sr, E, labels):
+        tv, ti = ops.score_topk(sr, E, None, 5)
+        rank, target = ops.score_rank(sr, E, None, labels)
+        sv, si = ops.score_select(sr, E, None, 5)
+        assert torch.equal(si, ti), (si[0].tolist(), ti[0].tolist())
+        return tv, ti, rank, target, sv, si
+    a, b = case(3, 300, 32), case(130, 1000, 64)
+    first = run(*a)
+    run(*b)
+    again = run(*a)
+    for x, y in zip(first, again):
+        assert torch.equal(x, y)
+    kinds = sorted({k[0] for k in pkg('score')._BYTE_WS})
+    assert kinds == ['rank', 'select', 'topk'], kinds
