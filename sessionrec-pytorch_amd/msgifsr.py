@@ -336,12 +336,12 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         """the operand copies of this step's weights (k-gram GRUs, the first MSHGNN layer's fc weights and its folded attention
         vectors, the read-out head) and the batch intake of a captured step in ONE launch ahead of the lookup (ops.step_prologue,
         csrc/prep.hip) - 5 launches of 5 - 8 us each otherwise, one in front of each reader.  The conditions mirror the
-        readers'; a reader that finds no copies makes its own."""
+        readers' (the GRUs' is the readers' own, ops.expand_path); a reader that finds no copies makes its own."""
         K, d = self.order, self.embedding_dim
         bf16 = ops.PRECISION['matmul'] == 'bf16'
         grad = torch.is_grad_enabled() and self.training
         gru, w16, head, fold = [], [], [], None
-        if bf16 and 1 < K <= 5 and ops.gru_expand_fast_ok(d, self.reducer) and ops.gru_fused_ok(d, K - 1):
+        if ops.expand_path(d, self.reducer, K) == 'fused':
             gru = [w for k in range(2, K + 1) for w in (self.expander.GRUs[k - 2].weight_ih_l0, self.expander.GRUs[k - 2].weight_hh_l0)]
             if not all(w.is_contiguous() for w in gru):
                 gru = []
@@ -381,7 +381,7 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         ncap = mg.meta['ncap']                             # block size of order k (capacity in padded layouts)
         pieces = ops.split_rows(rows, [ncap[k] * k for k in range(1, K + 1)])
         fast = None
-        if K > 1 and K <= 5 and ops.gru_expand_fast_ok(d, self.reducer):
+        if ops.expand_path(d, self.reducer, K) is not None:
             # bf16 path: every order's k-gram GRU in one autograd node, one launch per time step for all orders
             fast = ops.gru_expand_all([pieces[k - 1] for k in range(2, K + 1)], [self.expander.GRUs[k - 2] for k in range(2, K + 1)],
                                       list(range(2, K + 1)), [mg.dynp('N%d' % k) for k in range(2, K + 1)],

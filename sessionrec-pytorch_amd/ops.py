@@ -9,6 +9,9 @@ extent of a capacity-padded dimension (see batch.FlatBatch.dyn).
 
 Re-exported from the modules imported at the end of this file (ops.X stays the way to reach them):
   hgat.py   the batched MSHGNN layer: HgPlan, HGATLayer, hgat_layer
+  gru.py    the GRU step and the k-gram GRU expander: GRUPointwise, GramCombine, GRUExpand, GRUExpandAll, gru_step, gram_combine,
+            gru_expand, gru_expand_all, gru_wfrag, gru_wfrag_both, gru_fused_ok, gru_expand_fast_ok, expand_path, GruOrder,
+            gru_step_desc, gru_fused_desc, gru_fused_bwd_desc, _gru_wfrag_args
   score.py  full-catalog scoring: CEWorkspace, TableBF16, ScoreCE, ScoreStats, ScoreLogProb, score_ce, score_stats, score_logp,
             score_topk, score_rank, score_select, use_bf16_scoring, sr16_written, sr16_claim, finish_table_grad, MixtureArgs,
             _bf16_dim_ok, _prepare_sr, _ce_fwd, _ce_bwd, _mixture_args, _byte_ws, _logp_cols, _pad_rows
@@ -1434,455 +1437,6 @@ def seg_mean_add(H, F, seg, B, dynB=None):
     return SegMeanAdd.apply(H, F, seg, B, dynB)
 
 
-# ------------------------------------------------------------------------------------------ GRU
-class GRUPointwise(torch.autograd.Function):
-    """One GRU time step given the two projections (GI, GH); GH=None <=> h_prev = 0 (gh = b_hh)."""
-
-    @staticmethod
-    def forward(ctx, GI, GH, bhh, Hp, dyn):
-        GI = _rows(GI)
-        n, d3 = GI.shape
-        d = d3 // 3
-        dev = GI.device
-        Hn = torch.empty(n, d, device=dev, dtype=torch.float32)
-        gates = torch.empty(n, d3, device=dev, dtype=torch.float32)
-        if GH is not None:
-            GH, Hp = _rows(GH), _rows(Hp)
-            lib.srec_gru_pointwise_fwd(ptr(GI), _ld(GI), ptr(GH), _ld(GH), None, ptr(Hp), _ld(Hp), n, ptr(dyn), d,
-                                       ptr(Hn), d, ptr(gates), stream())
-        else:
-            bhh = bhh.contiguous()
-            lib.srec_gru_pointwise_fwd(ptr(GI), _ld(GI), None, 0, ptr(bhh), None, 0, n, ptr(dyn), d, ptr(Hn), d,
-                                       ptr(gates), stream())
-        ctx.save_for_backward(gates, GH, bhh, Hp)
-        ctx.dyn = dyn
-        return Hn
-
-    @staticmethod
-    def backward(ctx, dHn):
-        gates, GH, bhh, Hp = ctx.saved_tensors
-        dHn = _rows(dHn)
-        n, d3 = gates.shape
-        d = d3 // 3
-        dev = gates.device
-        dGI = torch.empty(n, d3, device=dev, dtype=torch.float32)
-        dGH = torch.empty(n, d3, device=dev, dtype=torch.float32)
-        if GH is not None:
-            dHp = torch.empty(n, d, device=dev, dtype=torch.float32)
-            lib.srec_gru_pointwise_bwd(ptr(dHn), _ld(dHn), ptr(gates), ptr(GH), _ld(GH), None, ptr(Hp), _ld(Hp), n,
-                                       ptr(ctx.dyn), d, ptr(dGI), d3, ptr(dGH), d3, ptr(dHp), d, stream())
-            return dGI, dGH, None, dHp, None
-        lib.srec_gru_pointwise_bwd(ptr(dHn), _ld(dHn), ptr(gates), None, 0, ptr(bhh), None, 0, n, ptr(ctx.dyn), d,
-                                   ptr(dGI), d3, ptr(dGH), d3, None, 0, stream())
-        db = torch.empty(d3, device=dev, dtype=torch.float32)
-        col_sum(dGH, n, d3, db, ctx.dyn)
-        return dGI, None, db, None, None
-
-
-class UnbindMid(torch.autograd.Function):
-    """x [n, k, m] -> k row-strided views x[:, t, :]; the backward is ONE stack instead of autograd's k zero-fills,
-    k slice copies and k-1 adds (SelectBackward)."""
-
-    @staticmethod
-    def forward(ctx, x):
-        ctx.shape = x.shape
-        return tuple(x[:, t, :] for t in range(x.shape[1]))
-
-    @staticmethod
-    def backward(ctx, *gs):
-        n, k, m = ctx.shape
-        gs = [g if g is not None else torch.zeros(n, m, device=gs[0].device if gs[0] is not None else None) for g in gs]
-        return torch.stack(gs, 1)
-
-
-def unbind_mid(x):
-    return UnbindMid.apply(x)
-
-
-def gru_step(GI, GH, bhh, Hp, dyn=None):
-    return GRUPointwise.apply(GI, GH, bhh, Hp, dyn)
-
-
-class GramCombine(torch.autograd.Function):
-    """0.5 * mean_t x[n,t,:] + 0.5 * h_last[n,:]"""
-
-    @staticmethod
-    def forward(ctx, X, Hl, k, dyn):
-        X = X.contiguous()
-        Hl = _rows(Hl)
-        n, d = Hl.shape
-        out = torch.empty(n, d, device=Hl.device, dtype=torch.float32)
-        lib.srec_gram_combine_fwd(ptr(X), ptr(Hl), _ld(Hl), n, ptr(dyn), k, d, ptr(out), d, stream())
-        ctx.k, ctx.dyn, ctx.xshape = k, dyn, tuple(X.shape)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        g = _rows(g)
-        n, d = g.shape
-        dX = torch.empty(ctx.xshape, device=g.device, dtype=torch.float32)
-        dH = torch.empty(n, d, device=g.device, dtype=torch.float32)
-        lib.srec_gram_combine_bwd(ptr(g), _ld(g), n, ptr(ctx.dyn), ctx.k, d, ptr(dX), ptr(dH), d, stream())
-        return dX, dH, None, None
-
-
-class GRUExpand(torch.autograd.Function):
-    """MSGIFSR SemanticExpander for one order k (msgifsr.py:32-45): out = 0.5 * mean_t x[n,t,:] + 0.5 * GRU(x).h_last,
-    as ONE autograd node on stacked buffers: the time steps share [k, n, *] tensors, so the backward needs one
-    weight-gradient GEMM and one bias column-sum for W_hh / b_hh over all steps, the hidden-state gradient is
-    accumulated by the backward-data GEMM itself (beta = 1) and nothing goes through autograd's select / add kernels."""
-
-    @staticmethod
-    def forward(ctx, x, Wih, bih, Whh, bhh, k, dyn_n, dyn_rows, combine=True):
-        x = x.contiguous()
-        nk, d = x.shape
-        n, d3 = nk // k, 3 * d
-        dev = x.device
-        Wih, Whh, bhh = _rows(Wih), _rows(Whh), bhh.contiguous()
-        GI = torch.empty(nk, d3, device=dev, dtype=torch.float32)
-        gemm_nt(x, Wih, GI, bih, dyn_rows, 1 if dyn_rows is not None else 0)
-        H = torch.empty(k, n, d, device=dev, dtype=torch.float32)
-        gates = torch.empty(k, n, d3, device=dev, dtype=torch.float32)
-        GH = torch.empty(max(k - 1, 1), n, d3, device=dev, dtype=torch.float32)
-        st = stream()
-        for t in range(k):
-            gi = GI.data_ptr() + 4 * t * d3                                   # GI[:, t, :], row stride k * 3d
-            if t == 0:
-                lib.srec_gru_pointwise_fwd(gi, k * d3, None, 0, ptr(bhh), None, 0, n, ptr(dyn_n), d, ptr(H[0]), d,
-                                           ptr(gates[0]), st)
-            else:
-                gemm_nt(H[t - 1], Whh, GH[t - 1], bhh, dyn_n, 1 if dyn_n is not None else 0)
-                lib.srec_gru_pointwise_fwd(gi, k * d3, ptr(GH[t - 1]), d3, None, ptr(H[t - 1]), d, n, ptr(dyn_n), d,
-                                           ptr(H[t]), d, ptr(gates[t]), st)
-        ctx.save_for_backward(x, Wih, Whh, bhh, H, gates, GH)
-        ctx.k, ctx.dyn_n, ctx.dyn_rows, ctx.combine = k, dyn_n, dyn_rows, combine
-        if not combine:                                   # 'max' / 'concat' reducers: only the GRU's last hidden state
-            return H[k - 1].clone()
-        out = torch.empty(n, d, device=dev, dtype=torch.float32)
-        lib.srec_gram_combine_fwd(ptr(x), ptr(H[k - 1]), d, n, ptr(dyn_n), k, d, ptr(out), d, st)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, Wih, Whh, bhh, H, gates, GH = ctx.saved_tensors
-        k, dyn_n, dyn_rows = ctx.k, ctx.dyn_n, ctx.dyn_rows
-        g = _rows(g)
-        n, d = g.shape
-        d3, dev, st = 3 * d, g.device, stream()
-        if ctx.combine:
-            dX = torch.empty(n * k, d, device=dev, dtype=torch.float32)
-            dh = torch.empty(n, d, device=dev, dtype=torch.float32)
-            lib.srec_gram_combine_bwd(ptr(g), _ld(g), n, ptr(dyn_n), k, d, ptr(dX), ptr(dh), d, st)
-        else:
-            dX = torch.zeros(n * k, d, device=dev, dtype=torch.float32)
-            dh = g.contiguous()
-        # d(gi) and d(gh) side by side in ONE [n k, 2 d3] buffer: both bias gradients are then one column-sum launch.
-        # d(gi) rows are (node, t) = node k + t; d(gh) slot t = rows [t n, (t+1) n).  The gate kernel writes every row of
-        # both (zeros for nodes past the live count).
-        dG = torch.empty(n * k, 2 * d3, device=dev, dtype=torch.float32)
-        dGI = dG[:, :d3]
-        dGH = [dG[t * n:(t + 1) * n, d3:] for t in range(k)]
-        for t in range(k - 1, -1, -1):
-            dgi = dG.data_ptr() + 4 * t * 2 * d3
-            if t > 0:
-                dhp = torch.empty(n, d, device=dev, dtype=torch.float32)
-                lib.srec_gru_pointwise_bwd(ptr(dh), d, ptr(gates[t]), ptr(GH[t - 1]), d3, None, ptr(H[t - 1]), d, n,
-                                           ptr(dyn_n), d, dgi, k * 2 * d3, ptr(dGH[t]), 2 * d3, ptr(dhp), d, st)
-                gemm_nn(dGH[t], Whh, dhp, dyn_n, 1 if dyn_n is not None else 0, beta=1.0)      # dh_{t-1} += dgh_t W_hh
-                dh = dhp
-            else:
-                lib.srec_gru_pointwise_bwd(ptr(dh), d, ptr(gates[0]), None, 0, ptr(bhh), None, 0, n, ptr(dyn_n), d,
-                                           dgi, k * 2 * d3, ptr(dGH[0]), 2 * d3, None, 0, st)
-        gWhh = torch.zeros_like(Whh) if k == 1 else torch.empty_like(Whh)
-        if k > 1:
-            gemm_tn(dG[n:, d3:], H[:k - 1].reshape((k - 1) * n, d), gWhh, None)
-        gb = torch.empty(2 * d3, device=dev, dtype=torch.float32)
-        col_sum(dG, n * k, 2 * d3, gb, None)
-        gbih, gbhh = gb[:d3], gb[d3:]
-        gemm_nn(dGI, Wih, dX, dyn_rows, 1 if dyn_rows is not None else 0, beta=1.0)             # + the mean term
-        gWih = torch.empty_like(Wih)
-        gemm_tn(dGI, x, gWih, dyn_rows)
-        return dX, gWih, gbih, gWhh, gbhh, None, None, None, None
-
-
-def gru_expand(x, gru, k, dyn_n=None, dyn_rows=None, combine=True):
-    return GRUExpand.apply(x, gru.weight_ih_l0, gru.bias_ih_l0, gru.weight_hh_l0, gru.bias_hh_l0, k, dyn_n, dyn_rows,
-                           combine)
-
-
-def gru_wfrag_t(ws):
-    """fragment-major bf16 copies of GRU weights [3 d, d] for the backward-data products (csrc/grufb.hip), one launch"""
-    n, d = len(ws), ws[0].shape[1]
-    outs = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    a_w, a_o = ptr_array(ws), ptr_array(outs)
-    lib.srec_gru_wfrag_t(n, _ct.addressof(a_w), _ct.addressof(a_o), d, stream())
-    return outs
-
-
-def _gru_wfrag_args(ws):
-    of = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    ob = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    return of, ob, (ptr_array(ws), ptr_array(of), ptr_array(ob))
-
-
-def gru_wfrag_both(ws):
-    """gru_wfrag and gru_wfrag_t of the same weights in one launch -> (forward copies, backward copies) - unless the prologue
-    launch of this forward pass made them (step_prologue)"""
-    hit = [_wprep_take('gru', w) for w in ws]
-    if all(h is not None for h in hit):
-        return [h[0] for h in hit], [h[1] for h in hit]
-    of, ob, args = _gru_wfrag_args(ws)
-    lib.srec_gru_wfrag_both(len(ws), *[_ct.addressof(a) for a in args], ws[0].shape[1], stream())
-    return of, ob
-
-
-def gru_wfrag(ws):
-    """fragment-major bf16 copies of GRU weights [3 d, d] (the B operands of the fused forward, csrc/gruf.hip), one launch"""
-    hit = [_wprep_take('gru', w) for w in ws]
-    if all(h is not None for h in hit):
-        return [h[0] for h in hit]
-    n, d = len(ws), ws[0].shape[1]
-    outs = [torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    a_w, a_o = ptr_array(ws), ptr_array(outs)
-    lib.srec_gru_wfrag(n, _ct.addressof(a_w), _ct.addressof(a_o), d, stream())
-    return outs
-
-
-def gru_fused_ok(d, P):
-    return d in (128, 256) and P <= GRU_MAXP and FUSED_GRU
-
-
-def gru_expand_fast_ok(d, reducer):
-    return PRECISION['matmul'] == 'bf16' and reducer == 'mean' and d % 64 == 0 and d <= 1024 and 256 % (d // 4) == 0
-
-
-class GRUExpandAll(torch.autograd.Function):
-    """SemanticExpander (msgifsr.py:32-45, reducer 'mean') for ALL orders k >= 2 of a batch as one autograd node on the bf16
-    path (csrc/grux.hip + csrc/gemm16.hip): one grouped GEMM and one fused gate kernel per time step serve every order;
-    in the backward the hidden-state gradient is accumulated by the backward-data GEMM itself (beta = 1), the bias
-    gradients come from per-block partial sums of the gate kernels, the weight gradients from row-split products."""
-
-    @staticmethod
-    def _rows16(xs, d, dev, st):
-        """bf16 copy of the gathered rows: one pass when the orders' rows are adjacent pieces of one buffer"""
-        P = len(xs)
-        esz = xs[0].element_size()
-        adjacent = all(xs[p + 1].data_ptr() == xs[p].data_ptr() + xs[p].numel() * esz for p in range(P - 1))
-        tot = sum(x.shape[0] for x in xs)
-        x16all = torch.empty(tot, d, device=dev, dtype=torch.bfloat16)
-        offs, o = [], 0
-        for x in xs:
-            offs.append(o)
-            o += x.shape[0]
-        if adjacent:
-            lib.srec_rows_bf16(ptr(xs[0]), d, tot, None, d, ptr(x16all), st)
-        else:
-            for x, o in zip(xs, offs):
-                lib.srec_rows_bf16(ptr(x), d, x.shape[0], None, d, x16all[o:].data_ptr(), st)
-        x16 = [x16all[o:o + x.shape[0]] for x, o in zip(xs, offs)]
-        return x16all, x16
-
-    @staticmethod
-    def forward(ctx, ks, dyn_ns, dyn_rows, *args):
-        P = len(ks)
-        ctx.tags = [_arena_tag(a) for a in args[:P]]        # pieces of a split tensor: their gradients go into its buffer
-        xs = [a.contiguous() for a in args[:P]]
-        params = args[P:]
-        ctx.defer, ctx.wparams = defer_scope(), [params[4 * p + j] for p in range(P) for j in (0, 2)]
-        ctx.bparams = [params[4 * p + j] for p in range(P) for j in (1, 3)]
-        Wih, bih, Whh, bhh = ([params[4 * p + j].contiguous() for p in range(P)] for j in range(4))
-        d = xs[0].shape[1]
-        d3, dev, st = 3 * d, xs[0].device, stream()
-        ns = [x.shape[0] // k for x, k in zip(xs, ks)]
-        ctx.fused = gru_fused_ok(d, P)
-        if not ctx.fused:
-            w16, wt16 = weights_bf16([w for p in range(P) for w in (Wih[p], Whh[p])])
-            Wih16, Whh16 = w16[0::2], w16[1::2]
-        H = [torch.empty(ks[p], ns[p], d, device=dev, dtype=torch.float32) for p in range(P)]
-        H16 = [torch.empty(max(ks[p] - 1, 1), ns[p], d, device=dev, dtype=torch.bfloat16) for p in range(P)]
-        # saved gates: fp16 on the fused path (values in [-1, 1] and gh_n; half the bytes of the expander's largest tensor)
-        gates = [torch.empty(ks[p], ns[p], 4 * d, device=dev, dtype=torch.float16 if ctx.fused else torch.float32) for p in range(P)]
-        outs = [torch.empty(ns[p], d, device=dev, dtype=torch.float32) for p in range(P)]
-        if ctx.fused:
-            # the whole recurrence in one launch (csrc/gruf.hip): a workgroup owns 32 nodes, the weights stream from L2
-            ws = [w for p in range(P) for w in (Wih[p], Whh[p])]
-            if any(ctx.needs_input_grad):
-                wf, wft = gru_wfrag_both(ws)         # wft: the backward's copies (csrc/grufb.hip)
-            else:
-                wf, wft = gru_wfrag(ws), []
-            x16all = torch.empty(sum(x.shape[0] for x in xs), d, device=dev, dtype=torch.bfloat16)
-            x16, o = [], 0
-            for x in xs:
-                x16.append(x16all[o:o + x.shape[0]])
-                o += x.shape[0]
-            q = GruFusedDesc()
-            q.np, q.d = P, d
-            for p in range(P):
-                q.n[p], q.k[p], q.dyn[p] = ns[p], ks[p], ptr(dyn_ns[p])
-                q.X[p], q.X16[p], q.Wih_f[p], q.Whh_f[p] = ptr(xs[p]), ptr(x16[p]), ptr(wf[2 * p]), ptr(wf[2 * p + 1])
-                q.bih[p], q.bhh[p], q.H[p], q.H16[p] = ptr(bih[p]), ptr(bhh[p]), ptr(H[p]), ptr(H16[p])
-                q.gates[p], q.out[p] = ptr(gates[p]), ptr(outs[p])
-            lib.srec_gru_fused_fwd(_ct.addressof(q), st)
-            ctx.save_for_backward(*x16, *H, *H16, *gates, *wft)
-            ctx.meta = (ks, dyn_ns, dyn_rows, ns, d, [tuple(w.shape) for w in Wih])
-            return tuple(outs)
-        x16all, x16 = GRUExpandAll._rows16(xs, d, dev, st)
-        GI = [torch.empty(x.shape[0], d3, device=dev, dtype=torch.float32) for x in xs]
-        gemm16('nt', [(xs[p].shape[0], d3, d, [(x16[p], Wih16[p])], GI[p], dyn_rows[p]) for p in range(P)], d, d, d3,
-               keep_dead=True)
-        GH = [torch.empty(ns[p], d3, device=dev, dtype=torch.float32) for p in range(P)]
-        for t in range(max(ks)):
-            act = [p for p in range(P) if t < ks[p]]
-            if t > 0:
-                gemm16('nt', [(ns[p], d3, d, [(H16[p][t - 1], Whh16[p])], GH[p], dyn_ns[p]) for p in act], d, d, d3,
-                       keep_dead=True)
-            q = GruStepDesc()
-            q.np, q.d = len(act), d
-            for i, p in enumerate(act):
-                q.n[i], q.k[i], q.t[i], q.dyn[i] = ns[p], ks[p], t, ptr(dyn_ns[p])
-                q.GI[i], q.bih[i], q.bhh[i] = ptr(GI[p]), ptr(bih[p]), ptr(bhh[p])
-                if t > 0:
-                    q.GH[i], q.Hp[i] = ptr(GH[p]), ptr(H[p][t - 1])
-                q.Hn[i], q.gates[i] = ptr(H[p][t]), ptr(gates[p][t])
-                if t < ks[p] - 1:
-                    q.Hn16[i] = ptr(H16[p][t])
-                else:
-                    q.X[i], q.out[i] = ptr(xs[p]), ptr(outs[p])
-            lib.srec_gru_step_fwd(_ct.addressof(q), st)
-        ctx.save_for_backward(*x16, *H, *H16, *gates, *wt16)
-        ctx.meta = (ks, dyn_ns, dyn_rows, ns, d, [tuple(w.shape) for w in Wih])
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        ks, dyn_ns, dyn_rows, ns, d, _ = ctx.meta
-        P = len(ks)
-        sv = ctx.saved_tensors
-        x16, H, H16, gates = sv[:P], sv[P:2 * P], sv[2 * P:3 * P], sv[3 * P:4 * P]
-        wt16 = sv[4 * P:]
-        WihT16, WhhT16 = wt16[0::2], wt16[1::2]
-        d3, dev, st = 3 * d, H[0].device, stream()
-        gs = [g.contiguous() if g is not None else torch.zeros(ns[p], d, device=dev) for p, g in enumerate(gs)]
-        rows = [ns[p] * ks[p] for p in range(P)]
-        if all(t is not None for t in ctx.tags):
-            dX = [_arena_rows(t, r, d, dev) for t, r in zip(ctx.tags, rows)]
-        else:
-            dXall = torch.empty(sum(rows), d, device=dev, dtype=torch.float32)
-            offs, o = [], 0
-            for r in rows:
-                offs.append(o)
-                o += r
-            dX = [dXall[o:o + r] for o, r in zip(offs, rows)]
-        dGI16 = [torch.empty(rows[p], d3, device=dev, dtype=torch.bfloat16) for p in range(P)]
-        dGH16 = [torch.empty(max(ks[p] - 1, 1), ns[p], d3, device=dev, dtype=torch.bfloat16) for p in range(P)]   # slot t - 1
-        if ctx.fused:
-            # every time step of every order in one launch (csrc/grufb.hip); wt16 = the fragment-major weights here
-            nr_c, ns_c = _ct.c_int(0), (_ct.c_int * P)(*ns)
-            lib.srec_gru_fused_nodes(P, _ct.addressof(ns_c), d, _ct.addressof(nr_c))   # nodes per workgroup: one partial bias row each
-            nr = nr_c.value
-            part = [torch.empty((ns[p] + nr - 1) // nr, 6 * d, device=dev, dtype=torch.float32) for p in range(P)]
-            q = GruFusedBwdDesc()
-            q.np, q.d = P, d
-            for p in range(P):
-                q.n[p], q.k[p], q.dyn[p] = ns[p], ks[p], ptr(dyn_ns[p])
-                q.gates[p], q.H[p], q.dout[p] = ptr(gates[p]), ptr(H[p]), ptr(gs[p])
-                q.Wih_f[p], q.Whh_f[p] = ptr(wt16[2 * p]), ptr(wt16[2 * p + 1])
-                q.dGI16[p], q.dGH16[p], q.dX[p], q.bias_part[p], q.part_row0[p] = ptr(dGI16[p]), ptr(dGH16[p]), ptr(dX[p]), ptr(part[p]), 0
-            lib.srec_gru_fused_bwd(_ct.addressof(q), st)
-            return GRUExpandAll._weight_grads(ctx, x16, H16, dGI16, dGH16, part, dX)
-        rb = max(8, 1024 // d)                           # nodes per block of the step kernel
-        nblk = [(ns[p] + rb - 1) // rb for p in range(P)]
-        part = [torch.empty(ks[p] * nblk[p], 6 * d, device=dev, dtype=torch.float32) for p in range(P)]
-        dHcur = [None] * P
-        for t in range(max(ks) - 1, -1, -1):
-            act = [p for p in range(P) if t < ks[p]]
-            q = GruStepDesc()
-            q.np, q.d = len(act), d
-            nxt = {}
-            for i, p in enumerate(act):
-                q.n[i], q.k[i], q.t[i], q.dyn[i] = ns[p], ks[p], t, ptr(dyn_ns[p])
-                q.gates[i] = ptr(gates[p][t])
-                if t == ks[p] - 1:
-                    q.dout[i], q.dX[i] = ptr(gs[p]), ptr(dX[p])
-                else:
-                    q.dH[i] = ptr(dHcur[p])
-                q.dGI16[i] = ptr(dGI16[p])
-                if t > 0:
-                    q.Hp[i] = ptr(H[p][t - 1])
-                    q.dGH16[i] = ptr(dGH16[p][t - 1])
-                    nxt[p] = torch.empty(ns[p], d, device=dev, dtype=torch.float32)
-                    q.dHp[i] = ptr(nxt[p])
-                q.bias_part[i], q.part_row0[i] = ptr(part[p]), t * nblk[p]
-            lib.srec_gru_step_bwd(_ct.addressof(q), st)
-            if t > 0:          # d h_{t-1} += d(gh_t) W_hh
-                gemm16('nt', [(ns[p], d, d3, [(dGH16[p][t - 1], WhhT16[p])], nxt[p], dyn_ns[p]) for p in act], d3, d3, d,
-                       beta=1.0)
-                for p in act:
-                    dHcur[p] = nxt[p]
-        # d x += d(gi) W_ih  (onto the mean term the last-step kernels wrote)
-        gemm16('nt', [(rows[p], d, d3, [(dGI16[p], WihT16[p])], dX[p], dyn_rows[p]) for p in range(P)], d3, d3, d, beta=1.0)
-        return GRUExpandAll._weight_grads(ctx, x16, H16, dGI16, dGH16, part, dX)
-
-    @staticmethod
-    def _weight_grads(ctx, x16, H16, dGI16, dGH16, part, dX):
-        ks, dyn_ns, dyn_rows, ns, d, _ = ctx.meta
-        P = len(ks)
-        d3, dev, st = 3 * d, dX[0].device, stream()
-        rows = [ns[p] * ks[p] for p in range(P)]
-        # weight gradients: the reduction runs over rows - split in-kernel into ~512-row pieces (hundreds of short workgroups
-        # instead of a dozen long ones), each writing its own slab; the slabs are summed in fixed order
-        probs, slabs = [], []
-        # (ctx.wparams = [W_ih, W_hh] per order, ctx.bparams = [b_ih, b_hh] per order: bucket slots when row-sharded)
-        gWih = [grad_buf(ctx.wparams[2 * p]) for p in range(P)]
-        gWhh = [grad_buf(ctx.wparams[2 * p + 1]) for p in range(P)]
-        for p in range(P):
-            nsp = max(1, (rows[p] + 511) // 512)
-            sl = torch.empty(nsp, d3, d, device=dev, dtype=torch.float32) if nsp > 1 else gWih[p].unsqueeze(0)
-            probs.append(GemmProb(d3, d, rows[p], [(dGI16[p], x16[p])], sl, dyn_rows[p], nsplit=nsp))
-            if nsp > 1:
-                slabs.append((sl, gWih[p]))
-            nsp = max(1, (ns[p] + 511) // 512)
-            sl = torch.empty(nsp, d3, d, device=dev, dtype=torch.float32) if nsp > 1 else gWhh[p].unsqueeze(0)
-            segs = [(dGH16[p][t - 1], H16[p][t - 1]) for t in range(1, ks[p])]
-            probs.append(GemmProb(d3, d, ns[p], segs, sl, dyn_ns[p], nsplit=nsp))
-            if nsp > 1:
-                slabs.append((sl, gWhh[p]))
-        for i in range(0, len(probs), G16_MAXP):
-            gemm16('tn', probs[i:i + G16_MAXP], d3, d, d)
-        # bias gradients from the partial rows
-        gb = [grad_buf_pair(ctx.bparams[2 * p], ctx.bparams[2 * p + 1]) for p in range(P)]
-        # the weight-gradient slab sums join the ONE end-of-backward launch (defer_slab_sum); the bias partials keep their own
-        # kernel: hundreds of partial rows of only 6 d columns - as a task of the generic slab sum (one thread per 4 columns
-        # walking all rows) they made that launch 44 us (profiles/r03d), gru_bias_final splits the rows over 16 lanes: 5 us
-        ok = can_defer(ctx.defer, ctx.wparams)
-        for sl, o_ in slabs:
-            defer_slab_sum(sl, o_, ok)
-        if ok and can_defer(ctx.defer, ctx.bparams):
-            # ... and so do the bias partials (hundreds of rows of 6 d columns: the "tall" tasks of srec_sum_slabs_multi)
-            for p in range(P):
-                defer_slab_sum(part[p], gb[p], True, tall=True)
-        else:
-            a_p, a_o = ptr_array(part), ptr_array(gb)
-            a_r = (_ct.c_int * P)(*[t_.shape[0] for t_ in part])
-            lib.srec_gru_bias_final(P, _ct.addressof(a_p), _ct.addressof(a_r), 6 * d, _ct.addressof(a_o), st)
-        grads = []
-        for p in range(P):
-            grads += [gWih[p], gb[p][:d3], gWhh[p], gb[p][d3:]]
-        return (None, None, None) + tuple(dX) + tuple(grads)
-
-
-def gru_expand_all(xs, grus, ks, dyn_ns, dyn_rows):
-    """xs[i]: [N_k k, d] gathered rows of order ks[i] (>= 2) -> [N_k, d] expander outputs, all orders in one node"""
-    params = []
-    for g in grus:
-        params += [g.weight_ih_l0, g.bias_ih_l0, g.weight_hh_l0, g.bias_hh_l0]
-    return GRUExpandAll.apply(tuple(ks), tuple(dyn_ns), tuple(dyn_rows), *xs, *params)
-
-
-def gram_combine(X, Hl, k, dyn=None):
-    return GramCombine.apply(X, Hl, k, dyn)
-
-
 # ------------------------------------------------------------------------------------------ GAT
 class GATRelation(torch.autograd.Function):
     """rst[v,h,:] = sum_{u->v} softmax_v(LeakyReLU(el_u + er_v)) * feat_src[u,h,:] for one relation.
@@ -2336,6 +1890,10 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
 DROP_TAP = None      # tests: set to a list to receive {'ms': [2, NT, D], 'mk': [per instance (E*H,)]} of every dropout layer call
 
 from .hgat import HgPlan, HGATLayer, hgat_layer  # noqa: E402,F401  (the MSHGNN layer: hgat.py imports this module)
+from .gru import (  # noqa: E402,F401  (the GRU step, the k-gram expander: gru.py imports this module)
+    GramCombine, GruOrder, GRUExpand, GRUExpandAll, GRUPointwise, _gru_wfrag_args, expand_path, gram_combine, gru_expand,
+    gru_expand_all, gru_expand_fast_ok, gru_fused_bwd_desc, gru_fused_desc, gru_fused_ok, gru_step, gru_step_desc, gru_wfrag,
+    gru_wfrag_both)
 from .score import (  # noqa: E402,F401  (full-catalog scoring: score.py imports this module)
     CEWorkspace, MixtureArgs, ScoreCE, ScoreLogProb, ScoreStats, TableBF16, _bf16_dim_ok, _byte_ws, _ce_bwd, _ce_fwd, _logp_cols,
     _mixture_args, _pad_rows, _prepare_sr, finish_table_grad, score_ce, score_logp, score_rank, score_select, score_stats,

@@ -1129,6 +1129,78 @@ def test_gru_fused_forward_equals_the_step_path(dev, d, padded, big, monkeypatch
             assert rel(a, b) < 3e-3, (p, nm, rel(a, b))
 
 
+def _small_gru_case(dev, d, lives, padded):
+    """ks = [2, 3] with capacities [40, 24] nodes (2.5 and 1.5 sixteen-node tiles): GRUs, gathered rows [152, d], first row of order 3,
+    dyn tensors of the `padded` orders (None: every node is live)"""
+    ks, caps = [2, 3], [40, 24]
+    grus = [torch.nn.GRU(d, d, 1, True, True).to(dev) for _ in ks]
+    for g in grus:
+        for w in g.parameters():
+            w.data.uniform_(-1 / d ** 0.5, 1 / d ** 0.5)
+    rows = torch.randn(sum(c * k for c, k in zip(caps, ks)), d, device=dev) * 0.5
+    dyn_n = [torch.tensor([l], device=dev, dtype=torch.int32) if p else None for l, p in zip(lives, padded)]
+    dyn_r = [torch.tensor([l * k], device=dev, dtype=torch.int32) if p else None for l, k, p in zip(lives, ks, padded)]
+    return ks, caps, grus, rows, caps[0] * ks[0], dyn_n, dyn_r
+
+
+def test_gru_expand_all_inputs_that_are_not_adjacent(dev):
+    """the step path (d = 64) copies the gathered rows to bf16 in ONE launch when the orders' inputs are adjacent pieces of one
+    buffer and in one launch per order otherwise, and returns d x as pieces of one buffer: same bits either way"""
+    ops = _ops()
+    torch.manual_seed(64)
+    ks, caps, grus, rows, o1, dyn_n, dyn_r = _small_gru_case(dev, 64, [33, 24], [True, False])
+    gout = [torch.randn(c, 64, device=dev) for c in caps]
+
+    def run(xs):
+        for g in grus:
+            g.zero_grad()
+        outs = ops.gru_expand_all(xs, grus, ks, dyn_n, dyn_r)
+        torch.autograd.backward(list(outs), gout)
+        return [o.detach().clone() for o in outs], [p.grad.clone() for g in grus for p in g.parameters()]
+
+    ops.set_precision('bf16')
+    try:
+        assert ops.gru_expand_fast_ok(64, 'mean') and not ops.gru_fused_ok(64, 2)
+        r = rows.clone().requires_grad_()
+        a = run([r[:o1], r[o1:]])
+        x0, held = rows[:o1].clone().requires_grad_(), [rows[o1:].clone()]
+        while held[-1].data_ptr() == x0.data_ptr() + x0.numel() * 4:       # (side by side by chance: the next copy cannot be there)
+            held.append(rows[o1:].clone())
+        x1 = held[-1].requires_grad_()
+        b = run([x0, x1])
+    finally:
+        ops.set_precision('fp32')
+    assert len(a[1]) == 8
+    for p in range(2):
+        assert torch.equal(a[0][p], b[0][p]), ('out', p)
+    assert a[0][0][33:].abs().max().item() == 0.0
+    assert torch.equal(r.grad, torch.cat([x0.grad, x1.grad])), 'dx'
+    for i, (ga, gb) in enumerate(zip(a[1], b[1])):
+        assert torch.equal(ga, gb), ('parameter gradient', i)
+
+
+def test_gru_fused_forward_without_gradients(dev):
+    """the fused path (d = 128) makes forward-only fragment copies of the weights under no_grad (srec_gru_wfrag) and both layouts
+    otherwise (srec_gru_wfrag_both): same outputs, exact zeros past the live nodes (2.5 and 1.5 sixteen-node tiles, 33 and 7 live)"""
+    ops = _ops()
+    torch.manual_seed(128)
+    lives = [33, 7]
+    ks, caps, grus, rows, o1, dyn_n, dyn_r = _small_gru_case(dev, 128, lives, [True, True])
+    ops.set_precision('bf16')
+    try:
+        assert ops.gru_expand_fast_ok(128, 'mean') and ops.gru_fused_ok(128, 2)
+        with torch.no_grad():
+            a = ops.gru_expand_all([rows[:o1], rows[o1:]], grus, ks, dyn_n, dyn_r)
+        assert not any(o.requires_grad for o in a)
+        b = ops.gru_expand_all([rows[:o1], rows[o1:]], grus, ks, dyn_n, dyn_r)
+        assert all(o.requires_grad for o in b)
+    finally:
+        ops.set_precision('fp32')
+    for p in range(2):
+        assert torch.equal(a[p], b[p].detach()), ('out', p)
+        assert a[p][lives[p]:].abs().max().item() == 0.0 and a[p][:lives[p]].abs().max().item() > 0.0
+
+
 def test_lookup_with_fused_dropout(dev):
     """feature dropout fused into the embedding gather and its backward (msgifsr.py:247): the output is table[idx] times a
     0 / (1 / (1 - p)) mask with keep-rate 1 - p, the backward applies the SAME mask (recomputed from the counter-based
