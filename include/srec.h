@@ -515,6 +515,22 @@ int srec_score_select(const float* sr, int ld_sr, long comp_stride, const float*
                       long id_lo, int B, int V, int d, int C, int K,
                       float* out_val, int* out_idx, void* ws, void* stream);
 
+/* ---- serving: the score of GIVEN items per session (score_items.hip) ---------------------------------------------------
+ * Replaces `logits = model(...); logits.gather(1, items)` (msgifsr.py:306-321 / srgnn.py:145-147) for re-ranking, allow-lists,
+ * sampled-negative evaluation and lists longer than SREC_SELECT_MAXK: out[b,m] (fp32 [B, M]) is the score of srec_score_rank /
+ * srec_score_select at the global id items[b * ld_items + m], with the same layouts and limits (1 <= C <= 4, d % 4 == 0,
+ * d <= 1024, L <= 64; cs / off_* / listed nullable; C == 1: z + off, no exp / log).  ld_items == 0: one list of M ids shared
+ * by all sessions.  Per slot: an id < 0 (padding) gives -INFINITY; a row outside [id_lo, id_lo + V) belongs to another shard
+ * and gives 0.0f without any memory read, so the results of disjoint row ranges ADD UP (as the targets of srec_score_rank);
+ * SREC_LISTED_SCORE: an item of listed[b,:] scores with off_in; SREC_LISTED_DROP: the shard that owns it gives -INFINITY
+ * (off_in is ignored).  Duplicate ids in a list are legal and scored independently.  The output is a pure function of the
+ * inputs: the summation order depends on (d, C) alone, no atomics, no workspace.  Nonzero and no launch for: pointers not
+ * aligned (sr, E: 16 bytes), d % 4 != 0, C or L out of range, M < 1, id_lo < 0, 0 < ld_items < M. */
+int srec_score_items(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                     const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                     const int* items, long ld_items, int M, long id_lo,
+                     int B, int V, int d, int C, float* out, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

@@ -408,6 +408,10 @@ class HipLocal:
         """this shard's k best rows (values, global ids) of ops.score_select: rows [id_lo, id_lo + n) of the catalog"""
         return self.ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo)
 
+    def score_items(self, srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo):
+        """this shard's share of ops.score_items: rows [id_lo, id_lo + n) of the catalog score, every other id gives 0"""
+        return self.ops.score_items(srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo)
+
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
 
@@ -859,6 +863,38 @@ class VocabParallel:
         if data_parallel:
             val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
         return val, idx
+
+    def score_items(self, srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False):
+        """the scores of given items over the sharded table (ops.score_items' contract; srs: list of C [B, d] session
+        vectors, off_ex / off_in [C, B], listed [B, L] global ids, items [B, M] or [M] global ids): every rank scores the ids
+        among its own LIVE rows with its id_lo (padding rows are never owners) and gives 0 for the others, -inf for padding
+        slots and dropped items - ONE sum-all-reduce of [B, M] floats finishes it.  data_parallel as in select(): every rank
+        passes its own B / world sessions (and their [B / world, M] items; a 1-D list is the same on every rank) and gets its
+        own sessions' scores."""
+        n_loc = srs[0].shape[0]
+        if data_parallel:
+            srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
+            gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
+            off_ex, off_in = gat(off_ex), gat(off_in)
+            if items.dim() == 2:
+                items = all_gather_cat(items.contiguous(), self.group)
+            if listed is not None:           # lists of different widths on the ranks: pad to the widest
+                w = torch.tensor([listed.shape[1]], dtype=torch.int64, device=listed.device)
+                if _active(self.group):
+                    all_reduce_(w, dist.ReduceOp.MAX, self.group)
+                pad = listed.new_full((listed.shape[0], int(w.item())), -1)
+                pad[:, :listed.shape[1]] = listed
+                listed = all_gather_cat(pad, self.group)
+        B = srs[0].shape[0]
+        if self.n_live > 0:
+            csl = None if cs is None else cs[:self.n_live]
+            out = self.local.score_items(srs, table[:self.n_live], csl, items, off_ex, off_in, listed, drop_listed, self.lo)
+        else:                                # a rank without live rows owns nothing
+            out = torch.zeros(B, items.shape[-1], device=srs[0].device, dtype=torch.float32)
+        all_reduce_sum(out, self.group)      # (-inf + 0 and -inf + -inf stay -inf: no slot is ever +inf)
+        if data_parallel:
+            out = out[self.rank * n_loc:(self.rank + 1) * n_loc]
+        return out
 
     # ---- replicated-parameter gradients: bucketed all-reduce, launched in backward order ----------------------------------
     N_BUCKETS = 3

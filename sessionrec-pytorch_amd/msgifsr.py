@@ -611,6 +611,19 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             off_in = None
         return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen)
 
+    def _score_items(self, *inputs, items, exclude_seen):
+        """the mixture of _recommend at given items: with `extra` the session's own items are `listed` and score through the
+        repeat branch (off_in); exclude_seen gives them -inf instead"""
+        if not (self.extra or (self.fusion and self.order > 1)):
+            return super()._score_items(*inputs, items=items, exclude_seen=exclude_seen)
+        (mg,) = inputs
+        srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg)
+        if self.extra or exclude_seen:
+            listed = self._session_items(mg)
+        if exclude_seen:
+            off_in = None
+        return self._items_of(srs, cs, items, off_ex, off_in, listed, exclude_seen)
+
     def forward(self, mg):
         sr = self.session_repr(mg)
         if self.extra:

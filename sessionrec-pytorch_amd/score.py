@@ -1,5 +1,5 @@
-"""Full-catalog scoring (csrc/score_ce*.hip, rank.hip, recommend.hip): the fused CE / statistics nodes, top-K, target rank,
-top-N select and the (B, V) log-probabilities, with the workspaces and argument conventions they share.
+"""Full-catalog scoring (csrc/score_ce*.hip, rank.hip, recommend.hip, score_items.hip): the fused CE / statistics nodes, top-K,
+target rank, top-N select, the scores of given items and the (B, V) log-probabilities, with the workspaces and argument conventions they share.
 ops.py keeps the GEMM wrappers and the tests' switches (reached through the module object at call time) and re-exports this."""
 import ctypes as _ct
 from collections import namedtuple
@@ -258,7 +258,7 @@ def score_topk(sr, table, cs, k):
     return val, idx
 
 
-# what score_rank / score_select launch with: srs as (pointer, row stride, component stride), C components of [B, d];
+# what score_rank / score_select / score_items launch with: srs as (pointer, row stride, component stride), C components of [B, d];
 # table [V, d] as rows; off_ex / off_in fp32 [C, B] or None; listed int32 [B, L] or None with L = 0
 MixtureArgs = namedtuple('MixtureArgs', 'srs ld_sr comp C B d table V off_ex off_in listed L')
 _LISTED_MAX = 64
@@ -266,11 +266,12 @@ _LISTED_TOO_MANY = {
     'score_rank': 'score_rank: %d listed items per session; the fix-up pass of csrc/rank.hip takes at most 64 '
                   '(evaluate such sessions with method="topk")',
     'score_select': 'score_select: %d listed items per session; csrc/recommend.hip takes at most 64',
+    'score_items': 'score_items: %d listed items per session; csrc/score_items.hip takes at most 64',
 }
 
 
 def _mixture_args(who, srs, table, off_ex, off_in, listed):
-    """The argument conventions score_rank and score_select share, as one MixtureArgs.  srs: [B, d] (row-strided views are
+    """The argument conventions score_rank, score_select and score_items share, as one MixtureArgs.  srs: [B, d] (row-strided views are
     taken as they are), [C, B, d], [1, B, d] or a list of C [B, d] tensors; off_ex / off_in: anything of C * B numbers or
     None; listed: [B, L] item ids, empty or None = no list.  More than 64 listed items per session raise ValueError in the
     words of `who`.  Pure torch (no launch, no library call): it checks CPU tensors as well."""
@@ -355,6 +356,42 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     lib.srec_score_select(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
                           ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, k, ptr(val), ptr(idx), ptr(ws), stream())
     return val, idx
+
+
+def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, checked=False):
+    """fp32 [B, M]: the score of score_rank / score_select, s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]), at the
+    given items of every session - no (B, V) tensor, no limit on M (csrc/score_items.hip: one gather pass, the session
+    vectors in registers).  items: [B, M] global ids per session or [M] shared by all sessions, any integer dtype; -1 is
+    padding and gives -inf; duplicates are scored independently.  Argument conventions as score_select: srs [B, d],
+    [C, B, d] or a list of C [B, d] tensors, C <= 4; off_ex / off_in [C, B] or None (= 0); listed [B, L] global item ids,
+    -1 = empty slot; drop_listed=False: listed items score with off_in; True: they give -inf (off_in is ignored).  id_lo:
+    global id of table row 0 (a row shard): an id outside [id_lo, id_lo + rows) gives 0.0, so the results of disjoint shards
+    add up.  An id < -1 raises ValueError before any launch (one device-to-host read of the smallest id; checked=True: the
+    caller has looked already); an upper bound cannot be checked here - a shard sees only its own range - the model-level
+    entry (model.score_items) checks it.
+    Measured at B 512, V 37 484, d 256 (profiles/score_items_timing.txt): with the lse pass a single
+    soft-max needs ahead of it, this route beats score_logp(...).gather(1, items) up to M = 2000 (342 against 352 us) and
+    loses at M = 4000 (462 against 370 us) - for lists of several thousand items per session materialise instead; a C = 3
+    mixture stays 2.6x ahead of forward().gather at M = 4000."""
+    a = _mixture_args('score_items', srs, table, off_ex, None if drop_listed else off_in, listed)
+    B, dev = a.B, a.srs.device
+    items = items.detach()
+    if items.is_floating_point() or items.is_complex() or items.dtype == torch.bool or items.dim() not in (1, 2):
+        raise TypeError('score_items: items must be an integer tensor [B, M] or [M], got %s %s' % (items.dtype, tuple(items.shape)))
+    if items.dim() == 2 and items.shape[0] != B:
+        raise ValueError('score_items: items has %d rows for %d sessions' % (items.shape[0], B))
+    M = items.shape[-1]
+    out = torch.empty(B, M, device=dev, dtype=torch.float32)
+    if B == 0 or M == 0:
+        return out
+    if not checked and int(items.min()) < -1:
+        raise ValueError('score_items: item id %d; ids are >= 0, or -1 for a padding slot' % int(items.min()))
+    items = items.to(torch.int32).contiguous()
+    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
+    lib.srec_score_items(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
+                         ptr(a.listed), a.L, mode, ptr(items), M if items.dim() == 2 else 0, M, int(id_lo), B, a.V, a.d, a.C,
+                         ptr(out), stream())
+    return out
 
 
 def _logp_cols(sr, ld_sr, table, cs, lse):

@@ -270,6 +270,57 @@ class _ScoringMixin:
                                      data_parallel=self.shard.eval_data_parallel)
         return ops.score_select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed)
 
+    def score_items(self, *inputs, items, exclude_seen=False):
+        """fp32 [B, M]: the log-probability forward() returns at the given items of every session - full-catalog soft-max
+        (or mixture), NO renormalisation over the candidates.  items: [B, M] item ids per session or [M] shared by all
+        sessions, any integer dtype, any M; -1 is padding and gives -inf; duplicates are allowed.  exclude_seen=True gives
+        -inf at the session's own items (at most 64 distinct items per session) and leaves the rest unchanged.  An id
+        < -1 or >= num_items raises ValueError before anything is launched.  One gather pass over the candidates' rows
+        (csrc/score_items.hip): no (B, V) score matrix, sharded table included.  Runs in eval mode under torch.no_grad()."""
+        n = self.shard.V if self.shard is not None else self._table().shape[0]
+        if items.numel() > 0:
+            lo, hi = (int(x) for x in torch.aminmax(items.detach()))
+            if lo < -1 or hi >= n:
+                raise ValueError('score_items: item id %d; ids are in [0, %d), or -1 for a padding slot' % (lo if lo < -1 else hi, n))
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                return self._score_items(*inputs, items=items, exclude_seen=exclude_seen)
+        finally:
+            self.train(was_training)
+
+    def _score_items(self, *inputs, items, exclude_seen):
+        sr = self.session_repr(*inputs)
+        st = self._state(sr.shape[0])
+        cs, inv_scale = self._col_scale(st)
+        off_ex = -self._lse(sr, cs, inv_scale, st).unsqueeze(0)      # log softmax = z - lse
+        listed = self._session_items(inputs[0]) if exclude_seen else None
+        return self._items_of([sr], cs, items, off_ex, None, listed, exclude_seen)
+
+    def _items_of(self, srs, cs, items, off_ex, off_in, listed, drop_listed):
+        items = items.to(srs[0].device)
+        if self.shard is not None:       # every shard scores the ids it owns, the others give 0: one all-reduce of [B, M] floats
+            return self.shard.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed,
+                                          data_parallel=self.shard.eval_data_parallel)
+        return ops.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed, checked=True)
+
+    def rerank(self, *inputs, items, k=None, exclude_seen=False):
+        """(log_probs fp32 [B, n], item_ids int32 [B, n]), n = M or min(k, M): the candidates of score_items ordered by
+        (value descending, id ascending) - the contract of recommend()'s lists without its limit of 128.  Slots that score
+        -inf (padding, and the session's own items under exclude_seen) come last with id -1; a candidate named twice is
+        returned twice."""
+        val = self.score_items(*inputs, items=items, exclude_seen=exclude_seen)
+        ids = items.to(val.device).to(torch.int64)
+        ids = torch.where(val == float('-inf'), torch.full_like(val, -1, dtype=torch.int64), ids.expand_as(val))
+        # two stable sorts, as the merge of dist.VocabParallel.select: by id (unfilled slots last), then by value
+        o = torch.argsort(torch.where(ids < 0, torch.full_like(ids, 2 ** 62), ids), dim=1, stable=True)
+        val, ids = val.gather(1, o), ids.gather(1, o)
+        o = torch.argsort(val, dim=1, descending=True, stable=True)
+        if k is not None:
+            o = o[:, :max(int(k), 0)]
+        return val.gather(1, o).contiguous(), ids.gather(1, o).to(torch.int32).contiguous()
+
     def _log_probs(self, sr):
         B = sr.shape[0]
         st = self._state(B)
