@@ -531,6 +531,36 @@ int srec_score_items(const float* sr, int ld_sr, long comp_stride, const float* 
                      const int* items, long ld_items, int M, long id_lo,
                      int B, int V, int d, int C, float* out, void* stream);
 
+/* ---- serving: per-item bias and catalogue filters in the two calls above (recommend.hip, score_items.hip) --------------------
+ * One more operand, added AFTER the mixture:  s'[b,v] = s[b,v] + bias[group[b] * ld_bias + v]  - a log-prior correction, a
+ * boost or a penalty; -INFINITY means "item v is not in the catalogue for this call".  bias: fp32, indexed by the LOCAL row
+ * like cs (a row shard passes the pointer to its first column and the full row stride ld_bias), G rows; group [B] picks the
+ * row of every session, group == NULL means row 0 for every session and is legal only with G == 1 (ld_bias is not read
+ * then).  bias == NULL: srec_score_select / srec_score_items, which ARE that case of these entry points, bit for bit.  NaN or
+ * +INFINITY in bias and a group id outside [0, G) are the CALLER's error: nothing here looks for them, the kernels assume
+ * neither occurs (a group id is held inside [0, G), nothing else is promised for it).  All other arguments, layouts and
+ * limits are those of the unbiased calls.
+ * Select: an item whose bias is -INFINITY is ineligible for that session and is NEVER returned, also when fewer than K items
+ * are eligible - the list then ends in (-INFINITY, -1) slots (eligibility is tested by itself: an eligible item that merely
+ * scores -INFINITY still precedes an unfilled slot, as in srec_score_select).  Lists are ordered by (biased value descending,
+ * id ascending), out_val holds the biased scores, and the output stays a pure function of the inputs (no atomics, no
+ * arrival order).  ws: srec_score_select_ws() bytes, as without a bias.
+ * Items: the shard that owns the id adds the bias, and -INFINITY stays -INFINITY; a padding slot (-1) gives -INFINITY; a
+ * foreign id gives 0.0f without a read of the table OR of the bias, so disjoint shards still add up, to the bits of one
+ * device; an item dropped by SREC_LISTED_DROP gives -INFINITY.
+ * An all-zero bias returns the ids and (by ==) the values of the unbiased call.
+ * Nonzero and no launch, beyond the unbiased calls' reasons: G < 1; group == NULL with G > 1; bias != NULL with ld_bias < V
+ * and G > 1; bias or group not aligned to 4 bytes. */
+int srec_score_select_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                             const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                             long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                             const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream);
+int srec_score_items_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                            const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                            const int* items, long ld_items, int M, long id_lo,
+                            int B, int V, int d, int C, const float* bias, long ld_bias,
+                            const int* group, int G, float* out, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

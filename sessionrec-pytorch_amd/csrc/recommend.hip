@@ -21,6 +21,14 @@
 // The output is a pure function of the inputs: positions come from comparisons of (value, id) keys, never from arrival.
 // LDS: 1.5 KB of offsets and masks + 32 K (value, id) pairs + 17 KB candidates + 32 L ids + the session tiles when the sum
 // stays within 160 KB (C = 3, d = 256, K = 128, L = 64: 156.5 KB), else the tiles are read through the cache.
+//
+// srec_score_select_biased: s' = s + bias[group[b], v], a per-item fp32 operand added AFTER the mixture; -INFINITY = the item is
+// not in the catalogue for this session: it never enters a list (a condition of `hit`, not a consequence of its score - an
+// item that merely scores -INFINITY still beats an unfilled slot, as before).  BIAS is a template parameter: 0 = none (the
+// instances of srec_score_select, unchanged), 1 = one row for all sessions (the lane that owns item v loads bias[v] once per
+// chunk beside its column scale), 2 = G rows (the 32 sessions' row offsets are staged in LDS, 256 bytes counted by
+// part_lds; a lane loads its item's bias for its 16 sessions ahead of the tile product, every load coalesced over the 32
+// items of a half-wavefront).  With the 256 bytes the C = 3, d = 256, K = 128, L = 64 case is 156.9 KB: still LDS tiles.
 #include "common.h"
 #include "score_tile.h"
 
@@ -42,6 +50,8 @@ struct SelArgs {
     int B, V, d, K;
     int items_per_range;
     float* pv; int* pi;             // [R][B][K] per-range lists (local rows; EMPTY = unfilled)
+    const float* bias; long ld_bias; // (appended: the unbiased instances read the arguments above where they were)
+    const int* group; int G;
 };
 
 __device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
@@ -97,12 +107,13 @@ __device__ __forceinline__ void merge_sorted(float* lv, int* li, int K, const fl
     __builtin_amdgcn_wave_barrier();
 }
 
-inline size_t part_lds(int C, int d, int K, int L, bool sr_lds) {
+inline size_t part_lds(int C, int d, int K, int L, bool sr_lds, bool grouped = false) {
     const size_t head = (size_t)(2 * MAXCOMP * SB + SB * 4 + SB * 4 + SB) * 4;
-    return head + (size_t)SB * K * 8 + (size_t)SB * CST * 4 + (size_t)SB * L * 4 + (sr_lds ? tile_bytes(C, d) : 0);
+    return head + (size_t)SB * K * 8 + (size_t)SB * CST * 4 + (size_t)SB * L * 4 + (grouped ? (size_t)SB * 8 : 0) +
+           (sr_lds ? tile_bytes(C, d) : 0);
 }
 
-template <int C, bool SR_LDS>
+template <int C, bool SR_LDS, int BIAS>
 __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int d = a.d, K = a.K, L = a.L;
@@ -115,7 +126,8 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     int* li = reinterpret_cast<int*>(lv + SB * K);                  // [SB][K] ... and local rows
     float* cand = reinterpret_cast<float*>(li + SB * K);            // [SB][CST] scores of this chunk's survivors
     int* lst = reinterpret_cast<int*>(cand + SB * CST);             // [SB][L] listed ids as local rows, in-range ones first
-    float* Ss = reinterpret_cast<float*>(lst + SB * L);             // [C][SB][LD] (SR_LDS); 16-byte aligned: all counts above are multiples of 4
+    unsigned long long* goff = reinterpret_cast<unsigned long long*>(lst + SB * L);   // [SB] bias row offsets (BIAS == 2 only)
+    float* Ss = reinterpret_cast<float*>(goff + (BIAS == 2 ? SB : 0));  // [C][SB][LD] (SR_LDS); 16-byte aligned: all counts above are multiples of 4
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
@@ -131,6 +143,10 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     }
     for (int i = tid; i < SB * K; i += 256) { lv[i] = -INFINITY; li[i] = EMPTY; }
     if (tid < SB * 4) inm[tid] = 0u;
+    if constexpr (BIAS == 2) {
+        // sessions past the batch read row 0; an id outside [0, G) is the caller's error and is held inside the operand
+        if (tid < SB) goff[tid] = b0 + tid < a.B ? (unsigned long long)min(max(a.group[b0 + tid], 0), a.G - 1) * a.ld_bias : 0ull;
+    }
     if (has_list) {
         // the session's listed ids inside [v0, v1), compacted to the front of its row in list order (ballot prefix)
         for (int j = wave; j < SB; j += 4) {
@@ -167,6 +183,13 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
         const bool vok = v < v1;
         const float* brow = a.E + (size_t)min(v, a.V - 1) * a.ld_e + 4 * half;
         const float csv = (a.cs != nullptr && vok) ? a.cs[v] : 1.f;
+        float bv = 0.f;               // BIAS == 1: this lane's item, all sessions
+        float bg[BIAS == 2 ? 16 : 1]; // BIAS == 2: this lane's item, its 16 sessions (under way during the tile product)
+        if constexpr (BIAS == 1) bv = vok ? a.bias[v] : 0.f;
+        if constexpr (BIAS == 2) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) bg[r] = a.bias[goff[session_of(r, half)] + min(v, a.V - 1)];
+        }
         f32x16 acc[C];
         dots<C, SR_LDS>(arow, brow, d, half, acc);
         __syncthreads();              // membership bits written; the merges of the previous chunk are done
@@ -180,8 +203,14 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
             float z[C];
 #pragma unroll
             for (int c = 0; c < C; ++c) z[c] = csv * acc[c][r] + of[c * SB + sl];
-            const float s = mix<C>(z);
-            const bool hit = vok && b0 + sl < a.B && !(in && drop) && better(s, v, lv[sl * K + K - 1], li[sl * K + K - 1]);
+            float s = mix<C>(z);
+            bool elig = true;         // a bias of -INFINITY: not in the catalogue of this session
+            if constexpr (BIAS != 0) {
+                const float bb = BIAS == 1 ? bv : bg[BIAS == 2 ? r : 0];
+                s += bb;
+                elig = bb != -INFINITY;
+            }
+            const bool hit = vok && b0 + sl < a.B && !(in && drop) && elig && better(s, v, lv[sl * K + K - 1], li[sl * K + K - 1]);
             const unsigned long long mk = __ballot(hit);
             if (hit) cand[sl * CST + wave * 32 + l31] = s;
             if (l31 == 0) surv[sl * 4 + wave] = half ? (unsigned)(mk >> 32) : (unsigned)mk;
@@ -263,20 +292,27 @@ inline int pick_ranges(int B, int V) {
     return R < 1 ? 1 : R;
 }
 
-template <int C, bool SR_LDS>
+template <int C, bool SR_LDS, int BIAS>
 int launch_part(const SelArgs& a, dim3 grid, size_t lds, hipStream_t st) {
     static std::atomic<unsigned long long> optin{0};
-    if (int rc = srec_lds_optin((const void*)select_part_kernel<C, SR_LDS>, LDS_BYTES, optin)) return rc;
-    hipLaunchKernelGGL((select_part_kernel<C, SR_LDS>), grid, dim3(256), lds, st, a);
+    if (int rc = srec_lds_optin((const void*)select_part_kernel<C, SR_LDS, BIAS>, LDS_BYTES, optin)) return rc;
+    hipLaunchKernelGGL((select_part_kernel<C, SR_LDS, BIAS>), grid, dim3(256), lds, st, a);
     return 0;
+}
+
+template <int C, int BIAS>
+int run_part(const SelArgs& a, dim3 grid, hipStream_t st) {
+    const bool fits = part_lds(C, a.d, a.K, a.L, true, BIAS == 2) <= (size_t)LDS_BYTES;
+    return fits ? launch_part<C, true, BIAS>(a, grid, part_lds(C, a.d, a.K, a.L, true, BIAS == 2), st)
+                : launch_part<C, false, BIAS>(a, grid, part_lds(C, a.d, a.K, a.L, false, BIAS == 2), st);
 }
 
 template <int C>
 int run(const SelArgs& a, int R, float* out_val, int* out_idx, hipStream_t st) {
     const dim3 grid(R, cdiv(a.B, SB));
-    const bool fits = part_lds(C, a.d, a.K, a.L, true) <= (size_t)LDS_BYTES;
-    const int rc = fits ? launch_part<C, true>(a, grid, part_lds(C, a.d, a.K, a.L, true), st)
-                        : launch_part<C, false>(a, grid, part_lds(C, a.d, a.K, a.L, false), st);
+    const int rc = a.bias == nullptr ? run_part<C, 0>(a, grid, st)
+                   : a.G == 1        ? run_part<C, 1>(a, grid, st)
+                                     : run_part<C, 2>(a, grid, st);
     if (rc) return rc;
     hipLaunchKernelGGL(select_merge_kernel, dim3(cdiv(a.B, 4)), dim3(256), 0, st, a.pv, a.pi, R, a.B, a.K, a.id_lo, out_val,
                        out_idx);
@@ -297,19 +333,21 @@ extern "C" int srec_score_select_ws(int B, int V, int d, int C, int L, int K, lo
     return 0;
 }
 
-extern "C" int srec_score_select(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                 const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                 long id_lo, int B, int V, int d, int C, int K, float* out_val, int* out_idx, void* ws,
-                                 void* stream) {
+extern "C" int srec_score_select_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                        const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                                        long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                                        const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream) {
     if (B <= 0) return 0;
     if (bad_shape(B, V, d, C, L, K) || (ld_sr & 3) || (ld_e & 3) || (comp_stride & 3) || ((uintptr_t)E & 15) ||
         ((uintptr_t)sr & 15) || out_val == nullptr || out_idx == nullptr || ws == nullptr || id_lo < 0 ||
-        id_lo + (long)V > 0x7fffffffL || (listed_mode != 0 && listed_mode != 1))
+        id_lo + (long)V > 0x7fffffffL || (listed_mode != 0 && listed_mode != 1) || G < 1 || (group == nullptr && G > 1) ||
+        (bias != nullptr && G > 1 && ld_bias < (long)V) || ((uintptr_t)bias & 3) || ((uintptr_t)group & 3))
         return SREC_BAD_ARG;
     SelArgs a{};
     a.sr = sr; a.ld_sr = ld_sr; a.comp_stride = comp_stride; a.E = E; a.ld_e = ld_e; a.cs = cs;
     a.off_ex = off_ex; a.off_in = off_in; a.listed = L > 0 ? listed : nullptr; a.L = a.listed != nullptr ? L : 0;
     a.drop = listed_mode; a.id_lo = id_lo; a.B = B; a.V = V; a.d = d; a.K = K;
+    a.bias = bias; a.ld_bias = ld_bias; a.group = group; a.G = G;
     const int R = pick_ranges(B, V);
     a.items_per_range = cdiv(cdiv(V, R), CHUNK) * CHUNK;
     const int Ract = cdiv(V, a.items_per_range);
@@ -322,4 +360,12 @@ extern "C" int srec_score_select(const float* sr, int ld_sr, long comp_stride, c
         case 3: return run<3>(a, Ract, out_val, out_idx, st);
         default: return run<4>(a, Ract, out_val, out_idx, st);
     }
+}
+
+extern "C" int srec_score_select(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                 const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                                 long id_lo, int B, int V, int d, int C, int K, float* out_val, int* out_idx, void* ws,
+                                 void* stream) {
+    return srec_score_select_biased(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d,
+                                    C, K, nullptr, 0, nullptr, 1, out_val, out_idx, ws, stream);
 }

@@ -22,6 +22,11 @@
 //     lane exchanges (the U C exchanges of a stage are independent of each other), so the order of the sum depends on
 //     (d, C) alone - never on M, the slot, the shard or the view.
 // No atomics, no workspace, no scratch memory; every out[b,m] is written by exactly one lane.  Sessions run along grid.x.
+//
+// srec_score_items_biased (template parameter BIAS; false: the instances of srec_score_items, unchanged): the owning shard
+// adds bias[group[b], local row] after the mixture.  The lookup sits where thread i resolves slot i: a bias of -INFINITY
+// turns the slot into a padding slot (no row is read for it), any other value goes to a third LDS word per slot that the
+// writing lane adds - no memory instruction joins the hot loop, and a foreign id reads neither the table nor the bias.
 #include "common.h"
 #include "score_tile.h"
 
@@ -46,14 +51,17 @@ struct ItemArgs {
     int B, V, d;
     int logT;                       // a row is read by 1 << logT lanes
     float* out;
+    const float* bias; long ld_bias; // (appended: the unbiased instances read the arguments above where they were)
+    const int* group; int G;
 };
 
-template <int C, int J>
+template <int C, int J, bool BIAS>
 __global__ __launch_bounds__(256) void score_items_kernel(ItemArgs a) {
     constexpr int U = 8 / J;                                        // row groups in flight per wavefront
     __shared__ int lst[MAXL];
     __shared__ int srow[CH];                                        // local row, ROW_PAD or ROW_FOREIGN
     __shared__ int sin[CH];                                         // 1: the slot's item is listed (SCORE mode)
+    __shared__ float sbias[BIAS ? CH : 1];                          // the slot's bias (finite: -INFINITY became ROW_PAD)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
@@ -78,12 +86,16 @@ __global__ __launch_bounds__(256) void score_items_kernel(ItemArgs a) {
     __syncthreads();
 
     const int* ids = a.items + (size_t)b * a.ld_items;
+    // this session's bias row; a group id outside [0, G) is the caller's error and is held inside the operand
+    const float* brow = nullptr;
+    if constexpr (BIAS) brow = a.bias + (a.group != nullptr ? (size_t)min(max(a.group[b], 0), a.G - 1) * a.ld_bias : 0);
     float* orow = a.out + (size_t)b * M;
     const int nchunk = (M + CH - 1) / CH;
     for (int chunk = blockIdx.y; chunk < nchunk; chunk += gridDim.y) {
         const int m0 = chunk * CH, n = min(CH, M - m0);
         {
             int row = ROW_PAD, in = 0;
+            float bv = 0.f;
             if (tid < n) {
                 const long id = ids[m0 + tid];
                 const long lr = id - a.id_lo;
@@ -93,11 +105,18 @@ __global__ __launch_bounds__(256) void score_items_kernel(ItemArgs a) {
                     } else {
                         for (int i = 0; i < L; ++i) in |= (int)((long)lst[i] == id);
                         row = (in && a.drop) ? ROW_PAD : (int)lr;
+                        if constexpr (BIAS) {
+                            if (row >= 0) {
+                                bv = brow[lr];
+                                if (bv == -INFINITY) row = ROW_PAD;
+                            }
+                        }
                     }
                 }
             }
             srow[tid] = row;
             sin[tid] = in;
+            if constexpr (BIAS) sbias[tid] = bv;
         }
         __syncthreads();
 
@@ -153,6 +172,7 @@ __global__ __launch_bounds__(256) void score_items_kernel(ItemArgs a) {
 #pragma unroll
                         for (int c = 0; c < C; ++c) z[c] = csv[u] * p[u][c] + (in ? oin[c] : oex[c]);
                         v = mix<C>(z);
+                        if constexpr (BIAS) v += sbias[sl];
                     } else {
                         v = row[u] == ROW_PAD ? -INFINITY : 0.f;
                     }
@@ -167,7 +187,9 @@ __global__ __launch_bounds__(256) void score_items_kernel(ItemArgs a) {
 template <int C, int J>
 int launch(const ItemArgs& a, hipStream_t st) {
     const int nchunk = cdiv(a.M, CH);
-    hipLaunchKernelGGL((score_items_kernel<C, J>), dim3(a.B, nchunk < 65535 ? nchunk : 65535), dim3(256), 0, st, a);
+    const dim3 grid(a.B, nchunk < 65535 ? nchunk : 65535);
+    if (a.bias == nullptr) hipLaunchKernelGGL((score_items_kernel<C, J, false>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((score_items_kernel<C, J, true>), grid, dim3(256), 0, st, a);
     SREC_LAUNCH_CHECK();
     return 0;
 }
@@ -181,11 +203,14 @@ int run(const ItemArgs& a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int srec_score_items(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                const int* items, long ld_items, int M, long id_lo, int B, int V, int d, int C, float* out,
-                                void* stream) {
+extern "C" int srec_score_items_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                       const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                                       const int* items, long ld_items, int M, long id_lo, int B, int V, int d, int C,
+                                       const float* bias, long ld_bias, const int* group, int G, float* out, void* stream) {
     if (B <= 0) return 0;
+    if (G < 1 || (group == nullptr && G > 1) || (bias != nullptr && G > 1 && ld_bias < (long)V) || ((uintptr_t)bias & 3) ||
+        ((uintptr_t)group & 3))
+        return SREC_BAD_ARG;
     if (V <= 0 || d <= 0 || (d & 3) || d > 1024 || C < 1 || C > MAXCOMP || L < 0 || L > MAXL || M < 1 || (ld_sr & 3) ||
         (ld_e & 3) || (comp_stride & 3) || ld_sr < d || ld_e < d || ((uintptr_t)E & 15) || ((uintptr_t)sr & 15) ||
         ((uintptr_t)items & 3) || ((uintptr_t)out & 3) || items == nullptr || out == nullptr || id_lo < 0 ||
@@ -196,6 +221,7 @@ extern "C" int srec_score_items(const float* sr, int ld_sr, long comp_stride, co
     a.off_ex = off_ex; a.off_in = listed_mode == 1 ? nullptr : off_in;
     a.listed = L > 0 ? listed : nullptr; a.L = a.listed != nullptr ? L : 0; a.drop = listed_mode;
     a.items = items; a.ld_items = ld_items; a.M = M; a.id_lo = id_lo; a.B = B; a.V = V; a.d = d; a.out = out;
+    a.bias = bias; a.ld_bias = ld_bias; a.group = G > 1 ? group : nullptr; a.G = G;
     while ((4 << a.logT) < d && a.logT < 6) ++a.logT;               // the smallest power of two of lanes that covers a row
     hipStream_t st = (hipStream_t)stream;
     switch (C) {
@@ -204,4 +230,12 @@ extern "C" int srec_score_items(const float* sr, int ld_sr, long comp_stride, co
         case 3: return run<3>(a, st);
         default: return run<4>(a, st);
     }
+}
+
+extern "C" int srec_score_items(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                                const int* items, long ld_items, int M, long id_lo, int B, int V, int d, int C, float* out,
+                                void* stream) {
+    return srec_score_items_biased(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, items, ld_items,
+                                   M, id_lo, B, V, d, C, nullptr, 0, nullptr, 1, out, stream);
 }

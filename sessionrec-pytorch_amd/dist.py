@@ -404,13 +404,15 @@ class HipLocal:
         """this shard's share of (rank, target) of ops.score_rank: rows [id_lo, id_lo + n) of the catalog"""
         return self.ops.score_rank(srs, table, cs, labels, off_ex, off_in, listed, id_lo, target, target_only)
 
-    def select(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo):
-        """this shard's k best rows (values, global ids) of ops.score_select: rows [id_lo, id_lo + n) of the catalog"""
-        return self.ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo)
+    def select(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, **bias):
+        """this shard's k best rows (values, global ids) of ops.score_select: rows [id_lo, id_lo + n) of the catalog.
+        bias: `bias=` (this shard's columns) and `group=` of ops.score_select, only when there is a bias"""
+        return self.ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
-    def score_items(self, srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo):
-        """this shard's share of ops.score_items: rows [id_lo, id_lo + n) of the catalog score, every other id gives 0"""
-        return self.ops.score_items(srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo)
+    def score_items(self, srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo, **bias):
+        """this shard's share of ops.score_items: rows [id_lo, id_lo + n) of the catalog score, every other id gives 0.
+        bias: as in select()"""
+        return self.ops.score_items(srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
@@ -825,12 +827,25 @@ class VocabParallel:
             rank = rank[self.rank * n_loc:(self.rank + 1) * n_loc]
         return rank
 
-    def select(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False):
+    def _bias_cols(self, bias, group, data_parallel):
+        """the keywords the local select / score_items take for a bias over GLOBAL ids ([V] or [G, V], the same on every
+        rank): this rank's columns [lo, lo + n_live) as a view (the row stride stays the full one), and the sessions' group
+        ids - all-gathered with the sessions under data_parallel.  No bias: no keywords, the call is what it was."""
+        if bias is None:
+            return {}
+        if data_parallel and group is not None:
+            group = all_gather_cat(group.reshape(-1).to(torch.int32).contiguous(), self.group)
+        return dict(bias=bias[..., self.lo:self.lo + self.n_live], group=group)
+
+    def select(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
+               bias=None, group=None):
         """the k best items of every session over the sharded table (ops.score_select's contract; srs: list of C [B, d]
         session vectors, off_ex / off_in [C, B], listed [B, L] global ids): every rank selects among its own LIVE rows with
         its id_lo (padding rows are never scored), ONE all-gather carries the (value, id) pairs of all ranks, and the lists
-        are merged by (value descending, id ascending) - the order of one device.  data_parallel as in topk()."""
+        are merged by (value descending, id ascending) - the order of one device.  data_parallel as in topk().  bias ([V] or
+        [G, V] over GLOBAL ids, the same on every rank) / group ([B] of this rank's sessions): ops.score_select's."""
         n_loc = srs[0].shape[0]
+        bkw = self._bias_cols(bias, group, data_parallel)
         if data_parallel:
             srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
             gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
@@ -845,7 +860,7 @@ class VocabParallel:
         B, dev = srs[0].shape[0], srs[0].device
         if self.n_live > 0:
             csl = None if cs is None else cs[:self.n_live]
-            val, idx = self.local.select(srs, table[:self.n_live], csl, k, off_ex, off_in, listed, drop_listed, self.lo)
+            val, idx = self.local.select(srs, table[:self.n_live], csl, k, off_ex, off_in, listed, drop_listed, self.lo, **bkw)
         else:
             val = torch.full((B, k), float('-inf'), device=dev)
             idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
@@ -864,14 +879,17 @@ class VocabParallel:
             val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
         return val, idx
 
-    def score_items(self, srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False):
+    def score_items(self, srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
+                    bias=None, group=None):
         """the scores of given items over the sharded table (ops.score_items' contract; srs: list of C [B, d] session
         vectors, off_ex / off_in [C, B], listed [B, L] global ids, items [B, M] or [M] global ids): every rank scores the ids
         among its own LIVE rows with its id_lo (padding rows are never owners) and gives 0 for the others, -inf for padding
         slots and dropped items - ONE sum-all-reduce of [B, M] floats finishes it.  data_parallel as in select(): every rank
         passes its own B / world sessions (and their [B / world, M] items; a 1-D list is the same on every rank) and gets its
-        own sessions' scores."""
+        own sessions' scores.  bias / group as in select(): the owner of an id adds its bias, so the sum is still one device's
+        (the bias holds no +inf: the model-level entry points check it)."""
         n_loc = srs[0].shape[0]
+        bkw = self._bias_cols(bias, group, data_parallel)
         if data_parallel:
             srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
             gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
@@ -888,7 +906,7 @@ class VocabParallel:
         B = srs[0].shape[0]
         if self.n_live > 0:
             csl = None if cs is None else cs[:self.n_live]
-            out = self.local.score_items(srs, table[:self.n_live], csl, items, off_ex, off_in, listed, drop_listed, self.lo)
+            out = self.local.score_items(srs, table[:self.n_live], csl, items, off_ex, off_in, listed, drop_listed, self.lo, **bkw)
         else:                                # a rank without live rows owns nothing
             out = torch.zeros(B, items.shape[-1], device=srs[0].device, dtype=torch.float32)
         all_reduce_sum(out, self.group)      # (-inf + 0 and -inf + -inf stay -inf: no slot is ever +inf)

@@ -596,12 +596,13 @@ class MSGIFSR(_ScoringMixin, nn.Module):
                 off_ex.append(la[c] - lse)
         return srs, cs, torch.stack(off_ex, 0), torch.stack(off_in, 0) if self.extra else None, listed
 
-    def _recommend(self, *inputs, k, exclude_seen):
+    def _recommend(self, *inputs, k, exclude_seen, **bias):
         """the mixture of target_rank: forward()'s log scores WITHOUT its (B, V) matrices (one per order, plus the
         in-session mask).  With `extra` the session's own items are `listed` and score through the repeat branch (off_in);
-        exclude_seen drops them instead, so only the explore branch (off_ex) matters."""
+        exclude_seen drops them instead, so only the explore branch (off_ex) matters.  bias (item_bias / item_group) is added
+        AFTER the mixture, by the kernel."""
         if not (self.extra or (self.fusion and self.order > 1)):
-            return super()._recommend(*inputs, k=k, exclude_seen=exclude_seen)
+            return super()._recommend(*inputs, k=k, exclude_seen=exclude_seen, **bias)
         (mg,) = inputs
         srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg)
         if self.extra or exclude_seen:
@@ -609,20 +610,20 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             listed = self._session_items(mg)
         if exclude_seen:
             off_in = None
-        return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen)
+        return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, **bias)
 
-    def _score_items(self, *inputs, items, exclude_seen):
+    def _score_items(self, *inputs, items, exclude_seen, **bias):
         """the mixture of _recommend at given items: with `extra` the session's own items are `listed` and score through the
         repeat branch (off_in); exclude_seen gives them -inf instead"""
         if not (self.extra or (self.fusion and self.order > 1)):
-            return super()._score_items(*inputs, items=items, exclude_seen=exclude_seen)
+            return super()._score_items(*inputs, items=items, exclude_seen=exclude_seen, **bias)
         (mg,) = inputs
         srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg)
         if self.extra or exclude_seen:
             listed = self._session_items(mg)
         if exclude_seen:
             off_in = None
-        return self._items_of(srs, cs, items, off_ex, off_in, listed, exclude_seen)
+        return self._items_of(srs, cs, items, off_ex, off_in, listed, exclude_seen, **bias)
 
     def forward(self, mg):
         sr = self.session_repr(mg)

@@ -304,6 +304,82 @@ def _mixture_args(who, srs, table, off_ex, off_in, listed):
     return MixtureArgs(srs, ld_sr, comp, C, B, d, table, table.shape[0], offs(off_ex), offs(off_in), listed, L)
 
 
+# the per-item bias of score_select / score_items: bias fp32 [V] or [G, V] with unit column stride (None = no bias), its row
+# stride, group int32 [B] or None, G rows
+BiasArgs = namedtuple('BiasArgs', 'bias ld_bias group G')
+_NO_BIAS = BiasArgs(None, 0, None, 1)
+
+
+def _bias_args(who, bias, group, B, V):
+    """The per-item bias of score_select and score_items as one BiasArgs.  bias: floating [V] (one row for all sessions) or
+    [G, V] with group [B] integer row ids in [0, G) (a [1, V] bias needs none); None = no bias.  A tensor with unit column
+    stride is taken as it is, whatever its row stride (a column slice of a wider tensor: a row shard of the catalogue);
+    anything else is made contiguous fp32.  A wrong last dimension, more than 2 dimensions, a non-floating dtype, `group`
+    without a 2-D bias or missing with G > 1, and a `group` that does not have B integer entries raise ValueError in the
+    words of `who`.  The VALUES are not looked at (NaN, +inf and group ids out of range are the caller's to exclude: the
+    model-level entry points check them).  Pure torch (no launch, no library call): it checks CPU tensors as well."""
+    if bias is None:
+        if group is not None:
+            raise ValueError('%s: group is given without a bias' % who)
+        return _NO_BIAS
+    bias = bias.detach()
+    if not bias.is_floating_point():
+        raise ValueError('%s: bias must be a floating tensor, got %s' % (who, bias.dtype))
+    if bias.dim() not in (1, 2):
+        raise ValueError('%s: bias must be [V] or [G, V], got %d dimensions' % (who, bias.dim()))
+    if bias.shape[-1] != V:
+        raise ValueError('%s: bias has %d columns for %d table rows' % (who, bias.shape[-1], V))
+    if bias.dim() == 1 and group is not None:
+        raise ValueError('%s: group needs a 2-D bias [G, V], got [V]' % who)
+    G = bias.shape[0] if bias.dim() == 2 else 1
+    if G < 1:
+        raise ValueError('%s: bias has no rows' % who)
+    if G > 1 and group is None:
+        raise ValueError('%s: a bias of %d rows needs group, one row id per session' % (who, G))
+    if group is not None:
+        group = group.detach()
+        if group.is_floating_point() or group.is_complex() or group.dtype == torch.bool or group.numel() != B:
+            raise ValueError('%s: group must hold %d integer row ids (one per session), got %s %s'
+                             % (who, B, group.dtype, tuple(group.shape)))
+        group = group.to(torch.int32).reshape(B).contiguous()
+    if bias.dtype != torch.float32 or bias.stride(-1) != 1 or (bias.dim() == 2 and G > 1 and bias.stride(0) < V):
+        bias = bias.to(torch.float32).contiguous()
+    return BiasArgs(bias, bias.stride(0) if bias.dim() == 2 else V, group if G > 1 else None, G)
+
+
+def catalog_bias(num_items, allow=None, deny=None, boost=None, device=None):
+    """fp32 [num_items], the `bias` of score_select / score_items and the `item_bias` of the models' recommend / score_items /
+    rerank, from the usual catalogue controls: allow (ids) - -inf everywhere EXCEPT these; deny (ids) - -inf on these; boost
+    ((ids, values)) - added on top (an id named twice: its values add up); a boost on a filtered item stays -inf.  Ids are
+    sequences or integer tensors; an id outside [0, num_items) raises ValueError.  Pure torch."""
+    def ids_of(x, what):
+        x = torch.as_tensor(x, device=device).reshape(-1)
+        if x.numel() and (x.is_floating_point() or x.dtype == torch.bool):
+            raise ValueError('catalog_bias: %s ids must be integers, got %s' % (what, x.dtype))
+        x = x.long()
+        if x.numel():
+            lo, hi = (int(v) for v in torch.aminmax(x))
+            if lo < 0 or hi >= num_items:
+                raise ValueError('catalog_bias: %s id %d; ids are in [0, %d)' % (what, lo if lo < 0 else hi, num_items))
+        return x
+    ninf = float('-inf')
+    if allow is not None:
+        out = torch.full((num_items,), ninf, dtype=torch.float32, device=device)
+        out[ids_of(allow, 'allow')] = 0.0
+    else:
+        out = torch.zeros(num_items, dtype=torch.float32, device=device)
+    if deny is not None:
+        out[ids_of(deny, 'deny')] = ninf
+    if boost is not None:
+        ids, vals = boost
+        ids = ids_of(ids, 'boost')
+        vals = torch.as_tensor(vals, dtype=torch.float32, device=device).reshape(-1)
+        if vals.numel() != ids.numel():
+            raise ValueError('catalog_bias: boost has %d ids and %d values' % (ids.numel(), vals.numel()))
+        out.index_add_(0, ids, vals)
+    return out
+
+
 def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id_lo=0, target=None, target_only=False):
     """(rank int32 [B], target fp32 [B]): the number of rows of `table` that score ahead of each session's label under
     s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) (off_in for the items of listed[b,:], off_ex elsewhere; ties
@@ -332,18 +408,23 @@ def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id
     return rank, target
 
 
-def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0):
+def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None):
     """(values fp32 [B,k] descending, item ids int32 [B,k]): the k best rows of `table` per session under the score of
     score_rank, s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) - no (B, V) tensor, k <= 128 (csrc/recommend.hip).
     Argument conventions as score_rank: srs [B, d], [C, B, d] or a list of C [B, d] tensors, C <= 4; off_ex / off_in [C, B]
     or None (= 0); listed [B, L] global item ids, -1 = empty slot; id_lo: global id of table row 0 (a row shard).
     drop_listed=False: listed items score with off_in; True: listed items are never returned (off_in is ignored).  Ties go
-    towards the lower id; a session with fewer than k eligible rows ends in (-inf, -1) slots."""
+    towards the lower id; a session with fewer than k eligible rows ends in (-inf, -1) slots.
+    bias: fp32 [V] or [G, V] aligned with the rows of `table` (group: [B] row ids in [0, G)), added AFTER the mixture -
+    s + bias[group[b], v]; -inf = the item is not in the catalogue for this call and is never returned, the order and the
+    values are those of the biased score (_bias_args; no NaN, no +inf, no group id out of range: not checked here).  Without a
+    bias the call and its result are what they were."""
     k = int(k)
     if k < 1 or k > CONST['SREC_SELECT_MAXK']:
         raise ValueError('score_select: k = %d; the selection kernel of csrc/recommend.hip keeps between 1 and %d items per '
                          'session' % (k, CONST['SREC_SELECT_MAXK']))
     a = _mixture_args('score_select', srs, table, off_ex, None if drop_listed else off_in, listed)
+    bi = _bias_args('score_select', bias, group, a.B, a.V)
     B, dev = a.B, a.srs.device
     val = torch.empty(B, k, device=dev, dtype=torch.float32)
     idx = torch.empty(B, k, device=dev, dtype=torch.int32)
@@ -353,12 +434,18 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     lib.srec_score_select_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
     ws = _byte_ws('select', dev, n.value)
     mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
-    lib.srec_score_select(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                          ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, k, ptr(val), ptr(idx), ptr(ws), stream())
+    if bi.bias is None:
+        lib.srec_score_select(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
+                              ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, k, ptr(val), ptr(idx), ptr(ws), stream())
+    else:
+        lib.srec_score_select_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
+                                     ptr(a.off_in), ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias),
+                                     bi.ld_bias, ptr(bi.group), bi.G, ptr(val), ptr(idx), ptr(ws), stream())
     return val, idx
 
 
-def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, checked=False):
+def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, checked=False,
+                bias=None, group=None):
     """fp32 [B, M]: the score of score_rank / score_select, s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]), at the
     given items of every session - no (B, V) tensor, no limit on M (csrc/score_items.hip: one gather pass, the session
     vectors in registers).  items: [B, M] global ids per session or [M] shared by all sessions, any integer dtype; -1 is
@@ -369,11 +456,14 @@ def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, dr
     add up.  An id < -1 raises ValueError before any launch (one device-to-host read of the smallest id; checked=True: the
     caller has looked already); an upper bound cannot be checked here - a shard sees only its own range - the model-level
     entry (model.score_items) checks it.
+    bias / group as in score_select: the rows' owner adds bias[group[b], row] after the mixture and -inf stays -inf; a padding
+    slot still gives -inf and a foreign id 0.0 without a read of the table or of the bias, so shards still add up.
     Measured at B 512, V 37 484, d 256 (profiles/score_items_timing.txt): with the lse pass a single
     soft-max needs ahead of it, this route beats score_logp(...).gather(1, items) up to M = 2000 (342 against 352 us) and
     loses at M = 4000 (462 against 370 us) - for lists of several thousand items per session materialise instead; a C = 3
     mixture stays 2.6x ahead of forward().gather at M = 4000."""
     a = _mixture_args('score_items', srs, table, off_ex, None if drop_listed else off_in, listed)
+    bi = _bias_args('score_items', bias, group, a.B, a.V)
     B, dev = a.B, a.srs.device
     items = items.detach()
     if items.is_floating_point() or items.is_complex() or items.dtype == torch.bool or items.dim() not in (1, 2):
@@ -388,9 +478,15 @@ def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, dr
         raise ValueError('score_items: item id %d; ids are >= 0, or -1 for a padding slot' % int(items.min()))
     items = items.to(torch.int32).contiguous()
     mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
-    lib.srec_score_items(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                         ptr(a.listed), a.L, mode, ptr(items), M if items.dim() == 2 else 0, M, int(id_lo), B, a.V, a.d, a.C,
-                         ptr(out), stream())
+    if bi.bias is None:
+        lib.srec_score_items(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
+                             ptr(a.listed), a.L, mode, ptr(items), M if items.dim() == 2 else 0, M, int(id_lo), B, a.V, a.d, a.C,
+                             ptr(out), stream())
+    else:
+        lib.srec_score_items_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
+                                    ptr(a.off_in), ptr(a.listed), a.L, mode, ptr(items), M if items.dim() == 2 else 0, M,
+                                    int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, ptr(out),
+                                    stream())
     return out
 
 

@@ -220,28 +220,72 @@ class _ScoringMixin:
             rank = torch.where(labels >= 0, rank.clamp(min=0), rank)
         return rank
 
-    def recommend(self, *inputs, k=20, exclude_seen=False):
+    def _item_bias(self, who, item_bias, item_group):
+        """the keywords ops.score_select / ops.score_items (and the sharded routes) take for item_bias / item_group - none at
+        all without a bias, so the call is then what it was.  Checked here, before anything of the model runs: the shape
+        ([num_items] or [G, num_items], floating; item_group integer, only with a 2-D bias and needed for G > 1), and the
+        VALUES the kernels assume - no NaN, no +inf (the all-reduce of the sharded score_items relies on "no slot is ever
+        +inf"), every group id in [0, G) - at the price of ONE device-to-host read of two flags behind a pass over the bias:
+        measured at V 37 484, 74 us per call for [V] and 88 us for [4, V] with 512 group ids, beside 0.46-1.7 ms for the
+        selection itself (profiles/item_bias_timing.md)."""
+        if item_bias is None:
+            if item_group is not None:
+                raise ValueError('%s: item_group is given without an item_bias' % who)
+            return {}
+        n = self.shard.V if self.shard is not None else self._table().shape[0]
+        dev = self._table().device
+        b = item_bias.detach()
+        if not b.is_floating_point() or b.dim() not in (1, 2) or b.shape[-1] != n:
+            raise ValueError('%s: item_bias must be a floating tensor [%d] or [G, %d] (one entry per catalogue item), got %s %s'
+                             % (who, n, n, b.dtype, tuple(b.shape)))
+        G = b.shape[0] if b.dim() == 2 else 1
+        if G < 1 or (item_group is None and G > 1) or (item_group is not None and b.dim() != 2):
+            raise ValueError('%s: item_group (one row id per session) goes with an item_bias [G, %d], and G > 1 needs it; got '
+                             'item_bias %s, item_group %s' % (who, n, tuple(b.shape), 'None' if item_group is None else 'given'))
+        b = b.to(dev)
+        flags = [(torch.isnan(b) | (b == float('inf'))).any()]
+        g = None
+        if item_group is not None:
+            g = item_group.detach()
+            if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+                raise ValueError('%s: item_group must be an integer tensor, got %s' % (who, g.dtype))
+            g = g.to(dev).reshape(-1)
+            flags.append(((g < 0) | (g >= G)).any())
+        bad = torch.stack(flags).tolist()                   # the one device-to-host read
+        if bad[0]:
+            raise ValueError('%s: item_bias holds NaN or +inf; values are finite, or -inf for an item outside the catalogue' % who)
+        if len(bad) > 1 and bad[1]:
+            raise ValueError('%s: item_group holds a row id outside [0, %d)' % (who, G))
+        return dict(bias=b, group=g)
+
+    def recommend(self, *inputs, k=20, exclude_seen=False, item_bias=None, item_group=None):
         """(log_probs fp32 [B,k] descending, item_ids int32 [B,k]): the k most probable next items of every session, k <= 128.
         The values are the numbers forward() returns at those items (log-probabilities); ties go towards the lower item
         id.  One fused selection pass over the table (csrc/recommend.hip): no (B, V) score matrix, sharded table included.
         exclude_seen=True never returns an item of the session itself (at most 64 distinct items per session); the remaining
         items keep forward()'s log-probabilities - there is NO renormalisation over the remaining items.  A session with
-        fewer than k eligible items ends in (-inf, -1) slots.  Runs in eval mode under torch.no_grad()."""
+        fewer than k eligible items ends in (-inf, -1) slots.  Runs in eval mode under torch.no_grad().
+        item_bias: fp32 [num_items], or [G, num_items] with item_group [B] row ids in [0, G) (sessions of several markets in
+        one batch), over GLOBAL item ids (ops.catalog_bias builds one from allow / deny / boost lists).  The values are then
+        forward()'s log-probabilities PLUS the bias, ordered by that sum; an item whose bias is -inf is never returned.  As
+        with exclude_seen there is NO renormalisation over the allowed items.  A wrong length, NaN or +inf in the bias and
+        a group id outside [0, G) raise ValueError before anything is launched (_item_bias: one device-to-host read)."""
+        bias = self._item_bias('recommend', item_bias, item_group)
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad():
-                return self._recommend(*inputs, k=k, exclude_seen=exclude_seen)
+                return self._recommend(*inputs, k=k, exclude_seen=exclude_seen, **bias)
         finally:
             self.train(was_training)
 
-    def _recommend(self, *inputs, k, exclude_seen):
+    def _recommend(self, *inputs, k, exclude_seen, **bias):
         sr = self.session_repr(*inputs)
         st = self._state(sr.shape[0])
         cs, inv_scale = self._col_scale(st)
         off_ex = -self._lse(sr, cs, inv_scale, st).unsqueeze(0)      # log softmax = z - lse
         listed = self._session_items(inputs[0]) if exclude_seen else None
-        return self._select_of([sr], cs, k, off_ex, None, listed, exclude_seen)
+        return self._select_of([sr], cs, k, off_ex, None, listed, exclude_seen, **bias)
 
     def _lse(self, sr, cs, inv_scale, st, labels=None):
         """log-sum-exp of every session's logits over the whole catalog: the fused statistics pass (no gradient kept)"""
@@ -264,19 +308,23 @@ class _ScoringMixin:
         items = iid[pos.clamp(max=iid.numel() - 1)]
         return torch.where(pos < seg[1:, None], items, torch.full_like(items, -1)).to(torch.int32)
 
-    def _select_of(self, srs, cs, k, off_ex, off_in, listed, drop_listed):
+    def _select_of(self, srs, cs, k, off_ex, off_in, listed, drop_listed, **bias):
+        """bias: `bias=` / `group=` over global ids (_item_bias), added after the mixture"""
         if self.shard is not None:       # every shard selects among its rows: one all-gather of [B, k] pairs, one merge
             return self.shard.select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed,
-                                     data_parallel=self.shard.eval_data_parallel)
-        return ops.score_select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed)
+                                     data_parallel=self.shard.eval_data_parallel, **bias)
+        return ops.score_select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, **bias)
 
-    def score_items(self, *inputs, items, exclude_seen=False):
+    def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None):
         """fp32 [B, M]: the log-probability forward() returns at the given items of every session - full-catalog soft-max
         (or mixture), NO renormalisation over the candidates.  items: [B, M] item ids per session or [M] shared by all
         sessions, any integer dtype, any M; -1 is padding and gives -inf; duplicates are allowed.  exclude_seen=True gives
         -inf at the session's own items (at most 64 distinct items per session) and leaves the rest unchanged.  An id
         < -1 or >= num_items raises ValueError before anything is launched.  One gather pass over the candidates' rows
-        (csrc/score_items.hip): no (B, V) score matrix, sharded table included.  Runs in eval mode under torch.no_grad()."""
+        (csrc/score_items.hip): no (B, V) score matrix, sharded table included.  Runs in eval mode under torch.no_grad().
+        item_bias / item_group as in recommend(): the values are forward()'s log-probabilities PLUS the bias (-inf stays
+        -inf), NO renormalisation; checked before anything is launched (_item_bias: one more device-to-host read)."""
+        bias = self._item_bias('score_items', item_bias, item_group)
         n = self.shard.V if self.shard is not None else self._table().shape[0]
         if items.numel() > 0:
             lo, hi = (int(x) for x in torch.aminmax(items.detach()))
@@ -286,31 +334,32 @@ class _ScoringMixin:
         self.eval()
         try:
             with torch.no_grad():
-                return self._score_items(*inputs, items=items, exclude_seen=exclude_seen)
+                return self._score_items(*inputs, items=items, exclude_seen=exclude_seen, **bias)
         finally:
             self.train(was_training)
 
-    def _score_items(self, *inputs, items, exclude_seen):
+    def _score_items(self, *inputs, items, exclude_seen, **bias):
         sr = self.session_repr(*inputs)
         st = self._state(sr.shape[0])
         cs, inv_scale = self._col_scale(st)
         off_ex = -self._lse(sr, cs, inv_scale, st).unsqueeze(0)      # log softmax = z - lse
         listed = self._session_items(inputs[0]) if exclude_seen else None
-        return self._items_of([sr], cs, items, off_ex, None, listed, exclude_seen)
+        return self._items_of([sr], cs, items, off_ex, None, listed, exclude_seen, **bias)
 
-    def _items_of(self, srs, cs, items, off_ex, off_in, listed, drop_listed):
+    def _items_of(self, srs, cs, items, off_ex, off_in, listed, drop_listed, **bias):
         items = items.to(srs[0].device)
         if self.shard is not None:       # every shard scores the ids it owns, the others give 0: one all-reduce of [B, M] floats
             return self.shard.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed,
-                                          data_parallel=self.shard.eval_data_parallel)
-        return ops.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed, checked=True)
+                                          data_parallel=self.shard.eval_data_parallel, **bias)
+        return ops.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed, checked=True, **bias)
 
-    def rerank(self, *inputs, items, k=None, exclude_seen=False):
+    def rerank(self, *inputs, items, k=None, exclude_seen=False, item_bias=None, item_group=None):
         """(log_probs fp32 [B, n], item_ids int32 [B, n]), n = M or min(k, M): the candidates of score_items ordered by
         (value descending, id ascending) - the contract of recommend()'s lists without its limit of 128.  Slots that score
-        -inf (padding, and the session's own items under exclude_seen) come last with id -1; a candidate named twice is
-        returned twice."""
-        val = self.score_items(*inputs, items=items, exclude_seen=exclude_seen)
+        -inf (padding, the session's own items under exclude_seen, and items whose item_bias is -inf) come last with id -1; a
+        candidate named twice is returned twice.  item_bias / item_group as in score_items(): ordered by log-probability PLUS
+        bias."""
+        val = self.score_items(*inputs, items=items, exclude_seen=exclude_seen, item_bias=item_bias, item_group=item_group)
         ids = items.to(val.device).to(torch.int64)
         ids = torch.where(val == float('-inf'), torch.full_like(val, -1, dtype=torch.int64), ids.expand_as(val))
         # two stable sorts, as the merge of dist.VocabParallel.select: by id (unfilled slots last), then by value

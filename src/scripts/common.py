@@ -51,6 +51,79 @@ def variant_flags(p, model):
         p.add_argument('--fusion', action='store_true', help='whether use IFR.')
 
 
+def catalog_flags(p):
+    """the catalogue controls of scripts/recommend.py and scripts/rerank.py (ops.catalog_bias combines them)"""
+    p.add_argument('--allow', default=None, metavar='FILE', help='only these items may be returned: one item id per line')
+    p.add_argument('--deny', default=None, metavar='FILE', help='these items are never returned: one item id per line')
+    p.add_argument('--item-bias', default=None, metavar='FILE',
+                   help='added to the log-probabilities before ranking: one `id:value` or `id<TAB>value` per line, unnamed items get 0')
+
+
+def read_id_file(path):
+    """[item id, ...]: one id per non-empty line; ValueError names the line that is none"""
+    out = []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            line = line.strip()
+            if line:
+                try:
+                    out.append(int(line))
+                except ValueError:
+                    raise ValueError('%s line %d: `%s` is no item id' % (path, n, line)) from None
+    return out
+
+
+def read_bias_file(path):
+    """([item id, ...], [value, ...]): one `id:value` or `id<TAB>value` per non-empty line; ValueError names the line that is
+    malformed or whose value is not finite"""
+    import math
+    ids, vals = [], []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            line = line.strip()
+            if not line:
+                continue
+            parts = line.split('\t') if '\t' in line else line.split(':')
+            try:
+                if len(parts) != 2:
+                    raise ValueError
+                i, v = int(parts[0]), float(parts[1])
+            except ValueError:
+                raise ValueError('%s line %d: `%s` is not `id:value` or `id<TAB>value`' % (path, n, line)) from None
+            if not math.isfinite(v):
+                raise ValueError('%s line %d: the value of item %d is not finite (use --deny to remove an item)' % (path, n, i))
+            ids.append(i)
+            vals.append(v)
+    return ids, vals
+
+
+def read_catalog(p, args):
+    """the keywords of ops.catalog_bias from --allow / --deny / --item-bias, or None when none is given.  Read and checked
+    against <dataset-dir>/num_items.txt before any model is built; p.error() for a file that cannot be read, an id outside the
+    catalogue, a value that is not finite and an --allow that names nothing."""
+    if args.allow is None and args.deny is None and args.item_bias is None:
+        return None
+    kw = {}
+    try:
+        with open(Path(args.dataset_dir) / 'num_items.txt') as f:
+            num_items = int(f.readline())
+        if args.allow is not None:
+            kw['allow'] = read_id_file(args.allow)
+            if not kw['allow']:
+                p.error('--allow %s names no item: nothing could be returned' % args.allow)
+        if args.deny is not None:
+            kw['deny'] = read_id_file(args.deny)
+        if args.item_bias is not None:
+            kw['boost'] = read_bias_file(args.item_bias)
+    except (OSError, ValueError) as e:
+        p.error(str(e))
+    for flag, ids in (('--allow', kw.get('allow', [])), ('--deny', kw.get('deny', [])), ('--item-bias', kw.get('boost', ([], []))[0])):
+        bad = [i for i in ids if not 0 <= i < num_items]
+        if bad:
+            p.error('%s: item id %d; ids are in [0, %d)' % (flag, bad[0], num_items))
+    return kw
+
+
 def build_model(model_name, args, num_items, device, caps=None):
     """(model on the CPU, evaluation collate_fn, training collate_fn) of a launcher's flags (run, scripts/recommend.py)"""
     from src.models import LESSR, MSGIFSR, NISER, SRGNN

@@ -6,11 +6,13 @@
 flags must be those of the training run.  --sessions holds one session per line in the format of datasets/*/test.txt
 (item ids separated by commas); the WHOLE line is the prefix whose next item is wanted.  Output: one line per input
 session, in input order - `id:logprob` pairs separated by tabs, best first (model.recommend: one fused selection pass over
-the item table, no (B, V) score matrix)."""
+the item table, no (B, V) score matrix).  --allow FILE / --deny FILE (one item id per line) restrict the catalogue for this
+run and --item-bias FILE (`id:value` or `id<TAB>value` per line) is added to the log-probabilities before ranking; the printed
+values are then log-probability + bias (ops.catalog_bias combines the three, the selection kernel applies them)."""
 import argparse
 import sys
 
-from common import DEFAULTS, build_model, model_flags, variant_flags
+from common import DEFAULTS, build_model, catalog_flags, model_flags, read_catalog, variant_flags
 
 MAX_TOP = 128           # SREC_SELECT_MAXK (include/srec.h)
 
@@ -59,6 +61,7 @@ def parser(model):
     p.add_argument('--sessions', required=True, help='one session per line, item ids separated by commas')
     p.add_argument('--top', type=int, default=20, help='items per session (at most %d)' % MAX_TOP)
     p.add_argument('--exclude-seen', action='store_true', help="never recommend an item of the session itself")
+    catalog_flags(p)
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -75,6 +78,7 @@ def parse(argv=None):
         p.error('--top must be between 1 and %d (the selection kernel keeps at most %d items per session)' % (MAX_TOP, MAX_TOP))
     if args.batch_size < 1:
         p.error('--batch-size must be positive')
+    args.catalog = read_catalog(p, args)
     return args
 
 
@@ -96,6 +100,7 @@ def main(argv=None):
     model = model.to(device).eval()
     ops.weights_changed()
     model.table_written()
+    item_bias = None if args.catalog is None else ops.catalog_bias(num_items, device=device, **args.catalog)
 
     sessions = read_session_file(args.sessions)
     cap = session_capacity(ops.limits(), getattr(args, 'order', 1), args.exclude_seen or getattr(args, 'extra', False))
@@ -108,7 +113,8 @@ def main(argv=None):
     try:
         for b in range(0, len(sessions), args.batch_size):
             inputs, _ = collate_fn([(s, 0) for s in sessions[b:b + args.batch_size]])
-            val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen)
+            val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen,
+                                       item_bias=item_bias)
             for ids, vals in zip(idx.cpu().tolist(), val.cpu().tolist()):
                 out.write(format_line(ids, vals) + '\n')
     finally:

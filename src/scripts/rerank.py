@@ -6,11 +6,12 @@
 i on line i, separated by commas (lines may differ in length); a file of ONE line serves every session.  Output: one line
 per input session, in input order - `id:logprob` pairs separated by tabs, best first, in recommend.py's format.  The values
 are the model's full-catalog log-probabilities of the candidates (model.rerank: one gather pass over the candidates' rows,
-no (B, V) score matrix, any number of candidates); candidates that cannot be returned (--exclude-seen) are left out."""
+no (B, V) score matrix, any number of candidates); candidates that cannot be returned (--exclude-seen, --allow / --deny) are left out.  --allow / --deny / --item-bias as in
+recommend.py: the values are then log-probability + bias."""
 import argparse
 import sys
 
-from common import DEFAULTS, build_model, model_flags, variant_flags
+from common import DEFAULTS, build_model, catalog_flags, model_flags, read_catalog, variant_flags
 from recommend import format_line, parse_line, read_session_file, session_capacity  # noqa: F401  (one format, one reader)
 
 
@@ -24,6 +25,7 @@ def parser(model):
     p.add_argument('--candidates', required=True, help='candidate item ids of session i on line i (one line: for every session)')
     p.add_argument('--top', type=int, default=None, help='items per session (default: every candidate)')
     p.add_argument('--exclude-seen', action='store_true', help="never return an item of the session itself")
+    catalog_flags(p)
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -40,6 +42,7 @@ def parse(argv=None):
         p.error('--top must be positive')
     if args.batch_size < 1:
         p.error('--batch-size must be positive')
+    args.catalog = read_catalog(p, args)
     return args
 
 
@@ -79,6 +82,7 @@ def main(argv=None):
     model = model.to(device).eval()
     ops.weights_changed()
     model.table_written()
+    item_bias = None if args.catalog is None else ops.catalog_bias(num_items, device=device, **args.catalog)
 
     cap = session_capacity(ops.limits(), getattr(args, 'order', 1), args.exclude_seen or getattr(args, 'extra', False))
     cut = sum(len(s) > cap for s in sessions)
@@ -92,7 +96,7 @@ def main(argv=None):
             inputs, _ = collate_fn([(s, 0) for s in sessions[b:b + args.batch_size]])
             items = th.tensor(pad_candidates(candidates[b:b + args.batch_size]), dtype=th.int64)
             val, idx = model.rerank(*[x.to(device) for x in inputs], items=items.to(device), k=args.top,
-                                    exclude_seen=args.exclude_seen)
+                                    exclude_seen=args.exclude_seen, item_bias=item_bias)
             for ids, vals in zip(idx.cpu().tolist(), val.cpu().tolist()):
                 out.write(format_line(ids, vals) + '\n')
     finally:
