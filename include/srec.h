@@ -561,6 +561,23 @@ int srec_score_items_biased(const float* sr, int ld_sr, long comp_stride, const 
                             int B, int V, int d, int C, const float* bias, long ld_bias,
                             const int* group, int G, float* out, void* stream);
 
+/* ---- serving: the log-normaliser of the served score over the ELIGIBLE catalogue (score_norm.hip) -----------------------
+ * out[b] (fp32 [B]) = logsumexp over the eligible rows v of s'[b,v], the biased score of srec_score_select_biased, with its
+ * layouts, limits (1 <= C <= 4, d % 4 == 0, d <= 1024, L <= 64, ids below 2^31) and eligibility: rows [0, V) of this call
+ * (global ids id_lo + row, a row shard); an item whose bias is -INFINITY does not contribute; SREC_LISTED_SCORE: an item of
+ * listed[b,:] contributes with off_in; SREC_LISTED_DROP: it does not contribute and off_in is ignored.  bias == NULL: no
+ * bias.  A session without an eligible row (or whose eligible rows all score -INFINITY) gives exactly -INFINITY, never NaN.
+ * Subtracting out[b] from off_ex[:, b] and off_in[:, b] renormalises what srec_score_select* / srec_score_items* return:
+ * logsumexp_c(z_c + off_c - Z) = s - Z.  The disjoint row ranges of shards combine by log-sum-exp of their results.
+ * No (B, V) tensor, no float atomics: one (max, sum) pair per (item range, session) in ws, folded in range order - the
+ * output is a pure function of the inputs.  ws: srec_score_norm_ws() bytes.  Nonzero and no launch for the reasons of
+ * srec_score_select_biased. */
+int srec_score_norm_ws(int B, int V, int d, int C, int L, long* bytes);
+int srec_score_norm(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                    const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                    long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
+                    const int* group, int G, float* out, void* ws, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

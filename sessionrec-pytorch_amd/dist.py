@@ -227,6 +227,17 @@ def reduce_scatter_pg(t, pg):
     return h[r * n:(r + 1) * n].clone().to(t.device)
 
 
+def lse_fold(z):
+    """[W, B] -> [B]: log-sum-exp over the rows, folded in row order; a column of -inf gives -inf (never exp(-inf - -inf)).
+    Elementwise torch in a fixed order: equal inputs give equal bits"""
+    m = z.max(dim=0).values
+    ms = torch.where(m == float('-inf'), torch.zeros_like(m), m)
+    l = torch.zeros_like(m)
+    for w in range(z.shape[0]):
+        l = l + torch.exp(z[w] - ms)
+    return torch.where(m == float('-inf'), m, ms + torch.log(l))
+
+
 def shard_bounds(V, world, rank):
     per = (V + world - 1) // world
     per = (per + 63) // 64 * 64                 # whole 64-row scoring tiles per shard
@@ -413,6 +424,10 @@ class HipLocal:
         """this shard's share of ops.score_items: rows [id_lo, id_lo + n) of the catalog score, every other id gives 0.
         bias: as in select()"""
         return self.ops.score_items(srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo, **bias)
+
+    def norm(self, srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, **bias):
+        """this shard's log-normaliser of ops.score_norm: rows [id_lo, id_lo + n) of the catalog.  bias: as in select()"""
+        return self.ops.score_norm(srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
@@ -837,6 +852,21 @@ class VocabParallel:
             group = all_gather_cat(group.reshape(-1).to(torch.int32).contiguous(), self.group)
         return dict(bias=bias[..., self.lo:self.lo + self.n_live], group=group)
 
+    def _gather_sessions(self, srs, off_ex, off_in, listed):
+        """data_parallel: every rank's own B / world sessions -> the sessions of all ranks, in rank order (session vectors,
+        offsets [C, B] and listed [B, L]; lists of different widths on the ranks are padded with -1 to the widest)"""
+        srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
+        gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
+        off_ex, off_in = gat(off_ex), gat(off_in)
+        if listed is not None:
+            w = torch.tensor([listed.shape[1]], dtype=torch.int64, device=listed.device)
+            if _active(self.group):
+                all_reduce_(w, dist.ReduceOp.MAX, self.group)
+            pad = listed.new_full((listed.shape[0], int(w.item())), -1)
+            pad[:, :listed.shape[1]] = listed
+            listed = all_gather_cat(pad, self.group)
+        return srs, off_ex, off_in, listed
+
     def select(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
                bias=None, group=None):
         """the k best items of every session over the sharded table (ops.score_select's contract; srs: list of C [B, d]
@@ -847,16 +877,7 @@ class VocabParallel:
         n_loc = srs[0].shape[0]
         bkw = self._bias_cols(bias, group, data_parallel)
         if data_parallel:
-            srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
-            gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
-            off_ex, off_in = gat(off_ex), gat(off_in)
-            if listed is not None:           # lists of different widths on the ranks: pad to the widest
-                w = torch.tensor([listed.shape[1]], dtype=torch.int64, device=listed.device)
-                if _active(self.group):
-                    all_reduce_(w, dist.ReduceOp.MAX, self.group)
-                pad = listed.new_full((listed.shape[0], int(w.item())), -1)
-                pad[:, :listed.shape[1]] = listed
-                listed = all_gather_cat(pad, self.group)
+            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
         B, dev = srs[0].shape[0], srs[0].device
         if self.n_live > 0:
             csl = None if cs is None else cs[:self.n_live]
@@ -879,6 +900,28 @@ class VocabParallel:
             val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
         return val, idx
 
+    def norm(self, srs, table, cs, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False, bias=None,
+             group=None):
+        """fp32 [B]: the log-normaliser of select()'s score over the eligible items of the sharded table (ops.score_norm's
+        contract): every rank takes Z over its own LIVE rows with its id_lo and its columns of the bias (a rank without live
+        rows gives -inf), ONE all-gather carries the [world, B] values, and every rank folds them in rank order with the same
+        -inf-safe log-sum-exp - equal bits on every rank.  data_parallel, bias and group as in select()."""
+        n_loc = srs[0].shape[0]
+        bkw = self._bias_cols(bias, group, data_parallel)
+        if data_parallel:
+            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
+        B, dev = srs[0].shape[0], srs[0].device
+        if self.n_live > 0:
+            csl = None if cs is None else cs[:self.n_live]
+            z = self.local.norm(srs, table[:self.n_live], csl, off_ex, off_in, listed, drop_listed, self.lo, **bkw)
+        else:
+            z = torch.full((B,), float('-inf'), device=dev, dtype=torch.float32)
+        if _active(self.group):
+            z = lse_fold(all_gather_cat(z.unsqueeze(0), self.group))
+        if data_parallel:
+            z = z[self.rank * n_loc:(self.rank + 1) * n_loc]
+        return z
+
     def score_items(self, srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
                     bias=None, group=None):
         """the scores of given items over the sharded table (ops.score_items' contract; srs: list of C [B, d] session
@@ -891,18 +934,9 @@ class VocabParallel:
         n_loc = srs[0].shape[0]
         bkw = self._bias_cols(bias, group, data_parallel)
         if data_parallel:
-            srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
-            gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
-            off_ex, off_in = gat(off_ex), gat(off_in)
+            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
             if items.dim() == 2:
                 items = all_gather_cat(items.contiguous(), self.group)
-            if listed is not None:           # lists of different widths on the ranks: pad to the widest
-                w = torch.tensor([listed.shape[1]], dtype=torch.int64, device=listed.device)
-                if _active(self.group):
-                    all_reduce_(w, dist.ReduceOp.MAX, self.group)
-                pad = listed.new_full((listed.shape[0], int(w.item())), -1)
-                pad[:, :listed.shape[1]] = listed
-                listed = all_gather_cat(pad, self.group)
         B = srs[0].shape[0]
         if self.n_live > 0:
             csl = None if cs is None else cs[:self.n_live]

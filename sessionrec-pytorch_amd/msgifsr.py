@@ -596,13 +596,14 @@ class MSGIFSR(_ScoringMixin, nn.Module):
                 off_ex.append(la[c] - lse)
         return srs, cs, torch.stack(off_ex, 0), torch.stack(off_in, 0) if self.extra else None, listed
 
-    def _recommend(self, *inputs, k, exclude_seen, **bias):
+    def _scoring_args(self, *inputs, exclude_seen, raw=False):
         """the mixture of target_rank: forward()'s log scores WITHOUT its (B, V) matrices (one per order, plus the
         in-session mask).  With `extra` the session's own items are `listed` and score through the repeat branch (off_in);
-        exclude_seen drops them instead, so only the explore branch (off_ex) matters.  bias (item_bias / item_group) is added
-        AFTER the mixture, by the kernel."""
+        exclude_seen drops them instead, so only the explore branch (off_ex) matters.  (raw: a mixture's offsets are never
+        skipped - a renormalising caller subtracts Z from them.)  A bias (item_bias / item_group) is added AFTER the mixture,
+        by the kernels."""
         if not (self.extra or (self.fusion and self.order > 1)):
-            return super()._recommend(*inputs, k=k, exclude_seen=exclude_seen, **bias)
+            return super()._scoring_args(*inputs, exclude_seen=exclude_seen, raw=raw)
         (mg,) = inputs
         srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg)
         if self.extra or exclude_seen:
@@ -610,20 +611,7 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             listed = self._session_items(mg)
         if exclude_seen:
             off_in = None
-        return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, **bias)
-
-    def _score_items(self, *inputs, items, exclude_seen, **bias):
-        """the mixture of _recommend at given items: with `extra` the session's own items are `listed` and score through the
-        repeat branch (off_in); exclude_seen gives them -inf instead"""
-        if not (self.extra or (self.fusion and self.order > 1)):
-            return super()._score_items(*inputs, items=items, exclude_seen=exclude_seen, **bias)
-        (mg,) = inputs
-        srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg)
-        if self.extra or exclude_seen:
-            listed = self._session_items(mg)
-        if exclude_seen:
-            off_in = None
-        return self._items_of(srs, cs, items, off_ex, off_in, listed, exclude_seen, **bias)
+        return srs, cs, off_ex, off_in, listed
 
     def forward(self, mg):
         sr = self.session_repr(mg)

@@ -230,16 +230,19 @@ def score_ce(sr, table, cs, labels, ws, tgrad, dynB=None, cs_inv_scale=1.0, tb=N
     return ScoreCE.apply(sr, table, cs, labels, ws, tgrad, dynB, cs_inv_scale, tb)
 
 
-_BYTE_WS = {}
+_BYTE_WS = {}          # the evaluation / selection kernels: kinds 'topk', 'rank', 'select'
+_NORM_WS = {}          # the log-normaliser of the serving calls: kind 'norm'
 
 
-def _byte_ws(kind, device, nbytes):
-    """never-resized byte scratch of the evaluation kernels, one per (kind, device, size): the kinds ('topk', 'rank',
-    'select') never share a buffer, so no two of their launches alias scratch that the separate caches kept apart"""
+def _byte_ws(kind, device, nbytes, cache=None):
+    """never-resized byte scratch, one per (kind, device, size): the kinds never share a buffer, so no two of their launches
+    alias scratch that separate caches kept apart.  cache: the dict that holds it - _BYTE_WS (default) for the evaluation
+    kernels ('topk', 'rank', 'select'), _NORM_WS for score_norm, whose partials live beside them, not among them"""
+    cache = _BYTE_WS if cache is None else cache
     key = (kind, device.index, nbytes)
-    ws = _BYTE_WS.get(key)
+    ws = cache.get(key)
     if ws is None:
-        ws = _BYTE_WS[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        ws = cache[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
     return ws
 
 
@@ -267,6 +270,7 @@ _LISTED_TOO_MANY = {
                   '(evaluate such sessions with method="topk")',
     'score_select': 'score_select: %d listed items per session; csrc/recommend.hip takes at most 64',
     'score_items': 'score_items: %d listed items per session; csrc/score_items.hip takes at most 64',
+    'score_norm': 'score_norm: %d listed items per session; csrc/score_norm.hip takes at most 64',
 }
 
 
@@ -487,6 +491,36 @@ def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, dr
                                     ptr(a.off_in), ptr(a.listed), a.L, mode, ptr(items), M if items.dim() == 2 else 0, M,
                                     int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, ptr(out),
                                     stream())
+    return out
+
+
+def score_norm(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None):
+    """fp32 [B]: Z[b] = logsumexp over the ELIGIBLE rows v of `table` of the score of score_select, s[b,v] + bias[group[b], v]
+    with s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) - the normaliser under which the values of score_select /
+    score_items become log-probabilities over what can be shown: pass off_ex - Z (and off_in - Z) to them.  No (B, V)
+    tensor (csrc/score_norm.hip: one online log-sum-exp pass over the table, partials folded in a fixed order - no atomics,
+    equal bits on every call).  Argument conventions and eligibility as score_select: srs [B, d], [C, B, d] or a list of C
+    [B, d] tensors, C <= 4; off_ex / off_in [C, B] or None (= 0); listed [B, L] global item ids, -1 = empty slot;
+    drop_listed=False: listed items contribute with off_in; True: they do not contribute (off_in is ignored); an item whose
+    bias is -inf does not contribute; id_lo: global id of table row 0 (a row shard: the Z of disjoint shards combine by
+    logsumexp).  A session with no eligible row gives exactly -inf, never NaN.
+    Measured at B 512, V 37 484, d 256 (profiles/score_norm_timing.md): 180 us at C = 1 against 427 us
+    for score_logp(...) + torch.logsumexp and 203 us for the statistics pass (score_stats); 506 - 552 us at C = 3 (a [4, V]
+    bias, a 20-item list scored or dropped) against 1.7 - 3.2 ms for the three-matrix mixture - no row in which materialising
+    is faster."""
+    a = _mixture_args('score_norm', srs, table, off_ex, None if drop_listed else off_in, listed)
+    bi = _bias_args('score_norm', bias, group, a.B, a.V)
+    B, dev = a.B, a.srs.device
+    out = torch.empty(B, device=dev, dtype=torch.float32)
+    if B == 0:
+        return out
+    n = _ct.c_long()
+    lib.srec_score_norm_ws(B, a.V, a.d, a.C, a.L, _ct.addressof(n))
+    ws = _byte_ws('norm', dev, n.value, _NORM_WS)
+    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
+    lib.srec_score_norm(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
+                        ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G,
+                        ptr(out), ptr(ws), stream())
     return out
 
 

@@ -258,34 +258,85 @@ class _ScoringMixin:
             raise ValueError('%s: item_group holds a row id outside [0, %d)' % (who, G))
         return dict(bias=b, group=g)
 
-    def recommend(self, *inputs, k=20, exclude_seen=False, item_bias=None, item_group=None):
+    def recommend(self, *inputs, k=20, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """(log_probs fp32 [B,k] descending, item_ids int32 [B,k]): the k most probable next items of every session, k <= 128.
         The values are the numbers forward() returns at those items (log-probabilities); ties go towards the lower item
         id.  One fused selection pass over the table (csrc/recommend.hip): no (B, V) score matrix, sharded table included.
         exclude_seen=True never returns an item of the session itself (at most 64 distinct items per session); the remaining
-        items keep forward()'s log-probabilities - there is NO renormalisation over the remaining items.  A session with
-        fewer than k eligible items ends in (-inf, -1) slots.  Runs in eval mode under torch.no_grad().
+        items keep forward()'s log-probabilities (renormalize=True: see below).  A session with fewer than k eligible items
+        ends in (-inf, -1) slots.  Runs in eval mode under torch.no_grad().
         item_bias: fp32 [num_items], or [G, num_items] with item_group [B] row ids in [0, G) (sessions of several markets in
         one batch), over GLOBAL item ids (ops.catalog_bias builds one from allow / deny / boost lists).  The values are then
-        forward()'s log-probabilities PLUS the bias, ordered by that sum; an item whose bias is -inf is never returned.  As
-        with exclude_seen there is NO renormalisation over the allowed items.  A wrong length, NaN or +inf in the bias and
-        a group id outside [0, G) raise ValueError before anything is launched (_item_bias: one device-to-host read)."""
+        forward()'s log-probabilities PLUS the bias, ordered by that sum; an item whose bias is -inf is never returned.  A
+        wrong length, NaN or +inf in the bias and a group id outside [0, G) raise ValueError before anything is launched
+        (_item_bias: one device-to-host read).
+        renormalize=False: the values are not renormalised over the items that remain.  renormalize=True: they are the
+        log-probabilities of the model's distribution RESTRICTED to the eligible items (not the session's own under
+        exclude_seen, bias > -inf) and tilted by the finite bias, p(v) ~ p_model(v) exp(bias_v): per session exp(value) sums to
+        one over the eligible catalogue.  Order and ids are those of renormalize=False, -inf slots stay -inf.  One more fused
+        pass over the table (csrc/score_norm.hip, no (B, V) matrix) - and for a single soft-max the full-catalogue statistics
+        pass is skipped instead, the normaliser being taken over the raw logits.  With nothing to renormalise (no item_bias,
+        no exclude_seen) the call is the one of renormalize=False, bit for bit."""
         bias = self._item_bias('recommend', item_bias, item_group)
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad():
-                return self._recommend(*inputs, k=k, exclude_seen=exclude_seen, **bias)
+                return self._recommend(*inputs, k=k, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
         finally:
             self.train(was_training)
 
-    def _recommend(self, *inputs, k, exclude_seen, **bias):
+    def _recommend(self, *inputs, k, exclude_seen, renormalize=False, **bias):
+        srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+        return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, **bias)
+
+    def _scoring_args(self, *inputs, exclude_seen, raw=False):
+        """(srs, cs, off_ex, off_in, listed) under which the score of ops.score_select / score_items / score_norm,
+        logsumexp_c(z_c[b,v] + off_c[b]), is what forward() returns: one soft-max here, off_ex = -lse.  listed: the
+        session's own items when exclude_seen drops them.  raw=True (the caller normalises over the eligible items itself):
+        the full-catalogue statistics pass is skipped and off_ex is None - the score is the raw logit."""
         sr = self.session_repr(*inputs)
         st = self._state(sr.shape[0])
         cs, inv_scale = self._col_scale(st)
-        off_ex = -self._lse(sr, cs, inv_scale, st).unsqueeze(0)      # log softmax = z - lse
+        off_ex = None if raw else -self._lse(sr, cs, inv_scale, st).unsqueeze(0)      # log softmax = z - lse
         listed = self._session_items(inputs[0]) if exclude_seen else None
-        return self._select_of([sr], cs, k, off_ex, None, listed, exclude_seen, **bias)
+        return [sr], cs, off_ex, None, listed
+
+    def _served(self, *inputs, exclude_seen, renormalize, **bias):
+        """_scoring_args; renormalize with something to renormalise (a bias or exclude_seen): the offsets minus Z, the
+        log-normaliser over the eligible items, so that the kernels return s - Z (a session with nothing eligible: Z = -inf,
+        offsets unchanged - all its slots are -inf anyway)"""
+        todo = bool(renormalize) and (bool(bias) or bool(exclude_seen))
+        srs, cs, off_ex, off_in, listed = self._scoring_args(*inputs, exclude_seen=exclude_seen, raw=todo)
+        if todo:
+            Z = self._norm_of(srs, cs, off_ex, off_in, listed, exclude_seen, **bias)
+            Zs = torch.where(Z == float('-inf'), torch.zeros_like(Z), Z).unsqueeze(0)
+            off_ex = -Zs if off_ex is None else off_ex - Zs
+            off_in = None if off_in is None else off_in - Zs
+        return srs, cs, off_ex, off_in, listed
+
+    def _norm_of(self, srs, cs, off_ex, off_in, listed, drop_listed, **bias):
+        if self.shard is not None:       # every shard over its rows: one all-gather of [W, B] floats, folded in rank order
+            return self.shard.norm(srs, self._table(), cs, off_ex, off_in, listed, drop_listed,
+                                   data_parallel=self.shard.eval_data_parallel, **bias)
+        return ops.score_norm(srs, self._table(), cs, off_ex, off_in, listed, drop_listed, **bias)
+
+    def log_mass(self, *inputs, exclude_seen=False, item_bias=None, item_group=None):
+        """fp32 [B]: the log of the probability mass, under forward()'s distribution, of the items a filter leaves - the
+        items recommend() could return with the same keywords (not the session's own under exclude_seen, item_bias > -inf);
+        with a finite bias the log-partition of the tilted distribution, log sum_v p_model(v) exp(bias_v).  0 up to round-off
+        without a filter, -inf for a session with nothing eligible.  It is what renormalize=True subtracts.  One fused pass
+        over the table (csrc/score_norm.hip), no (B, V) matrix, sharded table included; eval mode under torch.no_grad(),
+        item_bias / item_group checked first as in recommend()."""
+        bias = self._item_bias('log_mass', item_bias, item_group)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                srs, cs, off_ex, off_in, listed = self._scoring_args(*inputs, exclude_seen=exclude_seen)
+                return self._norm_of(srs, cs, off_ex, off_in, listed, exclude_seen, **bias)
+        finally:
+            self.train(was_training)
 
     def _lse(self, sr, cs, inv_scale, st, labels=None):
         """log-sum-exp of every session's logits over the whole catalog: the fused statistics pass (no gradient kept)"""
@@ -315,15 +366,18 @@ class _ScoringMixin:
                                      data_parallel=self.shard.eval_data_parallel, **bias)
         return ops.score_select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, **bias)
 
-    def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None):
+    def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """fp32 [B, M]: the log-probability forward() returns at the given items of every session - full-catalog soft-max
-        (or mixture), NO renormalisation over the candidates.  items: [B, M] item ids per session or [M] shared by all
+        (or mixture), never renormalised over the CANDIDATES (log_softmax over the returned row is the caller's one-liner).  items: [B, M] item ids per session or [M] shared by all
         sessions, any integer dtype, any M; -1 is padding and gives -inf; duplicates are allowed.  exclude_seen=True gives
         -inf at the session's own items (at most 64 distinct items per session) and leaves the rest unchanged.  An id
         < -1 or >= num_items raises ValueError before anything is launched.  One gather pass over the candidates' rows
         (csrc/score_items.hip): no (B, V) score matrix, sharded table included.  Runs in eval mode under torch.no_grad().
         item_bias / item_group as in recommend(): the values are forward()'s log-probabilities PLUS the bias (-inf stays
-        -inf), NO renormalisation; checked before anything is launched (_item_bias: one more device-to-host read)."""
+        -inf); checked before anything is launched (_item_bias: one more device-to-host read).
+        renormalize as in recommend(): True gives log-probabilities under the distribution restricted to the eligible
+        CATALOGUE (every item exclude_seen and item_bias leave, whether it is among the candidates or not) and tilted by the
+        bias - the numbers recommend(renormalize=True) returns for the same items."""
         bias = self._item_bias('score_items', item_bias, item_group)
         n = self.shard.V if self.shard is not None else self._table().shape[0]
         if items.numel() > 0:
@@ -334,17 +388,13 @@ class _ScoringMixin:
         self.eval()
         try:
             with torch.no_grad():
-                return self._score_items(*inputs, items=items, exclude_seen=exclude_seen, **bias)
+                return self._score_items(*inputs, items=items, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
         finally:
             self.train(was_training)
 
-    def _score_items(self, *inputs, items, exclude_seen, **bias):
-        sr = self.session_repr(*inputs)
-        st = self._state(sr.shape[0])
-        cs, inv_scale = self._col_scale(st)
-        off_ex = -self._lse(sr, cs, inv_scale, st).unsqueeze(0)      # log softmax = z - lse
-        listed = self._session_items(inputs[0]) if exclude_seen else None
-        return self._items_of([sr], cs, items, off_ex, None, listed, exclude_seen, **bias)
+    def _score_items(self, *inputs, items, exclude_seen, renormalize=False, **bias):
+        srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+        return self._items_of(srs, cs, items, off_ex, off_in, listed, exclude_seen, **bias)
 
     def _items_of(self, srs, cs, items, off_ex, off_in, listed, drop_listed, **bias):
         items = items.to(srs[0].device)
@@ -353,13 +403,15 @@ class _ScoringMixin:
                                           data_parallel=self.shard.eval_data_parallel, **bias)
         return ops.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed, checked=True, **bias)
 
-    def rerank(self, *inputs, items, k=None, exclude_seen=False, item_bias=None, item_group=None):
+    def rerank(self, *inputs, items, k=None, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """(log_probs fp32 [B, n], item_ids int32 [B, n]), n = M or min(k, M): the candidates of score_items ordered by
         (value descending, id ascending) - the contract of recommend()'s lists without its limit of 128.  Slots that score
         -inf (padding, the session's own items under exclude_seen, and items whose item_bias is -inf) come last with id -1; a
         candidate named twice is returned twice.  item_bias / item_group as in score_items(): ordered by log-probability PLUS
-        bias."""
-        val = self.score_items(*inputs, items=items, exclude_seen=exclude_seen, item_bias=item_bias, item_group=item_group)
+        bias.  renormalize as in score_items(): the normaliser is over the eligible CATALOGUE, not over the candidates - the
+        order is unchanged."""
+        val = self.score_items(*inputs, items=items, exclude_seen=exclude_seen, item_bias=item_bias, item_group=item_group,
+                               renormalize=renormalize)
         ids = items.to(val.device).to(torch.int64)
         ids = torch.where(val == float('-inf'), torch.full_like(val, -1, dtype=torch.int64), ids.expand_as(val))
         # two stable sorts, as the merge of dist.VocabParallel.select: by id (unfilled slots last), then by value

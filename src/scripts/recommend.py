@@ -8,7 +8,9 @@ flags must be those of the training run.  --sessions holds one session per line 
 session, in input order - `id:logprob` pairs separated by tabs, best first (model.recommend: one fused selection pass over
 the item table, no (B, V) score matrix).  --allow FILE / --deny FILE (one item id per line) restrict the catalogue for this
 run and --item-bias FILE (`id:value` or `id<TAB>value` per line) is added to the log-probabilities before ranking; the printed
-values are then log-probability + bias (ops.catalog_bias combines the three, the selection kernel applies them)."""
+values are then log-probability + bias (ops.catalog_bias combines the three, the selection kernel applies them).
+--renormalize prints them renormalised over the items that remain eligible (model.recommend(renormalize=True): one more
+fused pass, csrc/score_norm.hip)."""
 import argparse
 import sys
 
@@ -62,6 +64,9 @@ def parser(model):
     p.add_argument('--top', type=int, default=20, help='items per session (at most %d)' % MAX_TOP)
     p.add_argument('--exclude-seen', action='store_true', help="never recommend an item of the session itself")
     catalog_flags(p)
+    p.add_argument('--renormalize', action='store_true',
+                   help='print log-probabilities renormalised over the eligible catalogue (--exclude-seen, --allow / --deny, '
+                        '--item-bias): per session they sum to one over the items that can be shown')
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -114,7 +119,7 @@ def main(argv=None):
         for b in range(0, len(sessions), args.batch_size):
             inputs, _ = collate_fn([(s, 0) for s in sessions[b:b + args.batch_size]])
             val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen,
-                                       item_bias=item_bias)
+                                       item_bias=item_bias, renormalize=args.renormalize)
             for ids, vals in zip(idx.cpu().tolist(), val.cpu().tolist()):
                 out.write(format_line(ids, vals) + '\n')
     finally:

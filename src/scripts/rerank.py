@@ -7,7 +7,8 @@ i on line i, separated by commas (lines may differ in length); a file of ONE lin
 per input session, in input order - `id:logprob` pairs separated by tabs, best first, in recommend.py's format.  The values
 are the model's full-catalog log-probabilities of the candidates (model.rerank: one gather pass over the candidates' rows,
 no (B, V) score matrix, any number of candidates); candidates that cannot be returned (--exclude-seen, --allow / --deny) are left out.  --allow / --deny / --item-bias as in
-recommend.py: the values are then log-probability + bias."""
+recommend.py: the values are then log-probability + bias.  --renormalize as in recommend.py: over the eligible CATALOGUE, not
+over the candidates."""
 import argparse
 import sys
 
@@ -26,6 +27,9 @@ def parser(model):
     p.add_argument('--top', type=int, default=None, help='items per session (default: every candidate)')
     p.add_argument('--exclude-seen', action='store_true', help="never return an item of the session itself")
     catalog_flags(p)
+    p.add_argument('--renormalize', action='store_true',
+                   help='print log-probabilities renormalised over the eligible catalogue (--exclude-seen, --allow / --deny, '
+                        '--item-bias): per session they sum to one over the items that can be shown')
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -96,7 +100,7 @@ def main(argv=None):
             inputs, _ = collate_fn([(s, 0) for s in sessions[b:b + args.batch_size]])
             items = th.tensor(pad_candidates(candidates[b:b + args.batch_size]), dtype=th.int64)
             val, idx = model.rerank(*[x.to(device) for x in inputs], items=items.to(device), k=args.top,
-                                    exclude_seen=args.exclude_seen, item_bias=item_bias)
+                                    exclude_seen=args.exclude_seen, item_bias=item_bias, renormalize=args.renormalize)
             for ids, vals in zip(idx.cpu().tolist(), val.cpu().tolist()):
                 out.write(format_line(ids, vals) + '\n')
     finally:
