@@ -1,50 +1,36 @@
 // srec_score_rank: the RANK of every session's label among all catalog items WITHOUT materialising the (B, V) score
 // matrix and without a K limit (evaluate: train.py:36-55 = model forward -> logits.topk(20); every HR / MRR / NDCG at any
 // cutoff is a function of this one integer).  Scores may mix up to four soft-maxes (msgifsr.py:281-321: order fusion and
-// the repeat / explore gate):
-//   s[b,v] = logsumexp_{c<C}( cs[v] * <sr_c[b], E_v> + off[c,b] ),  off = off_in if v is in listed[b,:] else off_ex
-// (C == 1: s = z + off, no exp / log).  rank[b] = #{ local rows v, id_lo + v != label_b : s[b,v] > target_b, or
-// s[b,v] == target_b and id_lo + v < label_b } - the tie rule of topk.hip.  The label is left out BY ID, never by comparing
-// its own score, so round-off cannot make it count against itself.  Counts of disjoint row ranges add up: a row-sharded
-// table needs one integer all-reduce of rank (and one of target, which exactly one shard computes; the others write 0).
+// the repeat / explore gate): the served score of score_pass.h, without a bias.
+// rank[b] = #{ local rows v, id_lo + v != label_b : s[b,v] > target_b, or s[b,v] == target_b and id_lo + v < label_b } -
+// the tie rule of topk.hip.  The label is left out BY ID, never by comparing its own score, so round-off cannot make it
+// count against itself.  Counts of disjoint row ranges add up: a row-sharded table needs one integer all-reduce of rank
+// (and one of target, which exactly one shard computes; the others write 0).
 //
 // Target pass (rank_target_kernel): one wavefront per session scores the label's row (off_in if the label is listed);
 //   it also initialises rank[b] (0, or -1 for a label < 0).
-// Count pass (rank_count_kernel, the hot path; its tile product is score_tile.h, shared with recommend.hip): workgroup = 32
-//   sessions x one item range, 4 wavefronts.  The C session
-//   tiles sit in LDS for the lifetime of the workgroup (C = 3, d = 256: 98 KB); each wavefront owns 32 items of a
-//   128-item chunk whose rows stream straight from HBM into the B operand of v_mfma_f32_32x32x2_f32 (exact fp32): lane
-//   (item r, half h) loads the float4 at columns 8j + 4h, the A lane reads the same columns of its session from LDS, so the
-//   MFMA's two k slots of step i are columns 8j + i and 8j + 4 + i - a permutation of the sum, no staging of the table.
-//   The C accumulator tiles of a (session, item) pair live in one lane: scale by cs[v], add off_ex, combine, compare with
-//   target_b; one ballot + two popcounts per accumulator register count a session's items, partial counts meet in LDS and
-//   leave with ONE integer atomicAdd per (session, workgroup).  Integer sums: the result does not depend on their order.
-//   This pass treats every item as "ex".
+// Count pass (rank_count_kernel, the hot path): the pass of score_pass.h with the listed set and the bias compiled out -
+//   every item scores with off_ex.  A lane compares its (session, item) score with target_b; one ballot + two popcounts per
+//   accumulator register count a session's items, partial counts meet in LDS and leave with ONE integer atomicAdd per
+//   (session, workgroup).  Integer sums: the result does not depend on their order.
 // Fix-up pass (rank_fixup_kernel, only with a listed set): one wavefront per (b, j) scores u = listed[b,j] with off_ex and
 //   with off_in (same routine as the target pass) and adds [ahead(s_in)] - [ahead(s_ex)].  The order-1 node list of a
 //   session holds every item ONCE, so the lists need no dedup (a repeated id would be corrected twice).  The count pass saw
 //   that item's "ex" score in the MFMA's summation order, this pass in a wavefront's: within round-off of the target the two
 //   comparisons can disagree and the sum is off by one - callers clamp a live session's rank at 0.
-// Session tiles that do not fit the 160 KB of LDS (896 B of per-session scalars + C * 32 * (d + 4) floats, d rounded up to
-// 32: C * (d + 4) > 1273) are read through the cache instead - same code.
+// LDS: 896 B of per-session scalars + the session tiles (C = 3, d = 256: 98 KB) when they fit 160 KB; C * 32 * (d + 4) floats,
+// d rounded up to 32, do not when C * (d + 4) > 1273: they are read through the cache instead - same code.
 #include "common.h"
-#include "score_tile.h"
+#include "score_pass.h"
 
 namespace {
 
-using namespace score_tile;      // SB sessions x CHUNK items per step, mix<C>, the MFMA tile product (score_tile.h)
+using namespace score_tile;
 
-struct RankArgs {
-    const float* sr; int ld_sr; long comp_stride;
-    const float* E; int ld_e;
-    const float* cs;
-    const float* off_ex; const float* off_in;
-    const int* listed; int L;
-    const int* labels; long id_lo;
-    int B, V, d;
+struct RankArgs : PassArgs {
+    const int* labels;
     float* target; int target_given;
     int* rank;
-    int items_per_range;
 };
 
 __device__ __forceinline__ bool ahead(float s, long id, float t, long lab) { return s > t || (s == t && id < lab); }
@@ -145,10 +131,9 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankArgs a) {
         labs[tid] = (int)lv;
         cnt[tid] = 0;
     }
-    for (int i = tid; i < C * SB; i += 256) {
-        const int c = i / SB, b = b0 + i % SB;
-        offs[c * SB + i % SB] = (a.off_ex != nullptr && b < a.B) ? a.off_ex[(size_t)c * a.B + b] : 0.f;
-    }
+    const PassLds<false> ps{offs};
+    SCORE_PASS_STAGE_OFFSETS(C, a, ps, b0, tid)
+    SCORE_PASS_PROLOGUE(0, a, ps, b0, v0, v1, tid, lane, wave)
     if (SR_LDS) stage_tiles<C>(Ss, a.sr, a.ld_sr, a.comp_stride, b0, a.B, d, tid);
     __syncthreads();
 
@@ -161,24 +146,17 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankArgs a) {
     for (int r = 0; r < 16; ++r) { clo[r] = 0; chi[r] = 0; }
 
     for (int base = v0; base < v1; base += CHUNK) {
-        const int v = base + wave * 32 + l31;
-        const bool vok = v < v1;
-        const float* brow = a.E + (size_t)min(v, a.V - 1) * a.ld_e + 4 * half;
-        const float csv = (a.cs != nullptr && vok) ? a.cs[v] : 1.f;
+        SCORE_PASS_LANE_ITEM(0, it, a, ps, base, v1, wave, l31, half)
         f32x16 acc[C];
-        dots<C, SR_LDS>(arow, brow, d, half, acc);
+        dots<C, SR_LDS>(arow, it.brow, d, half, acc);
 
         // per-lane epilogue: item v (this lane's column) against 16 sessions
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int sl = session_of(r, half);
-            float z[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) z[c] = csv * acc[c][r] + offs[c * SB + sl];
-            const float s = mix<C>(z);
+            SCORE_PASS_ITEM_SCORE(C, 0, it, acc, r, ps, wave, l31, half, sl, in, s, bias_ok)
             const float t = tgt[sl];
             const int lv = labs[sl];
-            const bool hit = vok && v != lv && (s > t || (s == t && v < lv));
+            const bool hit = SCORE_PASS_ELIGIBLE(it, in, ps, true, bias_ok) && it.v != lv && (s > t || (s == t && it.v < lv));
             const unsigned long long m = __ballot(hit);
             clo[r] += __popc((unsigned)m);
             chi[r] += __popc((unsigned)(m >> 32));
@@ -198,26 +176,13 @@ __global__ __launch_bounds__(256) void rank_count_kernel(RankArgs a) {
     if (tid < SB && b0 + tid < a.B && cnt[tid] != 0 && a.labels[b0 + tid] >= 0) atomicAdd(&a.rank[b0 + tid], cnt[tid]);
 }
 
-inline int pick_ranges(int B, int V) {
-    const int tiles = cdiv(B, SB);
-    int R = cdiv(1024, tiles);                                  // ~4 workgroups per CU (as topk.hip)
-    const int maxR = cdiv(V, 2 * CHUNK);                        // at least 2 chunks per range
-    if (R > maxR) R = maxR;
-    return R < 1 ? 1 : R;
-}
-
 inline size_t count_lds(int C, int d, bool sr_lds) {
     const size_t head = (size_t)(SB + MAXCOMP * SB + SB + SB) * 4;
     return head + (sr_lds ? tile_bytes(C, d) : 0);
 }
 
-template <int C, bool SR_LDS>
-int launch_count(const RankArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-    static std::atomic<unsigned long long> optin{0};
-    if (int rc = srec_lds_optin((const void*)rank_count_kernel<C, SR_LDS>, LDS_BYTES, optin)) return rc;
-    hipLaunchKernelGGL((rank_count_kernel<C, SR_LDS>), grid, dim3(256), lds, st, a);
-    return 0;
-}
+template <int C, bool SR_LDS, int>
+struct RankCount { static constexpr auto kernel = rank_count_kernel<C, SR_LDS>; };
 
 template <int C>
 int run(const RankArgs& a0, hipStream_t st) {
@@ -227,13 +192,9 @@ int run(const RankArgs& a0, hipStream_t st) {
         SREC_LAUNCH_CHECK();
         return 0;
     }
-    const int R = pick_ranges(a.B, a.V);
-    a.items_per_range = cdiv(cdiv(a.V, R), CHUNK) * CHUNK;
-    const dim3 grid(cdiv(a.V, a.items_per_range), cdiv(a.B, SB));
-    const bool fits = count_lds(C, a.d, true) <= (size_t)LDS_BYTES;
-    const int rc = fits ? launch_count<C, true>(a, grid, count_lds(C, a.d, true), st)
-                        : launch_count<C, false>(a, grid, count_lds(C, a.d, false), st);
-    if (rc) return rc;
+    const dim3 grid(split_ranges(a, pick_ranges(a.B, a.V, 1024, 2)), cdiv(a.B, SB));    // ~4 workgroups per CU (as topk.hip)
+    const auto lds = [&](int c, bool sr_lds, bool) { return count_lds(c, a.d, sr_lds); };
+    if (int rc = launch_pass<RankCount, false, C>(a, grid, lds, st)) return rc;
     if (a.listed != nullptr && a.L > 0) {
         const long n = (long)a.B * a.L;
         hipLaunchKernelGGL((rank_fixup_kernel<C>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, a);
@@ -247,8 +208,7 @@ int run(const RankArgs& a0, hipStream_t st) {
 // rank == NULL (and !target_given): the target pass alone - a shard's share of target[], ahead of the sum over shards.
 // no scratch is needed (partial counts meet through integer atomics); a token size keeps the caller's cache uniform
 extern "C" int srec_score_rank_ws(int B, int V, int d, int C, int L, long* bytes) {
-    if (B <= 0 || V <= 0 || d <= 0 || (d & 3) || d > 1024 || C < 1 || C > MAXCOMP || L < 0 || L > MAXL || bytes == nullptr)
-        return SREC_BAD_ARG;
+    if (bad_shape(B, V, d, C, L) || bytes == nullptr) return SREC_BAD_ARG;
     *bytes = 16;
     return 0;
 }
@@ -259,20 +219,12 @@ extern "C" int srec_score_rank(const float* sr, int ld_sr, long comp_stride, con
                                void* stream) {
     (void)ws;
     if (B <= 0) return 0;
-    if (V <= 0 || d <= 0 || (d & 3) || d > 1024 || C < 1 || C > MAXCOMP || L < 0 || L > MAXL || (ld_sr & 3) || (ld_e & 3) ||
-        (comp_stride & 3) || ((uintptr_t)E & 15) || ((uintptr_t)sr & 15) || labels == nullptr || target == nullptr ||
-        (rank == nullptr && target_given) || id_lo < 0)
-        return SREC_BAD_ARG;
     RankArgs a{};
-    a.sr = sr; a.ld_sr = ld_sr; a.comp_stride = comp_stride; a.E = E; a.ld_e = ld_e; a.cs = cs;
-    a.off_ex = off_ex; a.off_in = off_in; a.listed = L > 0 ? listed : nullptr; a.L = a.listed != nullptr ? L : 0;
-    a.labels = labels; a.id_lo = id_lo; a.B = B; a.V = V; a.d = d; a.target = target; a.target_given = target_given;
-    a.rank = rank;
+    if (pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, 0, id_lo, B, V, d, C, nullptr, 0, nullptr, 1,
+                  false) ||
+        labels == nullptr || target == nullptr || (rank == nullptr && target_given))
+        return SREC_BAD_ARG;
+    a.labels = labels; a.target = target; a.target_given = target_given; a.rank = rank;
     hipStream_t st = (hipStream_t)stream;
-    switch (C) {
-        case 1: return run<1>(a, st);
-        case 2: return run<2>(a, st);
-        case 3: return run<3>(a, st);
-        default: return run<4>(a, st);
-    }
+    return switch_c(C, [&](auto c) { return run<c.value>(a, st); });
 }

@@ -1,9 +1,7 @@
 // srec_score_items: the score of srec_score_rank / srec_score_select at GIVEN items of every session - M candidate ids per
 // session (re-ranking, allow-lists, sampled-negative evaluation, lists longer than recommend.hip's 128), WITHOUT the (B, V)
-// score matrix (replaces `logits = model(...); logits.gather(1, items)` over msgifsr.py:306-321 / srgnn.py:145-147).  Same
-// score, layouts and limits as rank.hip / recommend.hip:
-//   s[b,v] = logsumexp_{c<C}( cs[v] * <sr_c[b], E_v> + off[c,b] ),  off = off_in if v is in listed[b,:] else off_ex
-// (C == 1: s = z + off, no exp / log); 1 <= C <= 4, d % 4 == 0, d <= 1024, L <= 64, cs / off_* / listed nullable.
+// score matrix (replaces `logits = model(...); logits.gather(1, items)` over msgifsr.py:306-321 / srgnn.py:145-147).  The
+// served score, its layouts and limits: score_pass.h, which also gives the argument block, its checks and switch_c.
 // Per slot: id < 0 (padding) -> -INFINITY; a row outside [id_lo, id_lo + V) belongs to another shard -> 0.0f, nothing is
 // read for it (results of disjoint row ranges add up); SREC_LISTED_SCORE: a listed item scores with off_in;
 // SREC_LISTED_DROP: the owning shard gives -INFINITY.  Duplicate ids are scored independently.
@@ -28,31 +26,22 @@
 // turns the slot into a padding slot (no row is read for it), any other value goes to a third LDS word per slot that the
 // writing lane adds - no memory instruction joins the hot loop, and a foreign id reads neither the table nor the bias.
 #include "common.h"
-#include "score_tile.h"
+#include "score_pass.h"
 
 namespace {
 
-using score_tile::MAXCOMP;
 using score_tile::MAXL;
 using score_tile::mix;
+using score_tile::PassArgs;
 
 constexpr int CH = 256;             // candidate slots per workgroup pass (one per thread when they are resolved)
 constexpr int ROW_PAD = -1;         // slot states below the local rows: -INFINITY ...
 constexpr int ROW_FOREIGN = -2;     // ... and 0.0f (another shard owns the id)
 
-struct ItemArgs {
-    const float* sr; int ld_sr; long comp_stride;
-    const float* E; int ld_e;
-    const float* cs;
-    const float* off_ex; const float* off_in;
-    const int* listed; int L; int drop;
+struct ItemArgs : PassArgs {        // off_in: null under SREC_LISTED_DROP; group: null when G == 1
     const int* items; long ld_items; int M;
-    long id_lo;
-    int B, V, d;
     int logT;                       // a row is read by 1 << logT lanes
     float* out;
-    const float* bias; long ld_bias; // (appended: the unbiased instances read the arguments above where they were)
-    const int* group; int G;
 };
 
 template <int C, int J, bool BIAS>
@@ -208,28 +197,17 @@ extern "C" int srec_score_items_biased(const float* sr, int ld_sr, long comp_str
                                        const int* items, long ld_items, int M, long id_lo, int B, int V, int d, int C,
                                        const float* bias, long ld_bias, const int* group, int G, float* out, void* stream) {
     if (B <= 0) return 0;
-    if (G < 1 || (group == nullptr && G > 1) || (bias != nullptr && G > 1 && ld_bias < (long)V) || ((uintptr_t)bias & 3) ||
-        ((uintptr_t)group & 3))
-        return SREC_BAD_ARG;
-    if (V <= 0 || d <= 0 || (d & 3) || d > 1024 || C < 1 || C > MAXCOMP || L < 0 || L > MAXL || M < 1 || (ld_sr & 3) ||
-        (ld_e & 3) || (comp_stride & 3) || ld_sr < d || ld_e < d || ((uintptr_t)E & 15) || ((uintptr_t)sr & 15) ||
-        ((uintptr_t)items & 3) || ((uintptr_t)out & 3) || items == nullptr || out == nullptr || id_lo < 0 ||
-        id_lo + (long)V > 0x7fffffffL || (ld_items != 0 && ld_items < (long)M) || (listed_mode != 0 && listed_mode != 1))
-        return SREC_BAD_ARG;
     ItemArgs a{};
-    a.sr = sr; a.ld_sr = ld_sr; a.comp_stride = comp_stride; a.E = E; a.ld_e = ld_e; a.cs = cs;
-    a.off_ex = off_ex; a.off_in = listed_mode == 1 ? nullptr : off_in;
-    a.listed = L > 0 ? listed : nullptr; a.L = a.listed != nullptr ? L : 0; a.drop = listed_mode;
-    a.items = items; a.ld_items = ld_items; a.M = M; a.id_lo = id_lo; a.B = B; a.V = V; a.d = d; a.out = out;
-    a.bias = bias; a.ld_bias = ld_bias; a.group = G > 1 ? group : nullptr; a.G = G;
+    if (score_tile::pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, listed_mode == 1 ? nullptr : off_in, listed, L,
+                              listed_mode, id_lo, B, V, d, C, bias, ld_bias, group, G, true) ||
+        M < 1 || ld_sr < d || ld_e < d || ((uintptr_t)items & 3) || ((uintptr_t)out & 3) || items == nullptr || out == nullptr ||
+        (ld_items != 0 && ld_items < (long)M))
+        return SREC_BAD_ARG;
+    if (G == 1) a.group = nullptr;
+    a.items = items; a.ld_items = ld_items; a.M = M; a.out = out;
     while ((4 << a.logT) < d && a.logT < 6) ++a.logT;               // the smallest power of two of lanes that covers a row
     hipStream_t st = (hipStream_t)stream;
-    switch (C) {
-        case 1: return run<1>(a, st);
-        case 2: return run<2>(a, st);
-        case 3: return run<3>(a, st);
-        default: return run<4>(a, st);
-    }
+    return score_tile::switch_c(C, [&](auto c) { return run<c.value>(a, st); });
 }
 
 extern "C" int srec_score_items(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,

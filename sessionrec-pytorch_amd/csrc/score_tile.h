@@ -1,10 +1,10 @@
-// Tile scoring shared by rank.hip (count against a target) and recommend.hip (select the K best): a workgroup of 4
+// The MFMA tile product under the catalogue pass of score_pass.h (rank.hip, recommend.hip, score_norm.hip): a workgroup of 4
 // wavefronts scores 32 sessions against a 128-item chunk with v_mfma_f32_32x32x2_f32 (exact fp32), up to four session
 // vectors (mixture components) per session.  The C session tiles sit in LDS when they fit, else they are read through the
 // cache - same code, same summation order, same result.
 //   lane (item r = lane & 31, half h = lane >> 5) loads the float4 at columns 8j + 4h of its item row, the A lane reads the
 //   same columns of its session, so the MFMA's two k slots of step i are columns 8j + i and 8j + 4 + i - a permutation of the
-//   sum, no staging of the table.  Accumulator register r of lane (l31, h) is (session score_tile_session(r, h), item l31).
+//   sum, no staging of the table.  Accumulator register r of lane (l31, h) is (session session_of(r, h), item l31).
 #pragma once
 #include "common.h"
 

@@ -314,6 +314,10 @@ BiasArgs = namedtuple('BiasArgs', 'bias ld_bias group G')
 _NO_BIAS = BiasArgs(None, 0, None, 1)
 
 
+def _listed_mode(drop_listed):
+    return CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
+
+
 def _bias_args(who, bias, group, B, V):
     """The per-item bias of score_select and score_items as one BiasArgs.  bias: floating [V] (one row for all sessions) or
     [G, V] with group [B] integer row ids in [0, G) (a [1, V] bias needs none); None = no bias.  A tensor with unit column
@@ -437,14 +441,10 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     n = _ct.c_long()
     lib.srec_score_select_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
     ws = _byte_ws('select', dev, n.value)
-    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
-    if bi.bias is None:
-        lib.srec_score_select(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                              ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, k, ptr(val), ptr(idx), ptr(ws), stream())
-    else:
-        lib.srec_score_select_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
-                                     ptr(a.off_in), ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias),
-                                     bi.ld_bias, ptr(bi.group), bi.G, ptr(val), ptr(idx), ptr(ws), stream())
+    # (no bias: bias NULL, G 1 - what srec_score_select passes on, the same kernel instances)
+    lib.srec_score_select_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
+                                 ptr(a.off_in), ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k,
+                                 ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, ptr(val), ptr(idx), ptr(ws), stream())
     return val, idx
 
 
@@ -481,16 +481,10 @@ def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, dr
     if not checked and int(items.min()) < -1:
         raise ValueError('score_items: item id %d; ids are >= 0, or -1 for a padding slot' % int(items.min()))
     items = items.to(torch.int32).contiguous()
-    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
-    if bi.bias is None:
-        lib.srec_score_items(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                             ptr(a.listed), a.L, mode, ptr(items), M if items.dim() == 2 else 0, M, int(id_lo), B, a.V, a.d, a.C,
-                             ptr(out), stream())
-    else:
-        lib.srec_score_items_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
-                                    ptr(a.off_in), ptr(a.listed), a.L, mode, ptr(items), M if items.dim() == 2 else 0, M,
-                                    int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, ptr(out),
-                                    stream())
+    lib.srec_score_items_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
+                                ptr(a.off_in), ptr(a.listed), a.L, _listed_mode(drop_listed), ptr(items),
+                                M if items.dim() == 2 else 0, M, int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias,
+                                ptr(bi.group), bi.G, ptr(out), stream())
     return out
 
 
@@ -517,10 +511,9 @@ def score_norm(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_liste
     n = _ct.c_long()
     lib.srec_score_norm_ws(B, a.V, a.d, a.C, a.L, _ct.addressof(n))
     ws = _byte_ws('norm', dev, n.value, _NORM_WS)
-    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
     lib.srec_score_norm(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                        ptr(a.listed), a.L, mode, int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G,
-                        ptr(out), ptr(ws), stream())
+                        ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias,
+                        ptr(bi.group), bi.G, ptr(out), ptr(ws), stream())
     return out
 
 
