@@ -117,6 +117,13 @@ int srec_scatter_add_sorted_drop(const float* g, int ld_g, const int* items, con
 int srec_scatter_add_sorted_ex(const float* g, int ld_g, const int* items, const int* ptr, const int* pos, float* dst,
                                int ld_dst, int u_cap, const int* dyn, int d, int accumulate, float p, int seed,
                                const int* counter, int salt, const float* projW, int ld_w, float* radial, void* stream);
+/* srec_scatter_add_sorted_ex (radial NULL) as the FIRST level of a two-level lookup gradient whose second level the optimizer's
+ * row pass performs (srec_adam_rows_lookup): wavefront u < min(*stamp_dyn, stamp_cap) also writes slot[stamp_items[u]] = u + 1
+ * (stamp_items[u] < 0 skipped; slot int32 [table rows], zero before and zeroed again by the row pass).  stamp_cap <= u_cap. */
+int srec_scatter_add_sorted_stamp(const float* g, int ld_g, const int* items, const int* ptr, const int* pos, float* dst,
+                                  int ld_dst, int u_cap, const int* dyn, int d, int accumulate, float p, int seed,
+                                  const int* counter, int salt, const int* stamp_items, int stamp_cap, const int* stamp_dyn,
+                                  int* slot, void* stream);
 /* row-sharded lookup backward (the nn.Embedding gradient of srgnn.py:133 / msgifsr.py:247 when the table is sharded over the
  * ranks): dst[rel[q], :] += rows[q, :] for every request q < w ucap with rel[q] >= 0, the requests of ALL w <= 16 ranks in one launch
  * and - an item may be requested by several ranks - added per item in rank order (the bits of w rank-by-rank
@@ -341,6 +348,22 @@ int srec_adam_rows(float* W, const float* G, float* M, float* V, int n, int d, i
 int srec_adam_rows_proj(float* W, const float* G, float* M, float* V, int n, int d, int ld, const float* hyper, int use_wd,
                         float max_norm, int renorm_write, float* cs_out, float cs_scale, int eps_mode, float cs_eps,
                         const float* proj_cs, float proj_inv_scale, float* radial, void* dst16, int Dp, void* stream);
+/* srec_adam_rows (proj_cs NULL) / srec_adam_rows_proj with the second level of a two-level lookup gradient folded in: row i
+ * with u = slot[i] != 0 first adds s = sum of part[cptr[u - 1] .. cptr[u]) (dense rows of d floats, in piece order) to its
+ * gradient and, with radial, <W_i, s> to radial[i] - the bits of srec_scatter_add_sorted_ex(part, .., accumulate = 1) followed by
+ * the plain row pass - then clears slot[i].  G itself is NOT updated.  u_cap = entries of cptr - 1, n_part = rows of part. */
+int srec_adam_rows_lookup(float* W, const float* G, float* M, float* V, int n, int d, int ld, const float* hyper, int use_wd,
+                          float max_norm, int renorm_write, float* cs_out, float cs_scale, int eps_mode, float cs_eps,
+                          const float* proj_cs, float proj_inv_scale, float* radial, void* dst16, int Dp, int* slot,
+                          const float* part, const int* cptr, int u_cap, int n_part, void* stream);
+/* the table's row pass and ONE multi-tensor launch (desc: at most 88 tensors, stepped with multi_hyper) as one launch of two
+ * workgroup ranges; proj_cs / radial nullable as in srec_adam_rows / _proj, slot NULL: no lookup (part, cptr ignored).  The
+ * bits of the two launches apart. */
+int srec_adam_rows_multi(float* W, const float* G, float* M, float* V, int n, int d, int ld, const float* hyper, int use_wd,
+                         float max_norm, int renorm_write, float* cs_out, float cs_scale, int eps_mode, float cs_eps,
+                         const float* proj_cs, float proj_inv_scale, float* radial, void* dst16, int Dp, int* slot,
+                         const float* part, const int* cptr, int u_cap, int n_part, const void* desc, const float* multi_hyper,
+                         void* stream);
 
 /* ---- MSGIFSR MSHGNN layer, all relations of both HeteroGraphConvs in one batched pass (hgat.hip) ------------------
  * Replaces msgifsr.py:70-89 (conv1(g) + conv2(reverse g), relation sum, head max, + session mean) around the fc GEMMs

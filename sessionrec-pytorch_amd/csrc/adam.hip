@@ -16,6 +16,8 @@
 //                  (lessr.py:126, msgifsr.py:162) and the next step's cosine scale
 //                  cs_v = scale/||E_v|| (niser.py:151, msgifsr.py:279) - so the reference's
 //                  per-step full-table normalise passes cost no extra traffic.
+#include <cstdlib>
+
 #include "common.h"
 #include "hyper_role.h"
 
@@ -65,14 +67,93 @@ __global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict_
 // epilogues - W is stored ONCE, already renormalised when renorm_write is set, and dst16 (nullable) receives the bf16 operand
 // copy of the row as the next forward's scoring kernels read it (zero in the columns d .. Dp): the stand-alone
 // renorm + copy pass of the next step (srec_renorm_rows_bf16: 11 us, 57 MB at C3) disappears.
+//
+// slot != NULL: the second level of a two-level lookup gradient (rowops.hip scatter_add_sorted_kernel over the pieces of each
+// item, srec_scatter_add_sorted_ex) is done HERE instead of in a launch of its own in front of this one.  The first level
+// stamped slot[item] = u + 1 (srec_scatter_add_sorted_stamp); a row with a stamp sums its pieces part[cptr[u] .. cptr[u + 1])
+// with that kernel's loop and expressions, so that gradient, radial sum and everything after them keep their bits:
+//   s = sum of the pieces in order;  rdot = wave_sum(sum_c W s);  G' = s + G;  radial' = radial[i] + rdot
+// and clears its stamp.  A row without one (all but <= a few hundred of the table) pays one 4-byte load.
+__device__ __forceinline__ float4 lookup_pieces(const float* __restrict__ g, int ld_g, int beg, int end, int c) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    int e = beg;
+    // 8 row loads in flight, added in order (the second-level launch keeps 16: the additions are sequential either way, so the
+    // depth changes no bit - and 16 float4 in flight would take this kernel from 75 to 89 VGPRs, 6 to 5 waves per SIMD, for
+    // every row of the table; the hottest item of the benchmark's batches has ~50 pieces)
+    for (; e + 8 <= end; e += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float4*>(g + (size_t)(e + k) * ld_g + c);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
+    }
+    for (; e + 4 <= end; e += 4) {
+        const float4 v0 = *reinterpret_cast<const float4*>(g + (size_t)e * ld_g + c);
+        const float4 v1 = *reinterpret_cast<const float4*>(g + (size_t)(e + 1) * ld_g + c);
+        const float4 v2 = *reinterpret_cast<const float4*>(g + (size_t)(e + 2) * ld_g + c);
+        const float4 v3 = *reinterpret_cast<const float4*>(g + (size_t)(e + 3) * ld_g + c);
+        s.x += v0.x; s.y += v0.y; s.z += v0.z; s.w += v0.w;
+        s.x += v1.x; s.y += v1.y; s.z += v1.z; s.w += v1.w;
+        s.x += v2.x; s.y += v2.y; s.z += v2.z; s.w += v2.w;
+        s.x += v3.x; s.y += v3.y; s.z += v3.z; s.w += v3.w;
+    }
+    for (; e < end; ++e) {
+        const float4 v = *reinterpret_cast<const float4*>(g + (size_t)e * ld_g + c);
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    return s;
+}
+
+// gg = s + gg for the columns c .. c + 3 of a stamped row; rdot (want_rdot) takes the lane's share of <W, s>
+__device__ __forceinline__ void lookup_add(float4 s, const float4& wv, float4& gg, bool want_rdot, float& rdot) {
+    // pinned to what the compiler makes of this expression in scatter_add_sorted_kernel: four rounded products (one packed
+    // multiply pair there), added left to right - no multiply-add
+#pragma clang fp contract(off)
+    if (want_rdot) rdot += wv.x * s.x + wv.y * s.y + wv.z * s.z + wv.w * s.w;
+    s.x += gg.x; s.y += gg.y; s.z += gg.z; s.w += gg.w;
+    gg = s;
+}
+__device__ __forceinline__ void lookup_fold(const float* __restrict__ part, int d, int beg, int end, int c, const float4& wv,
+                                            float4& gg, bool want_rdot, float& rdot) {
+    lookup_add(lookup_pieces(part, d, beg, end, c), wv, gg, want_rdot, rdot);
+}
+
+// <p, g> of one float4 group of the HOLD body: p.x g.x + p.y g.y + p.z g.z + p.w g.w with the multiply-adds spelled out.  Left to
+// the compiler, the order of that chain follows the code around it (it was y, x, z, w before the lookup fold existed and x, y, z,
+// w with it: an ulp of the projection coefficient, which Adam turns into whole steps of rows with tiny gradients); this is the
+// order the trained results were produced with.
+__device__ __forceinline__ float row_dot4(const float4& p, const float4& g) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(p.w, g.w, __builtin_fmaf(p.z, g.z, __builtin_fmaf(p.x, g.x, p.y * g.y)));
+}
+
+struct LookupArgs { int* slot; const float* part; const int* cptr; int u_cap, n_part; };
+
+// (the ROWS role of the optimizer launch below: workgroup `blk` of cdiv(n, 4))
 template <bool HOLD>
-__global__ void adam_rows_kernel(float* __restrict__ W, const float* __restrict__ G, float* __restrict__ M,
+__device__ __forceinline__ void adam_rows_body(int blk, float* __restrict__ W, const float* __restrict__ G, float* __restrict__ M,
                                  float* __restrict__ Vv, int n, int d, int ld, const float* __restrict__ hyper,
                                  int use_wd, float max_norm, int renorm_write, float* __restrict__ cs_out, float cs_scale,
                                  int eps_mode, float cs_eps, const float* __restrict__ proj_cs, float proj_inv_scale,
-                                 float* __restrict__ radial, unsigned short* __restrict__ dst16, int Dp) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+                                 float* __restrict__ radial, unsigned short* __restrict__ dst16, int Dp, LookupArgs lk) {
+    const int i = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= n) return;
+    // (wave-uniform) the row's stamp; a value outside the piece table is no stamp of this step's lookup and is only cleared
+    int pbeg = 0, pend = 0;
+    bool stamped = false;
+    if (lk.slot != nullptr) {
+        const int su = lk.slot[i];
+        if (su != 0) {
+            if (su > 0 && su <= lk.u_cap) {
+                pbeg = lk.cptr[su - 1];
+                pend = lk.cptr[su];
+                stamped = pbeg >= 0 && pend <= lk.n_part;
+            }
+            if (lane == 0) lk.slot[i] = 0;
+        }
+    }
+    const bool want_rdot = stamped && radial != nullptr;
+    float rdot = 0.f;
     const Hyper h = load_hyper(hyper);
     const float wd = use_wd ? h.wd : 0.f, step = h.step, rs2 = h.bc2s;
     // the skip scalars of hyper_role ({0, 1, 1, eps, 0, 0, 0, 1}: the Adam arithmetic below keeps every bit): the renorm must
@@ -89,29 +170,50 @@ __global__ void adam_rows_kernel(float* __restrict__ W, const float* __restrict_
     float pcoef = 0.f;
     float4 pw[4], gw[4];
     if (HOLD) {
+        // the piece sums come first, while nothing else of the row is in registers: the loads in flight there must not cost
+        // the unstamped rows - all but a few hundred - their occupancy
+        float4 sw[4];
+        if (stamped) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = lane * 4 + j * 256;
+                sw[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c < d) sw[j] = lookup_pieces(lk.part, d, pbeg, pend, c);
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int c = lane * 4 + j * 256;
             pw[j] = make_float4(0.f, 0.f, 0.f, 0.f); gw[j] = pw[j];
             if (c < d) { pw[j] = *reinterpret_cast<const float4*>(W + off + c); gw[j] = *reinterpret_cast<const float4*>(G + off + c); }
         }
+        if (stamped) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (lane * 4 + j * 256 < d) lookup_add(sw[j], pw[j], gw[j], want_rdot, rdot);
+            if (want_rdot) rdot = wave_sum(rdot);
+        }
     }
     if (proj_cs != nullptr) {
         float dot = 0.f;
         if (HOLD) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) dot += pw[j].x * gw[j].x + pw[j].y * gw[j].y + pw[j].z * gw[j].z + pw[j].w * gw[j].w;
+            for (int j = 0; j < 4; ++j) dot += row_dot4(pw[j], gw[j]);
         } else {
             for (int c = lane * 4; c < d; c += 256) {
                 const float4 pp = *reinterpret_cast<const float4*>(W + off + c);
-                const float4 gg = *reinterpret_cast<const float4*>(G + off + c);
+                float4 gg = *reinterpret_cast<const float4*>(G + off + c);
+                if (stamped) lookup_fold(lk.part, d, pbeg, pend, c, pp, gg, want_rdot, rdot);
                 dot += pp.x * gg.x + pp.y * gg.y + pp.z * gg.z + pp.w * gg.w;
             }
+            if (want_rdot) rdot = wave_sum(rdot);
         }
         dot = wave_sum(dot);
         const float iv = proj_cs[i] * proj_inv_scale;
         if (radial != nullptr) {
-            dot -= radial[i];
+            float rad = radial[i];
+            if (want_rdot) rad += rdot;                     // what `radial[item] += rdot` of the second-level launch left here
+            dot -= rad;
             if (lane == 0) radial[i] = 0.f;
         }
         pcoef = dot * iv * iv;
@@ -164,6 +266,7 @@ __global__ void adam_rows_kernel(float* __restrict__ W, const float* __restrict_
     for (int c = lane * 4; c < d; c += 256) {
         float4 pp = *reinterpret_cast<float4*>(W + off + c);
         float4 gg = *reinterpret_cast<const float4*>(G + off + c);
+        if (stamped) { float unused = 0.f; lookup_fold(lk.part, d, pbeg, pend, c, pp, gg, false, unused); }   // (the same sums again)
         gg.x -= pp.x * pcoef; gg.y -= pp.y * pcoef; gg.z -= pp.z * pcoef; gg.w -= pp.w * pcoef;
         float4 mm = *reinterpret_cast<float4*>(M + off + c);
         float4 vv = *reinterpret_cast<float4*>(Vv + off + c);
@@ -210,11 +313,12 @@ struct MultiArgs {
     int nt;
 };
 
-__global__ __launch_bounds__(256) void adam_multi_kernel(MultiArgs a) {
-    int lo = 0, hi = a.nt;                                   // largest t with blk0[t] <= blockIdx.x
+// (the MULTI role of the optimizer launch below: workgroup `blk` of a.blk0[a.nt])
+__device__ __forceinline__ void adam_multi_body(const MultiArgs& a, int blk) {
+    int lo = 0, hi = a.nt;                                   // largest t with blk0[t] <= blk
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        if (a.blk0[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+        if (a.blk0[mid] <= blk) lo = mid; else hi = mid;
     }
     const int t = lo;
     float* __restrict__ p = a.p[t];
@@ -224,7 +328,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(MultiArgs a) {
     const int n = a.n[t];
     const Hyper h = load_hyper(a.hyper);
     const float wd = ((a.wd_mask[t >> 6] >> (t & 63)) & 1ull) ? h.wd : 0.f, step = h.step, rs2 = h.bc2s;
-    const int e0 = ((int)blockIdx.x - a.blk0[t]) * MCHUNK;
+    const int e0 = (blk - a.blk0[t]) * MCHUNK;
     const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
 #pragma unroll
     for (int u = 0; u < MCHUNK / 1024; ++u) {
@@ -248,31 +352,98 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(MultiArgs a) {
     }
 }
 
+// The optimizer's launch: two workgroup ranges, ROWS (the item table, adam_rows_body) and MULTI (the small tensors of the merged
+// groups, adam_multi_body), each with its own step scalars - the rows are different, the hyper blocks are different, neither role
+// reads what the other writes.  With both filled (srec_adam_rows_multi) a training step has one kernel node less and the tail
+// of one role runs under the other; a launch with one role (srec_adam_rows / _proj / _lookup, srec_adam_multi) is the same body
+// under a kernel of its own, without the other role's arguments (3.5 KB of descriptor) or registers.
+// multi_first: the MULTI workgroups (4096 elements of four arrays each: ~4 x the bytes of a ROWS workgroup at d 256) take the
+// low workgroup indices.
+struct RowsArgs {
+    float* W; const float* G; float* M; float* Vv; int n, d, ld; const float* hyper; int use_wd; float max_norm; int renorm_write;
+    float* cs_out; float cs_scale; int eps_mode; float cs_eps; const float* proj_cs; float proj_inv_scale; float* radial;
+    unsigned short* dst16; int Dp; LookupArgs lk;
+};
+
+template <bool HOLD>
+__device__ __forceinline__ void adam_rows_role(const RowsArgs& r, int blk) {
+    adam_rows_body<HOLD>(blk, r.W, r.G, r.M, r.Vv, r.n, r.d, r.ld, r.hyper, r.use_wd, r.max_norm, r.renorm_write, r.cs_out,
+                         r.cs_scale, r.eps_mode, r.cs_eps, r.proj_cs, r.proj_inv_scale, r.radial, r.dst16, r.Dp, r.lk);
+}
+
+template <bool HOLD>
+__global__ void adam_rows_kernel(RowsArgs r) { adam_rows_role<HOLD>(r, (int)blockIdx.x); }
+
+__global__ __launch_bounds__(256) void adam_multi_kernel(MultiArgs a) { adam_multi_body(a, (int)blockIdx.x); }
+
+template <bool HOLD>
+__global__ __launch_bounds__(256) void adam_rows_kernel_with_multi(RowsArgs r, int rows_blocks, int multi_blocks, int multi_first,
+                                                                   MultiArgs a) {
+    const int b = (int)blockIdx.x;
+    const bool multi = multi_first ? b < multi_blocks : b >= rows_blocks;
+    if (multi) {
+        adam_multi_body(a, multi_first ? b : b - rows_blocks);
+        return;
+    }
+    adam_rows_role<HOLD>(r, multi_first ? b - multi_blocks : b);
+}
+
+struct MultiDesc { int nt; const int* use_wd; const long* numel; float* const* p; const float* const* g; float* const* m; float* const* v; };
+
+// tensors [t0, t0 + a.nt) of the host descriptor -> kernel arguments; -> the MULTI role's workgroup count, or -1
+int multi_fill(const MultiDesc* d, int t0, const float* hyper, MultiArgs& a) {
+    a.nt = d->nt - t0 < MT ? d->nt - t0 : MT;
+    a.hyper = hyper;
+    int blocks = 0;
+    for (int t = 0; t < a.nt; ++t) {
+        const int s = t0 + t;
+        if (d->numel[s] <= 0 || d->numel[s] > 0x7fffffffL || d->p[s] == nullptr || d->g[s] == nullptr ||
+            d->m[s] == nullptr || d->v[s] == nullptr || (((uintptr_t)d->p[s] | (uintptr_t)d->g[s] | (uintptr_t)d->m[s] | (uintptr_t)d->v[s]) & 3))
+            return -1;
+        a.p[t] = d->p[s]; a.g[t] = d->g[s]; a.m[t] = d->m[s]; a.v[t] = d->v[s];
+        a.n[t] = (int)d->numel[s];
+        if (d->use_wd[s]) a.wd_mask[t >> 6] |= 1ull << (t & 63);
+        a.blk0[t] = blocks;
+        blocks += (a.n[t] + MCHUNK - 1) / MCHUNK;
+    }
+    a.blk0[a.nt] = blocks;
+    return blocks;
+}
+
+int role_order() {
+    static const int order = [] { const char* e = getenv("SREC_ADAM_ROLE_ORDER"); return (e != nullptr && e[0] == 'r') ? 0 : 1; }();
+    return order;                                  // 1: MULTI first (the default, measured: profiles/r07_notes.md); "rows": ROWS first
+}
+
+void tail_launch(const RowsArgs& r, int rows_blocks, const MultiArgs& a, int multi_blocks, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const bool hold = r.d <= 1024;
+    if (rows_blocks > 0 && multi_blocks > 0) {
+        if (hold)
+            hipLaunchKernelGGL(adam_rows_kernel_with_multi<true>, dim3(rows_blocks + multi_blocks), dim3(256), 0, st, r, rows_blocks,
+                               multi_blocks, role_order(), a);
+        else
+            hipLaunchKernelGGL(adam_rows_kernel_with_multi<false>, dim3(rows_blocks + multi_blocks), dim3(256), 0, st, r, rows_blocks,
+                               multi_blocks, role_order(), a);
+    } else if (rows_blocks > 0) {
+        if (hold) hipLaunchKernelGGL(adam_rows_kernel<true>, dim3(rows_blocks), dim3(256), 0, st, r);
+        else hipLaunchKernelGGL(adam_rows_kernel<false>, dim3(rows_blocks), dim3(256), 0, st, r);
+    } else if (multi_blocks > 0) {
+        hipLaunchKernelGGL(adam_multi_kernel, dim3(multi_blocks), dim3(256), 0, st, a);
+    }
+}
+
 }  // namespace
 
 // desc: HOST srec_adam_multi_desc (srec.h) - nt tensors {p, g, m, v, numel, use_wd}; any nt (launched MT at a time).
 extern "C" int srec_adam_multi(const void* desc_, const float* hyper, void* stream) {
-    struct Desc { int nt; const int* use_wd; const long* numel; float* const* p; const float* const* g; float* const* m; float* const* v; };
-    const Desc* d = (const Desc*)desc_;
+    const MultiDesc* d = (const MultiDesc*)desc_;
     if (d == nullptr || d->nt < 0 || hyper == nullptr) return SREC_BAD_ARG;
     for (int t0 = 0; t0 < d->nt; t0 += MT) {
         MultiArgs a{};
-        a.nt = d->nt - t0 < MT ? d->nt - t0 : MT;
-        a.hyper = hyper;
-        int blocks = 0;
-        for (int t = 0; t < a.nt; ++t) {
-            const int s = t0 + t;
-            if (d->numel[s] <= 0 || d->numel[s] > 0x7fffffffL || d->p[s] == nullptr || d->g[s] == nullptr ||
-                d->m[s] == nullptr || d->v[s] == nullptr || (((uintptr_t)d->p[s] | (uintptr_t)d->g[s] | (uintptr_t)d->m[s] | (uintptr_t)d->v[s]) & 3))
-                return SREC_BAD_ARG;
-            a.p[t] = d->p[s]; a.g[t] = d->g[s]; a.m[t] = d->m[s]; a.v[t] = d->v[s];
-            a.n[t] = (int)d->numel[s];
-            if (d->use_wd[s]) a.wd_mask[t >> 6] |= 1ull << (t & 63);
-            a.blk0[t] = blocks;
-            blocks += (a.n[t] + MCHUNK - 1) / MCHUNK;
-        }
-        a.blk0[a.nt] = blocks;
-        hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+        const int blocks = multi_fill(d, t0, hyper, a);
+        if (blocks < 0) return SREC_BAD_ARG;
+        tail_launch(RowsArgs{}, 0, a, blocks, stream);
     }
     SREC_LAUNCH_CHECK();
     return 0;
@@ -334,20 +505,27 @@ extern "C" int srec_adam_flat(float* p, const float* g, float* m, float* v, long
     return 0;
 }
 
+// desc (nullable): the small tensors of ONE multi-tensor launch (<= MT of them) that ride in the same launch, with multi_hyper
 static int adam_rows_run(float* W, const float* G, float* M, float* V, int n, int d, int ld, const float* hyper, int use_wd,
                          float max_norm, int renorm_write, float* cs_out, float cs_scale, int eps_mode, float cs_eps,
-                         const float* proj_cs, float proj_inv_scale, float* radial, void* dst16, int Dp, void* stream) {
-    if (n <= 0) return 0;
-    if (d <= 0 || (d & 3) || (ld & 3)) return SREC_BAD_ARG;
-    if (dst16 != nullptr && (d > 1024 || Dp < d || (Dp & 3) || Dp > 1024)) return SREC_BAD_ARG;
-    if (d <= 1024)
-        hipLaunchKernelGGL(adam_rows_kernel<true>, dim3(cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, W, G, M, V, n, d, ld, hyper,
-                           use_wd, max_norm, renorm_write, cs_out, cs_scale, eps_mode, cs_eps, proj_cs, proj_inv_scale, radial,
-                           (unsigned short*)dst16, Dp);
-    else
-        hipLaunchKernelGGL(adam_rows_kernel<false>, dim3(cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, W, G, M, V, n, d, ld, hyper,
-                           use_wd, max_norm, renorm_write, cs_out, cs_scale, eps_mode, cs_eps, proj_cs, proj_inv_scale, radial,
-                           (unsigned short*)nullptr, 0);
+                         const float* proj_cs, float proj_inv_scale, float* radial, void* dst16, int Dp, void* stream,
+                         LookupArgs lk = LookupArgs{nullptr, nullptr, nullptr, 0, 0}, const void* desc = nullptr,
+                         const float* multi_hyper = nullptr) {
+    MultiArgs a{};
+    int multi_blocks = 0;
+    if (desc != nullptr) {
+        const MultiDesc* md = (const MultiDesc*)desc;
+        if (md->nt < 0 || md->nt > MT || multi_hyper == nullptr) return SREC_BAD_ARG;
+        multi_blocks = md->nt > 0 ? multi_fill(md, 0, multi_hyper, a) : 0;
+        if (multi_blocks < 0) return SREC_BAD_ARG;
+    }
+    if (n <= 0 && multi_blocks == 0) return 0;
+    if (n > 0 && (d <= 0 || (d & 3) || (ld & 3))) return SREC_BAD_ARG;
+    if (n > 0 && dst16 != nullptr && (d > 1024 || Dp < d || (Dp & 3) || Dp > 1024)) return SREC_BAD_ARG;
+    const bool hold = d <= 1024;
+    RowsArgs r{W, G, M, V, n, d, ld, hyper, use_wd, max_norm, renorm_write, cs_out, cs_scale, eps_mode, cs_eps, proj_cs,
+               proj_inv_scale, radial, hold ? (unsigned short*)dst16 : (unsigned short*)nullptr, hold ? Dp : 0, lk};
+    tail_launch(r, n > 0 ? cdiv(n, 4) : 0, a, multi_blocks, stream);
     SREC_LAUNCH_CHECK();
     return 0;
 }
@@ -369,4 +547,35 @@ extern "C" int srec_adam_rows_proj(float* W, const float* G, float* M, float* V,
     if (proj_cs == nullptr) return SREC_BAD_ARG;
     return adam_rows_run(W, G, M, V, n, d, ld, hyper, use_wd, max_norm, renorm_write, cs_out, cs_scale, eps_mode, cs_eps, proj_cs,
                          proj_inv_scale, radial, dst16, Dp, stream);
+}
+
+// the row pass (projection when proj_cs != NULL) that also performs the second level of a two-level lookup gradient: see
+// adam_rows_kernel (slot) and srec.h
+extern "C" int srec_adam_rows_lookup(float* W, const float* G, float* M, float* V, int n, int d, int ld, const float* hyper,
+                                     int use_wd, float max_norm, int renorm_write, float* cs_out, float cs_scale, int eps_mode,
+                                     float cs_eps, const float* proj_cs, float proj_inv_scale, float* radial, void* dst16, int Dp,
+                                     int* slot, const float* part, const int* cptr, int u_cap, int n_part, void* stream) {
+    if (slot == nullptr || part == nullptr || cptr == nullptr || u_cap < 0 || n_part < 0) return SREC_BAD_ARG;
+    if (proj_cs == nullptr && radial != nullptr) return SREC_BAD_ARG;
+    if (((uintptr_t)part & 15) != 0) return SREC_BAD_ARG;
+    return adam_rows_run(W, G, M, V, n, d, ld, hyper, use_wd, max_norm, renorm_write, cs_out, cs_scale, eps_mode, cs_eps, proj_cs,
+                         proj_inv_scale, radial, dst16, Dp, stream, LookupArgs{slot, part, cptr, u_cap, n_part});
+}
+
+// srec_adam_rows_proj / srec_adam_rows_lookup (slot NULL: no lookup) and srec_adam_multi (desc: <= 88 tensors, its own step
+// scalars multi_hyper) as ONE launch
+extern "C" int srec_adam_rows_multi(float* W, const float* G, float* M, float* V, int n, int d, int ld, const float* hyper,
+                                    int use_wd, float max_norm, int renorm_write, float* cs_out, float cs_scale, int eps_mode,
+                                    float cs_eps, const float* proj_cs, float proj_inv_scale, float* radial, void* dst16, int Dp,
+                                    int* slot, const float* part, const int* cptr, int u_cap, int n_part, const void* desc,
+                                    const float* multi_hyper, void* stream) {
+    if (desc == nullptr || multi_hyper == nullptr || hyper == nullptr) return SREC_BAD_ARG;
+    if (proj_cs == nullptr && radial != nullptr) return SREC_BAD_ARG;
+    LookupArgs lk{nullptr, nullptr, nullptr, 0, 0};
+    if (slot != nullptr) {
+        if (part == nullptr || cptr == nullptr || u_cap < 0 || n_part < 0 || ((uintptr_t)part & 15) != 0) return SREC_BAD_ARG;
+        lk = LookupArgs{slot, part, cptr, u_cap, n_part};
+    }
+    return adam_rows_run(W, G, M, V, n, d, ld, hyper, use_wd, max_norm, renorm_write, cs_out, cs_scale, eps_mode, cs_eps, proj_cs,
+                         proj_inv_scale, radial, dst16, Dp, stream, lk, desc, multi_hyper);
 }

@@ -70,10 +70,19 @@ __global__ void scatter_add_sorted_kernel(const float* __restrict__ g, int ld_g,
                                           float* __restrict__ dst, int ld_dst, int u_cap,
                                           const int* __restrict__ dyn, int d, int accumulate, srec_rng rng,
                                           const float* __restrict__ projW = nullptr, int ld_w = 0,
-                                          float* __restrict__ radial = nullptr) {
+                                          float* __restrict__ radial = nullptr,
+                                          const int* __restrict__ stamp_items = nullptr, int stamp_cap = 0,
+                                          const int* __restrict__ stamp_dyn = nullptr, int* __restrict__ slot = nullptr) {
     // radial (nullable; deferred row-normalisation projection, see srec_adam_rows_proj): radial[item] += <W_item, sum> - the
     // part of THIS gradient along the item's row, which the projection applied later to the whole buffer must not remove
     const int u = blockIdx.x * WPB + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    // slot (nullable; srec_scatter_add_sorted_stamp): this launch is the FIRST level of a two-level lookup gradient and the
+    // optimizer's row pass will sum the pieces itself - wavefront u tells it where: slot[stamp_items[u]] = u + 1 (a side job
+    // of the first stamp_cap wavefronts, whatever segment they sum; the distinct items make the writes disjoint)
+    if (slot != nullptr && lane == 0 && u < dyn_count(stamp_dyn, stamp_cap)) {
+        const int it = stamp_items[u];
+        if (it >= 0) slot[it] = u + 1;
+    }
     if (u >= dyn_count(dyn, u_cap)) return;
     const int beg = ptr[u], end = ptr[u + 1], item = items[u];
     if (item < 0) return;                             // row owned by another shard
@@ -656,6 +665,24 @@ extern "C" int srec_scatter_add_sorted_ex(const float* g, int ld_g, const int* i
     hipLaunchKernelGGL(scatter_add_sorted_kernel, dim3(cdiv(u_cap, WPB)), dim3(256), 0, (hipStream_t)stream, g, ld_g,
                        items, ptr, pos, dst, ld_dst, u_cap, dyn, d, accumulate,
                        srec_rng{(unsigned)seed, counter, (unsigned)salt, p}, projW, ld_w, radial);
+    SREC_LAUNCH_CHECK();
+    return 0;
+}
+
+// srec_scatter_add_sorted_ex without the radial sum, as the first level of a two-level lookup gradient whose second level the
+// optimizer's row pass does (srec_adam_rows_lookup): also stamps slot[stamp_items[u]] = u + 1 for u < min(*stamp_dyn, stamp_cap)
+// with stamp_items[u] >= 0.  stamp_cap <= u_cap: one wavefront per stamp.
+extern "C" int srec_scatter_add_sorted_stamp(const float* g, int ld_g, const int* items, const int* ptr, const int* pos,
+                                             float* dst, int ld_dst, int u_cap, const int* dyn, int d, int accumulate,
+                                             float p, int seed, const int* counter, int salt, const int* stamp_items,
+                                             int stamp_cap, const int* stamp_dyn, int* slot, void* stream) {
+    if (u_cap <= 0) return stamp_cap > 0 ? SREC_BAD_ARG : 0;
+    if (bad_row_args(d, ld_g) || (ld_dst & 3) || p < 0.f || p >= 1.f || (p > 0.f && ld_g != d)) return SREC_BAD_ARG;
+    if (stamp_cap < 0 || stamp_cap > u_cap || (stamp_cap > 0 && (stamp_items == nullptr || slot == nullptr))) return SREC_BAD_ARG;
+    hipLaunchKernelGGL(scatter_add_sorted_kernel, dim3(cdiv(u_cap, WPB)), dim3(256), 0, (hipStream_t)stream, g, ld_g,
+                       items, ptr, pos, dst, ld_dst, u_cap, dyn, d, accumulate,
+                       srec_rng{(unsigned)seed, counter, (unsigned)salt, p}, (const float*)nullptr, 0, (float*)nullptr,
+                       stamp_items, stamp_cap, stamp_dyn, stamp_cap > 0 ? slot : (int*)nullptr);
     SREC_LAUNCH_CHECK();
     return 0;
 }

@@ -468,6 +468,55 @@ class TableGrad:
         self.pending = None
         self.radial = torch.zeros(weight.shape[0], device=weight.device, dtype=torch.float32) if defer else None
         self.radial_dirty = False    # a lookup backward has added radial sums that no row pass has consumed yet
+        # Lookup gradient summed by the row pass (two-level lookup backward under a pending projection, SREC_LOOKUP_IN_ROWPASS):
+        # the first level stamps slot[item] = u + 1 and the backward records lookup = (part, cptr, items, dyn_u) INSTEAD of
+        # launching the second level; the optimizer's row pass (srec_adam_rows_lookup) sums the pieces of every stamped row
+        # into the gradient as it reads it, adds their radial part, and clears the stamps.  `lookup` keeps `part` alive until
+        # that launch has been issued (under capture it lives in the graph's pool).  slot is all zero whenever lookup is None
+        # and slot_dirty is False.  Any other reader goes through materialize(), which runs the second level after all.
+        self.slot = torch.zeros(weight.shape[0], device=weight.device, dtype=torch.int32) if defer else None
+        self.lookup = None
+        self.slot_dirty = False      # stamps that no row pass has cleared
+
+    def lookup_in_rowpass(self):
+        """may a two-level lookup backward leave its second level to the optimizer's row pass?"""
+        return self.defer and self.slot is not None and self.pending is not None \
+            and os.environ.get('SREC_LOOKUP_IN_ROWPASS', '1') != '0'
+
+    def hand_over(self, part, cptr, items, dyn_u):
+        assert self.lookup is None
+        self.lookup = (part, cptr, items, dyn_u)
+        self.slot_dirty = True
+        self.radial_dirty = True
+
+    def take_lookup(self):
+        """the row pass consumes the recorded lookup (its launch clears the stamps)"""
+        lk, self.lookup = self.lookup, None
+        self.slot_dirty = False
+        return lk
+
+    def flush_lookup(self):
+        """a recorded lookup goes through the second-level launch after all (another reader than the row pass; a second lookup
+        backward before the step): buf and radial as if it had never been deferred, stamps cleared"""
+        if self.lookup is not None:
+            part, cptr, items, dyn_u = self.lookup
+            d = self.buf.shape[1]
+            ar = _arange(part.shape[0] + 1, part.device)
+            if self.pending is not None:
+                table = self.pending[0]
+                lib.srec_scatter_add_sorted_ex(ptr(part), d, ptr(items), ptr(cptr), ptr(ar), ptr(self.buf), self.buf.stride(0),
+                                               items.numel(), ptr(dyn_u), d, 1, 0.0, 0, None, 0, ptr(table), table.stride(0),
+                                               ptr(self.radial), stream())
+            else:
+                lib.srec_scatter_add_sorted(ptr(part), d, ptr(items), ptr(cptr), ptr(ar), ptr(self.buf), self.buf.stride(0),
+                                            items.numel(), ptr(dyn_u), d, 1, stream())
+            self.lookup = None
+        self._clear_slot()
+
+    def _clear_slot(self):
+        if self.slot is not None and self.slot_dirty:         # (never in the regular backward -> step sequence)
+            self.slot.zero_()
+        self.slot_dirty = False
 
     def overwritten(self):
         """the scoring backward has just overwritten every row of `buf` (non-accumulating): whatever an earlier backward
@@ -475,6 +524,8 @@ class TableGrad:
         into the old contents (a skipped / NaN-guarded step, two backwards before a step, a training loss evaluated
         without stepping) - belongs to the old contents and goes with them"""
         self.pending = None
+        self.lookup = None                                    # (its rows were meant for the old contents)
+        self._clear_slot()
         if self.radial is not None and self.radial_dirty:     # (never in the regular backward -> step sequence: no fill
             self.radial.zero_()                               #  kernel in a captured step)
         self.radial_dirty = False
@@ -486,6 +537,7 @@ class TableGrad:
 
     def materialize(self):
         """apply a pending projection to `buf` (after it, buf is the true table gradient)"""
+        self.flush_lookup()
         if self.pending is not None:
             table, cs, inv_scale = self.pending
             lib.srec_rownorm_project_radial(ptr(table), table.stride(0), ptr(cs), float(inv_scale), ptr(self.buf),
@@ -546,6 +598,18 @@ class EmbeddingLookup(torch.autograd.Function):
             C = chunk_ptr.numel() - 1
             part = torch.empty(max(C, 1), d, device=g.device, dtype=torch.float32)
             ar = _arange(C + 1, g.device)
+            if radial is not None and tg.lookup_in_rowpass() and 0 < items.numel() <= C and tg.buf.stride(0) == d:
+                # the optimizer's row pass sums the pieces of each item itself (TableGrad.slot / lookup): no second-level launch.
+                # An earlier lookup of this step that still waits goes through its second-level launch first.
+                tg.flush_lookup()
+                pdrop, seed, cnt, salt = ctx.drop if ctx.drop is not None else (0.0, 0, None, 0)
+                lib.srec_scatter_add_sorted_stamp(ptr(g), _ld(g), ptr(ar), ptr(chunk_ptr), ptr(upos), ptr(part), d, C, None, d, 0,
+                                                  pdrop, seed, cnt, salt, ptr(items), items.numel(), ptr(ctx.dyn_u), ptr(tg.slot),
+                                                  stream())
+                tg.hand_over(part, cptr, items, ctx.dyn_u)
+                return ret, None, None, None, None, None, None
+            if tg is not None:
+                tg.flush_lookup()                           # (order of the additions into buf / radial: as the backwards ran)
             first_level(ptr(g), _ld(g), ptr(ar), ptr(chunk_ptr), ptr(upos), ptr(part), d, C, None, 0)   # padded chunks are
             if radial is not None:                                                                          # empty segments
                 lib.srec_scatter_add_sorted_ex(ptr(part), d, ptr(items), ptr(cptr), ptr(ar), ptr(dst), dst.stride(0),
@@ -555,6 +619,7 @@ class EmbeddingLookup(torch.autograd.Function):
                 lib.srec_scatter_add_sorted(ptr(part), d, ptr(items), ptr(cptr), ptr(ar), ptr(dst), dst.stride(0),
                                             items.numel(), ptr(ctx.dyn_u), d, acc, stream())
         elif radial is not None:
+            tg.flush_lookup()
             pdrop, seed, cnt, salt = ctx.drop if ctx.drop is not None else (0.0, 0, None, 0)
             lib.srec_scatter_add_sorted_ex(ptr(g), _ld(g), ptr(items), ptr(uptr), ptr(upos), ptr(dst), dst.stride(0),
                                            items.numel(), ptr(ctx.dyn_u), d, acc, pdrop, seed, cnt, salt, ptr(ptable),

@@ -13,11 +13,13 @@ of `launch()` replays correctly however far the host runs ahead; `advance()` is 
 plus a stream-ordered config copy when the lr schedule changed a group.
 """
 import ctypes as _ct
+import os
 
 import torch
 
 from ._lib import STRUCTS, lib, ptr, ptr_array, stream
 
+_MULTI_PER_LAUNCH = 88      # tensors of one multi-tensor launch (csrc/adam.hip MT): a longer list is several launches
 _AdamMultiDesc = STRUCTS['srec_adam_multi_desc']      # bound from include/srec.h; its members are HOST arrays, passed by address
 
 
@@ -274,6 +276,7 @@ class FusedAdam(torch.optim.Optimizer):
         # small tensors of ALL groups that step together: groups which differ only in weight decay (fix_weight_decay: the
         # biases / norms are the same Adam with wd 0) share ONE multi-tensor launch - the kernel takes the decay per tensor
         merged = {}                          # (lr, betas, eps, slot) -> [gi of the hyper to use, wd of it, rows]
+        rows_wait = None                     # the table's row pass, recorded and not launched yet (see below)
         for gi, group, items in work:
             if not items:
                 continue
@@ -313,19 +316,30 @@ class FusedAdam(torch.optim.Optimizer):
                     shard = getattr(model, 'shard', None)
                     n_rows = shard.n_live if (shard is not None and 0 < shard.n_live < p.shape[0]) else p.shape[0]
                     pend = tgrad.pending if (tgrad is not None and g.data_ptr() == tgrad.buf.data_ptr()) else None
+                    if pend is not None and tgrad.lookup is not None and (n_rows != p.shape[0] or p.stride(0) != g.stride(0)):
+                        tgrad.flush_lookup()          # (a pass that stops short of the table's last row cannot clear every stamp)
+                    rows_args = (ptr(p), ptr(g), ptr(state['exp_avg']), ptr(state['exp_avg_sq']), n_rows, p.shape[1], p.stride(0),
+                                 ptr(hyper), use_wd, mn, renorm_write, ptr(cs_out), cs_scale, eps_mode, 1e-12)
+                    proj_args, lk_args, part = (None, 0.0, None), (None, None, None, 0, 0), None
                     if pend is not None:
-                        lib.srec_adam_rows_proj(ptr(p), ptr(g), ptr(state['exp_avg']), ptr(state['exp_avg_sq']), n_rows,
-                                                p.shape[1], p.stride(0), ptr(hyper), use_wd, mn, renorm_write, ptr(cs_out), cs_scale,
-                                                eps_mode, 1e-12, ptr(pend[1]), float(pend[2]), ptr(tgrad.radial), ptr(d16), dp16,
-                                                stream())
+                        proj_args = (ptr(pend[1]), float(pend[2]), ptr(tgrad.radial))
+                        if tgrad.lookup is not None:
+                            # the lookup backward left the second level of its row sums to this pass (ops.TableGrad.slot / lookup);
+                            # `part` stays referenced until the launch is issued (under capture it lives in the graph's pool)
+                            part, cptr, items, _ = tgrad.take_lookup()
+                            lk_args = (ptr(tgrad.slot), ptr(part), ptr(cptr), items.numel(), part.shape[0])
                         tgrad.pending = None
                         tgrad.radial_dirty = False
+                    elif tgrad is not None:
+                        tgrad.materialize()
+                    rows_call = (rows_args, proj_args, (ptr(d16), dp16), lk_args, part, p.device)
+                    # one optimizer launch: the row pass waits for the multi-tensor launch of the small tensors and shares its
+                    # launch (srec_adam_rows_multi) - unless a gradient join sits between them (the sharded job's bucket stream:
+                    # the row pass needs none of the replicated gradients and goes first, as it always did)
+                    if self.grad_join is None and os.environ.get('SREC_ADAM_ONE_LAUNCH', '1') != '0':
+                        rows_wait = rows_call
                     else:
-                        if tgrad is not None:
-                            tgrad.materialize()
-                        lib.srec_adam_rows(ptr(p), ptr(g), ptr(state['exp_avg']), ptr(state['exp_avg_sq']), n_rows,
-                                           p.shape[1], p.stride(0), ptr(hyper), use_wd, mn, renorm_write, ptr(cs_out), cs_scale,
-                                           eps_mode, 1e-12, ptr(d16), dp16, stream())
+                        self._rows_launch(rows_call)
                     if fold:
                         # (renormalised rows in place, bf16 copy written): consumed by the model's next _prepare_table / _table_bf16
                         st['table_prepared'] = (bool(renorm_write) or mn_model <= 0, tb is not None, p._version)
@@ -333,6 +347,8 @@ class FusedAdam(torch.optim.Optimizer):
                         st['cs_fresh'] = True
                 else:
                     self._join_grads()
+                    if is_table and tgrad is not None:
+                        tgrad.flush_lookup()          # (a lookup backward left its second level to a row pass: this route has none)
                     lib.srec_adam_flat(ptr(p), ptr(g), ptr(state['exp_avg']), ptr(state['exp_avg_sq']), p.numel(),
                                        ptr(hyper), use_wd, stream())
             for slot, rows in multi.items():
@@ -357,11 +373,34 @@ class FusedAdam(torch.optim.Optimizer):
                     ptr_array([r[2]['exp_avg'] for r in rows]), ptr_array([r[2]['exp_avg_sq'] for r in rows])]
             desc = _AdamMultiDesc(nt, *[_ct.addressof(a) for a in keep])       # (keep: alive across the call)
             hyper = self._buffers(gi, slot, rows[0][0].device)['hyper']
+            if rows_wait is not None and nt <= _MULTI_PER_LAUNCH and rows[0][0].device == rows_wait[5]:
+                self._rows_launch(rows_wait, (_ct.addressof(desc), ptr(hyper)))      # the first group rides with the row pass
+                rows_wait = None
+                continue
+            if rows_wait is not None:
+                self._rows_launch(rows_wait)
+                rows_wait = None
             lib.srec_adam_multi(_ct.addressof(desc), ptr(hyper), stream())
+        if rows_wait is not None:
+            self._rows_launch(rows_wait)
         if tgrad is not None:
             tgrad.fresh = False
         from . import ops
         ops.weights_changed()
+
+    @staticmethod
+    def _rows_launch(call, multi=None):
+        """issue a recorded row pass of the table: alone (the entry point today's arguments select), or with the multi-tensor
+        launch multi = (descriptor address, its step scalars) in the same launch"""
+        rows_args, proj_args, d16_args, lk_args, _part, _ = call
+        if multi is not None:
+            lib.srec_adam_rows_multi(*rows_args, *proj_args, *d16_args, *lk_args, *multi, stream())
+        elif lk_args[0] is not None:
+            lib.srec_adam_rows_lookup(*rows_args, *proj_args, *d16_args, *lk_args, stream())
+        elif proj_args[0] is not None:
+            lib.srec_adam_rows_proj(*rows_args, *proj_args, *d16_args, stream())
+        else:
+            lib.srec_adam_rows(*rows_args, *d16_args, stream())
 
     grad_join = None          # callable: make the all-reduced replicated gradients (grad_override) visible to the compute stream -
     #                           dist.VocabParallel leaves the join of its side stream to the optimizer, which calls it AFTER the
