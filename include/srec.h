@@ -392,6 +392,16 @@ int srec_hg_drop_prep(const float* x, const float* cnt, int rows, int D, float p
 /* ... and, in the same pass, xc16 [2, rows, D] = bf16(xc): the operand copy the bf16 projection GEMM reads */
 int srec_hg_drop_prep16(const float* x, const float* cnt, int rows, int D, float p, int seed, const int* counter, int salt,
                         float* ms, float* xc, float* rm, float* xres, float pa, long na, float* mk, void* xc16, void* stream);
+/* live-source rows of every projection block of desc (HOST srec_hg_desc; only its topology is read): lists = HOST array of n_blocks
+ * device pointers, lists[b] [ncap of the block's type] int32 <- ascending type-local rows u < *dyn_n with an out-edge
+ * (out_ptr[i][u + 1] > out_ptr[i][u]) in at least one instance i whose SOURCE block is b; counts [n_blocks] (device) <- their
+ * numbers.  A projection row is read only through the source index of such an edge (srec_hg_fwd / srec_hg_bwd), so the projection
+ * GEMM may skip every row that is not listed (srec_gemm16_nt_rows).  One workgroup per block; at most 4 source instances per block. */
+int srec_hg_live_rows(const void* desc, const void* lists, int* counts, void* stream);
+/* ... srec_hg_drop_prep16 with srec_hg_live_rows(desc, lists, counts) as one more workgroup range of its launch */
+int srec_hg_drop_prep16_live(const float* x, const float* cnt, int rows, int D, float p, int seed, const int* counter, int salt,
+                             float* ms, float* xc, float* rm, float* xres, float pa, long na, float* mk, void* xc16,
+                             const void* desc, const void* lists, int* counts, void* stream);
 /* (ms of srec_hg_drop_prep / _prep16 is nullable: srec_hg_drop_merge with ms = NULL recomputes the masks from p / seed / counter /
  * salt, the mask tensor is then neither written nor read) */
 int srec_hg_drop_merge(const float* t, int S, const float* ms, long n, float* dx, float p, int seed, const int* counter,
@@ -430,6 +440,11 @@ int srec_gemm_f32_group_run_defer(const void* desc, float* ws, long ws_floats, l
  *   srec_weights_bf16: n <= 8 matrices W_i [R_i, C_i] fp32 -> bf16 copy and transposed bf16 copy [C_i, R_i] in one launch;
  *                   W / W16 / WT16 are HOST arrays of n device pointers (WT16 entries may be NULL), R / Cc HOST int arrays. */
 int srec_gemm16_nt(const void* desc, void* stream);
+/* srec_gemm16_nt over row lists: rows = HOST array of np device pointers (a NULL entry: that problem takes all rows).  Problem p
+ * computes the rows rows[p][0 .. *dyn[p]) of C_p only - ascending int32 row numbers < M, dyn[p] = the list's device count - from the
+ * same rows of A_p; every other row of C_p is left unwritten, a listed row gets the bytes srec_gemm16_nt gives it.  bf16 output
+ * with SREC_G16_KEEP_DEAD only (the forward projections over the live-source rows of srec_hg_live_rows). */
+int srec_gemm16_nt_rows(const void* desc, const void* rows, void* stream);
 int srec_gemm16_tn(const void* desc, void* stream);
 int srec_rows_bf16(const float* src, int ld, int n, const int* dyn, int d, void* dst16, void* stream);
 /* out [C, n] = sum_r part [C, R, n] in fixed order (the row-split weight-gradient products of one module), n % 4 == 0 */

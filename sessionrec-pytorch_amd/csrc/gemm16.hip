@@ -36,6 +36,7 @@ struct G16Args {
     const unsigned short* B[G16_MAXP][G16_MAXS];
     void* C[G16_MAXP];
     const int* dyn[G16_MAXP];
+    const int* rows[G16_MAXP];    // nt with a row list (srec_gemm16_nt_rows): tile row r is row rows[r] of A and C, *dyn of them; NULL = all rows
     int M[G16_MAXP], N[G16_MAXP], K[G16_MAXP], nseg[G16_MAXP], koff[G16_MAXP], nsplit[G16_MAXP], start[G16_MAXP + 1];
     int np, lda, ldb, ldc;
     int ldap[G16_MAXP], ldbp[G16_MAXP], ldcp[G16_MAXP];   // per-problem leading dimensions (the group's lda / ldb / ldc unless overridden)
@@ -107,8 +108,13 @@ constexpr int NS = 4, PD = 3;        // default LDS ring: 4 stages, 3 stages of 
 // per CU.  Piece p of tile row r sits in slot p ^ ((r >> 2) & 3): the 16 lanes of every ds_read_b128 group hit 16
 // distinct 16-B slots.
 // NW: waves per workgroup, 2 x (NW / 2)
-template <int TM, int TN, bool C16, int BK = 32, int NS = 4, int NW = 4>
+// RL: problems may carry a row list (G16Args.rows): the tile's TM row indices are loaded once into LDS and become the per-lane
+// LDS-DMA source rows and the store rows of the epilogue.  K loop and per-row arithmetic are those of RL = false: a listed row of C
+// gets the bytes the unlisted launch gives it; rows outside the list are not written.
+template <int TM, int TN, bool C16, int BK = 32, int NS = 4, int NW = 4, bool RL = false>
 __global__ __launch_bounds__(64 * NW) void gemm16_nt_kernel(G16Args g) {
+    static_assert(!RL || (C16 && TM <= 64 * NW), "row lists: bf16-output launches only, one index per thread");
+    __shared__ int rows_s[RL ? TM : 1];
     constexpr int WN = NW / 2, NT = 64 * NW;          // waves along N, threads
     constexpr int PD = NS - 1;
     constexpr int RPI = 512 / BK;                        // tile rows per DMA instruction (1 KiB)
@@ -155,6 +161,13 @@ __global__ __launch_bounds__(64 * NW) void gemm16_nt_kernel(G16Args g) {
             }
         return;
     }
+    if (RL) {                                            // (tile rows past the live count repeat the last live one, as below)
+        if (tid < TM) {
+            const int r = m0 + min(tid, Ml - 1 - m0);
+            rows_s[tid] = g.rows[p] != nullptr ? min(max(g.rows[p][r], 0), M - 1) : r;
+        }
+        __syncthreads();
+    }
 
     f32x16 acc[IM][IN];
 #pragma unroll
@@ -180,11 +193,12 @@ __global__ __launch_bounds__(64 * NW) void gemm16_nt_kernel(G16Args g) {
         const int i = ii * NW + wave;                    // wave-uniform
         const int r = RPI * (i < NIA ? i : i - NIA) + rl;
         const unsigned pc = (unsigned)((sl ^ ((r >> FS) & (PPR - 1))) * 8);
-        voff[ii] = i < NIA ? ((unsigned)min(r, Ml - 1 - m0) * (unsigned)g.ldap[p] + pc) * 2u
+        voff[ii] = i < NIA ? ((unsigned)(RL ? rows_s[r] : min(r, Ml - 1 - m0)) * (unsigned)g.ldap[p] + pc) * 2u
                            : ((unsigned)min(r, N - 1 - n0) * (unsigned)g.ldbp[p] + pc) * 2u;
     }
     int is_seg = 0, is_k = 0;
-    const unsigned short* Aseg = g.A[p][0] + (size_t)m0 * g.ldap[p];
+    const size_t a0 = RL ? 0 : (size_t)m0 * g.ldap[p];  // (a row list addresses A from its first row)
+    const unsigned short* Aseg = g.A[p][0] + a0;
     const unsigned short* Bseg = g.B[p][0] + (size_t)n0 * g.ldbp[p];
     auto stage = [&](int it) {
         const unsigned dst = lds0 + (unsigned)((it % NS) * STG) * 2u;
@@ -197,7 +211,7 @@ __global__ __launch_bounds__(64 * NW) void gemm16_nt_kernel(G16Args g) {
         if (is_k >= K) {                                 // next K segment (another module's projection / weight)
             is_k = 0;
             if (++is_seg < g.nseg[p]) {
-                Aseg = g.A[p][is_seg] + (size_t)m0 * g.ldap[p];
+                Aseg = g.A[p][is_seg] + a0;
                 Bseg = g.B[p][is_seg] + (size_t)n0 * g.ldbp[p];
             }
         }
@@ -264,10 +278,11 @@ __global__ __launch_bounds__(64 * NW) void gemm16_nt_kernel(G16Args g) {
 #pragma unroll
         for (int t = 0; t < WR * PPW / 64; ++t) {
             const int idx = t * 64 + lane, rr = idx / PPW, pc = idx % PPW;
-            const int row = m0 + wm * WR + rr, col = n0 + wn * WC + pc * 8;
-            if (row >= M || (g.keep_dead && row >= Ml)) continue;
+            const int trow = m0 + wm * WR + rr, col = n0 + wn * WC + pc * 8;
+            if (trow >= M || ((RL || g.keep_dead) && trow >= Ml)) continue;
+            const int row = RL ? rows_s[wm * WR + rr] : trow;
             uint4 v = *reinterpret_cast<const uint4*>(patch + rr * LDP + pc * 8);
-            if (row >= Ml) v = make_uint4(0u, 0u, 0u, 0u);
+            if (trow >= Ml) v = make_uint4(0u, 0u, 0u, 0u);
             if (col + 7 < N) {
                 *reinterpret_cast<uint4*>(C16p + (size_t)row * g.ldcp[p] + col) = v;
             } else {
@@ -581,11 +596,21 @@ int optin(K kernel, int bytes, std::atomic<unsigned long long>& done) {
 
 // desc: host srec_gemm_group (srec_hg.h) with bf16 A and B.  C_p [M, N] (+)= sum_s A_ps [M, K] B_ps [N, K]^T; K % 32 == 0,
 // lda / ldb % 8 == 0, 16-B aligned bases; c16: bf16 output (beta ignored); dyn clamps the output rows.
-extern "C" int srec_gemm16_nt(const void* desc_, void* stream) {
+static int gemm16_nt_run(const void* desc_, const int* const* rows, void* stream) {
     const srec_gemm16_group* h = (const srec_gemm16_group*)desc_;
     if (h == nullptr || h->np <= 0 || h->np > G16_MAXP) return SREC_BAD_ARG;
     G16Args g{};
     int blocks = 0;
+    bool listed = false;
+    for (int p = 0; rows != nullptr && p < h->np; ++p) {
+        g.rows[p] = rows[p];
+        if (rows[p] == nullptr) continue;
+        listed = true;
+        // the list's count is the live row count; 32-bit byte offsets from the operand's first row
+        const long lda = h->lda_p[p] > 0 ? h->lda_p[p] : h->lda;
+        if (h->dyn[p] == nullptr || (long)h->M[p] * lda * 2 > 0xffffffffL) return SREC_BAD_ARG;
+    }
+    if (listed && (h->c16 & (SREC_G16_C_BF16 | SREC_G16_KEEP_DEAD)) != (SREC_G16_C_BF16 | SREC_G16_KEEP_DEAD)) return SREC_BAD_ARG;
     // small-N problems (backward-data, N = D): 64-row tiles keep every CU busy
     // (tile-shape heuristics count LIVE rows where the caller knows them: mhint = expected *dyn of a capacity-padded problem)
     auto Mh = [&](int p) { return (h->mhint[p] > 0 && h->mhint[p] < h->M[p]) ? h->mhint[p] : h->M[p]; };
@@ -629,19 +654,24 @@ extern "C" int srec_gemm16_nt(const void* desc_, void* stream) {
     }
     hipStream_t st = (hipStream_t)stream;
     const bool c16 = h->c16 & SREC_G16_C_BF16;
-    static std::atomic<unsigned long long> optin_mask[8];
-#define SREC_G16(TMV, TNV, C16V, BKV, NSV, slot)                                                                       \
+    static std::atomic<unsigned long long> optin_mask[11];
+#define SREC_G16_RL(TMV, TNV, C16V, BKV, NSV, RLV, slot)                                                               \
     do {                                                                                                               \
         const size_t lds = (size_t)NSV * (TMV + TNV) * BKV * 2;                                                        \
-        if (int rc = optin(gemm16_nt_kernel<TMV, TNV, C16V, BKV, NSV>, (int)lds, optin_mask[slot])) return rc;         \
-        hipLaunchKernelGGL((gemm16_nt_kernel<TMV, TNV, C16V, BKV, NSV>), dim3(blocks), dim3(256), lds, st, g);         \
+        if (int rc = optin(gemm16_nt_kernel<TMV, TNV, C16V, BKV, NSV, 4, RLV>, (int)lds, optin_mask[slot])) return rc; \
+        hipLaunchKernelGGL((gemm16_nt_kernel<TMV, TNV, C16V, BKV, NSV, 4, RLV>), dim3(blocks), dim3(256), lds, st, g); \
     } while (0)
+#define SREC_G16(TMV, TNV, C16V, BKV, NSV, slot) SREC_G16_RL(TMV, TNV, C16V, BKV, NSV, false, slot)
     // measured at the bench's GAT shapes (tools/gemm16_bench.py): every ring lands at 33-40 us for the 16-GFLOP forward
     // (deeper rings lose more in occupancy than they gain in flight): 3 x 32-deep stages for the bf16-output forward,
     // 2 x 64-deep stages for backward-data.  Few workgroups (<= 1.5 per CU): LDS is plentiful and every workgroup is latency
     // bound on its own DMA - a 4-stage ring keeps three 64-deep stages in flight instead of one
     const bool deep = blocks <= 384;
-    if (tn == 64) {
+    if (listed) {                                        // (bf16 output: the shapes of the unlisted launch, so a row's bytes are the same)
+        if (tn == 64) SREC_G16_RL(64, 64, true, 64, 2, true, 8);
+        else if (tm == 128) SREC_G16_RL(128, 128, true, 32, 3, true, 9);
+        else SREC_G16_RL(64, 128, true, 32, 3, true, 10);
+    } else if (tn == 64) {
         if (c16) SREC_G16(64, 64, true, 64, 2, 0); else if (deep) SREC_G16(64, 64, false, 64, 4, 1); else SREC_G16(64, 64, false, 64, 2, 2);
     } else if (deep && tm == 64 && !c16) {
         SREC_G16(64, 128, false, 64, 4, 3);
@@ -651,8 +681,18 @@ extern "C" int srec_gemm16_nt(const void* desc_, void* stream) {
         if (c16) SREC_G16(64, 128, true, 32, 3, 6); else SREC_G16(64, 128, false, 64, 2, 7);
     }
 #undef SREC_G16
+#undef SREC_G16_RL
     SREC_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int srec_gemm16_nt(const void* desc_, void* stream) { return gemm16_nt_run(desc_, nullptr, stream); }
+
+// ... with a row list per problem: rows = HOST array of np device pointers (NULL entry: all rows).  Problem p then computes the rows
+// rows[p][0 .. *dyn[p]) of C_p only (ascending int32 row numbers < M, *dyn[p] <= M of them) from the same rows of A; every other row
+// of C_p is left unwritten.  bf16 output with SREC_G16_KEEP_DEAD only.
+extern "C" int srec_gemm16_nt_rows(const void* desc_, const void* rows, void* stream) {
+    return gemm16_nt_run(desc_, (const int* const*)rows, stream);
 }
 
 #ifdef SREC_G16_TIMING

@@ -1763,6 +1763,90 @@ extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const fl
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ live-source rows
+namespace {
+// A projection row P[m][u, :] is read only as the SOURCE of an edge (hg_agg_node / hg_bwd_dst_node through esrc; the logits come
+// from the folded vectors on x, the residual is x itself).  Per projection block: the ascending list of the live rows with an
+// out-edge in some instance that reads the block as source, and its count - what the projection GEMM computes (gemm16.hip, row
+// lists).  One workgroup per block, 1024 rows per round (4 consecutive rows per thread), an ordered block scan: deterministic.
+struct LiveArgs {
+    const int* out_ptr[MAXB][4];
+    const int* dyn[MAXB];
+    int* list[MAXB];
+    int* counts;
+    int ncap[MAXB], nsrc[MAXB];
+    int nb;
+};
+
+__device__ __forceinline__ void hg_live_rows_block(const LiveArgs& a, int b) {
+    __shared__ int wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = max(0, dyn_count(a.dyn[b], a.ncap[b]));
+    int* __restrict__ list = a.list[b];
+    int base = 0;
+    for (int r0 = 0; r0 < n; r0 += 1024) {
+        const int u0 = r0 + 4 * tid;
+        bool f[4] = {false, false, false, false};
+        for (int q = 0; q < a.nsrc[b]; ++q) {
+            const int* op = a.out_ptr[b][q];
+            int o[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) o[k] = u0 + k <= n ? op[u0 + k] : 0;      // (out_ptr has ncap + 1 entries)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) f[k] = f[k] || (u0 + k < n && o[k + 1] > o[k]);
+        }
+        const int cnt = (int)f[0] + (int)f[1] + (int)f[2] + (int)f[3];
+        int inc = cnt;                                                           // inclusive scan over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += v;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int off = base + inc - cnt, tot = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) off += wsum[w];
+            tot += wsum[w];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (f[k]) list[off++] = u0 + k;
+        base += tot;
+        __syncthreads();                                                         // wsum is rewritten by the next round
+    }
+    if (tid == 0) a.counts[b] = base;
+}
+
+__global__ __launch_bounds__(256) void hg_live_rows_kernel(LiveArgs a) { hg_live_rows_block(a, (int)blockIdx.x); }
+
+// lists: HOST array of n_blocks device pointers
+int hg_live_fill(LiveArgs& a, const srec_hg_desc* d, const void* lists, int* counts) {
+    if (d == nullptr || lists == nullptr || counts == nullptr || d->n_blocks <= 0 || d->n_blocks > MAXB || d->n_inst > MAXI) return SREC_BAD_ARG;
+    a.nb = d->n_blocks; a.counts = counts;
+    for (int b = 0; b < d->n_blocks; ++b) {
+        const int t = d->blk_type[b];
+        if (t < 0 || t >= d->n_types || ((int* const*)lists)[b] == nullptr) return SREC_BAD_ARG;
+        a.list[b] = ((int* const*)lists)[b]; a.ncap[b] = d->ncap[t]; a.dyn[b] = d->dyn_n[t]; a.nsrc[b] = 0;
+    }
+    for (int i = 0; i < d->n_inst; ++i) {
+        const int b = d->inst_sblk[i];
+        if (b < 0 || b >= d->n_blocks || a.nsrc[b] >= 4 || d->out_ptr[i] == nullptr) return SREC_BAD_ARG;
+        a.out_ptr[b][a.nsrc[b]++] = d->out_ptr[i];
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int srec_hg_live_rows(const void* desc, const void* lists, int* counts, void* stream) {
+    LiveArgs a{};
+    if (int rc = hg_live_fill(a, (const srec_hg_desc*)desc, lists, counts)) return rc;
+    hipLaunchKernelGGL(hg_live_rows_kernel, dim3(a.nb), dim3(256), 0, (hipStream_t)stream, a);
+    SREC_LAUNCH_CHECK();
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ feature dropout glue
 namespace {
 // One pass for the feature dropout of a layer call (HGATLayer with drop = (p_feat, p_attn), ops.py): from the uniform draws
@@ -1773,19 +1857,23 @@ namespace {
 //   xres  = x * rm
 // blocks [0, nb1): feature masks of the two convs and the masked inputs; blocks [nb1, ...): attention-dropout multipliers
 // mk [na] (all relation instances back to back).  Masks come from the counter-based hash of common.h.
-__global__ void hg_drop_prep_kernel(const float* __restrict__ x, const float* __restrict__ cnt, long n, int D, long rows,
+// In front of them live.nb workgroups (0: none) build the live-source row lists of the layer call (hg_live_rows_block): they
+// read the batch's topology only and start first, so the longest workgroups of the launch are not its tail.
+__global__ __launch_bounds__(256) void hg_drop_prep_kernel(const float* __restrict__ x, const float* __restrict__ cnt, long n, int D, long rows,
                                     float p, srec_rng rng, float* __restrict__ ms, float* __restrict__ xc,
                                     float* __restrict__ rm, float* __restrict__ xres, int nb1, float pa, long na,
-                                    float* __restrict__ mk, unsigned short* __restrict__ xc16) {
+                                    float* __restrict__ mk, unsigned short* __restrict__ xc16, LiveArgs live) {
+    if ((int)blockIdx.x < live.nb) { hg_live_rows_block(live, (int)blockIdx.x); return; }
+    const int bx = (int)blockIdx.x - live.nb;
     const unsigned key = srec_rng_key(rng);
-    if ((int)blockIdx.x >= nb1) {
-        const long j = ((long)((int)blockIdx.x - nb1) * blockDim.x + threadIdx.x) * 4;
+    if (bx >= nb1) {
+        const long j = ((long)(bx - nb1) * blockDim.x + threadIdx.x) * 4;
         const float sa = 1.f / (1.f - pa);
         for (int e = 0; e < 4; ++e)
             if (j + e < na) mk[j + e] = srec_keep(key ^ 0xA5A5A5A5u, (unsigned)(j + e), pa, sa);
         return;
     }
-    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const long i = ((long)bx * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
     const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;
     const long row = i / D;
@@ -1848,15 +1936,20 @@ __global__ void hg_drop_merge_kernel(const float* __restrict__ t, int S, const f
 // multipliers mk [na] - all masks from the counter-based hash keyed by (seed, *counter, salt).
 static int hg_drop_prep_run(const float* x, const float* cnt, int rows, int D, float p, int seed, const int* counter,
                             int salt, float* ms, float* xc, float* rm, float* xres, float pa, long na, float* mk,
-                            unsigned short* xc16, void* stream) {
+                            unsigned short* xc16, void* stream, const LiveArgs& live = LiveArgs{}) {
+    if (rows <= 0 && live.nb > 0) {
+        hipLaunchKernelGGL(hg_live_rows_kernel, dim3(live.nb), dim3(256), 0, (hipStream_t)stream, live);
+        SREC_LAUNCH_CHECK();
+    }
     if (rows <= 0) return 0;
     if (D <= 0 || (D & 3) || p < 0.f || p >= 1.f || pa < 0.f || pa >= 1.f) return SREC_BAD_ARG;
     const long n = (long)rows * D;
     if (2 * n > 0xffffffffL || na > 0xffffffffL) return SREC_BAD_ARG;
     const int nb1 = (int)((n / 4 + 255) / 256);
     const int nb2 = (pa > 0.f && na > 0 && mk != nullptr) ? (int)(((na + 3) / 4 + 255) / 256) : 0;
-    hipLaunchKernelGGL(hg_drop_prep_kernel, dim3((unsigned)(nb1 + nb2)), dim3(256), 0, (hipStream_t)stream, x, cnt, n, D,
-                       (long)rows, p, srec_rng{(unsigned)seed, counter, (unsigned)salt, p}, ms, xc, rm, xres, nb1, pa, na, mk, xc16);
+    hipLaunchKernelGGL(hg_drop_prep_kernel, dim3((unsigned)(live.nb + nb1 + nb2)), dim3(256), 0, (hipStream_t)stream, x, cnt, n, D,
+                       (long)rows, p, srec_rng{(unsigned)seed, counter, (unsigned)salt, p}, ms, xc, rm, xres, nb1, pa, na, mk, xc16,
+                       live);
     SREC_LAUNCH_CHECK();
     return 0;
 }
@@ -1872,6 +1965,15 @@ extern "C" int srec_hg_drop_prep16(const float* x, const float* cnt, int rows, i
                                    void* xc16, void* stream) {
     if (xc16 == nullptr) return SREC_BAD_ARG;
     return hg_drop_prep_run(x, cnt, rows, D, p, seed, counter, salt, ms, xc, rm, xres, pa, na, mk, (unsigned short*)xc16, stream);
+}
+
+extern "C" int srec_hg_drop_prep16_live(const float* x, const float* cnt, int rows, int D, float p, int seed, const int* counter,
+                                        int salt, float* ms, float* xc, float* rm, float* xres, float pa, long na, float* mk,
+                                        void* xc16, const void* desc, const void* lists, int* counts, void* stream) {
+    if (xc16 == nullptr) return SREC_BAD_ARG;
+    LiveArgs live{};
+    if (int rc = hg_live_fill(live, (const srec_hg_desc*)desc, lists, counts)) return rc;
+    return hg_drop_prep_run(x, cnt, rows, D, p, seed, counter, salt, ms, xc, rm, xres, pa, na, mk, (unsigned short*)xc16, stream, live);
 }
 
 // dx [n] += (sum_s t[0][s]) * ms[0] + (sum_s t[1][s]) * ms[1], t [2, S, n], ms [2, n] or NULL (then the masks of

@@ -6,7 +6,7 @@ from collections import namedtuple
 import torch
 
 from . import ops                    # (ops.py imports this module at its end: import the package or ops first, never hgat alone)
-from ._lib import CONST, lib, ptr, stream
+from ._lib import CONST, lib, ptr, ptr_array, stream
 from .ops import GemmProb, HgDesc, _ld, _rows
 
 # dropout state of one call.  xc [2, NT, D]: dropped inputs of conv1 / conv2;  xres [NT, D]: residual rows summed over the instances;
@@ -54,7 +54,8 @@ class HgPlan:
                 and any(bm == m and bt == t for bm, bt in self.blocks)]
 
     def scratch(self, dev):
-        """-> (fp32 tensor, offsets) of the small per-call scratch: eL,eR,wL,wR per block; V,Z per module; A,DP,der per instance"""
+        """-> (fp32 tensor, offsets) of the small per-call scratch: eL,eR,wL,wR per block; V,Z per module; A,DP,der per instance;
+        the live-source row list of every block and their counts (int32, live_rows)"""
         H, ncap = self.H, [tp[1] for tp in self.types]
         sizes = [((nm, b), ncap[t] * H) for b, (m, t) in enumerate(self.blocks) for nm in ('eL', 'eR', 'wL', 'wR')]
         # (Z slot t < n_types also holds the summed bias row of node type t during the forward: slots for max(modules, types))
@@ -64,20 +65,32 @@ class HgPlan:
             sizes += [(('A', i), E), (('DP', i), E), (('der', i), ncap[self.blocks[db][1]] * H)]
         sizes += [(('smean', t), self.B * self.D) for t in range(len(ncap))]       # session means of the input rows per type [B, D]
         sizes.append((('sess', 0), sum(ncap)))                                     # session of every stacked row (int32)
+        sizes += [(('live', b), max(ncap[t], 1)) for b, (m, t) in enumerate(self.blocks)]
+        sizes.append((('nlive', 0), max(len(self.blocks), 1)))
         off, lay = 0, {}
         for key, n in sizes:
             lay[key] = off
             off += n
         return torch.empty(max(off, 1), device=dev, dtype=torch.float32), lay
 
+    def live_rows(self, small, lay):
+        """-> ([int32 row list per projection block], int32 counts [n_blocks]) inside the scratch: the type-local rows of the block
+        that some edge reads as its source, ascending (srec_hg_live_rows) - the only rows of P anybody reads"""
+        i32 = small.view(torch.int32)
+        lists = [i32[lay[('live', b)]:][:max(self.types[t][1], 1)] for b, (m, t) in enumerate(self.blocks)]
+        return lists, i32[lay[('nlive', 0)]:][:len(self.blocks)]
+
+    def fill_drop(self, d, drop):                          # (d.rm stays NULL: srec_hg_bwd recomputes it from the masks' hash)
+        for m in range(len(self.modules)):
+            d.xin[m] = ptr(drop.xc[self.mod_conv[m]])
+        d.xres, d.rm_cnt = ptr(drop.xres), ptr(drop.cnt)
+        d.rm_p, d.rm_seed, d.rm_counter, d.rm_salt = drop.rng
+        for i in range(len(self.insts)):
+            d.Mk[i] = ptr(drop.mk[i]) if drop.mk is not None else None
+
     def fill(self, d, small, lay, P, dP, params, grads, drop=None):
-        if drop is not None:                               # (d.rm stays NULL: srec_hg_bwd recomputes it from the masks' hash)
-            for m in range(len(self.modules)):
-                d.xin[m] = ptr(drop.xc[self.mod_conv[m]])
-            d.xres, d.rm_cnt = ptr(drop.xres), ptr(drop.cnt)
-            d.rm_p, d.rm_seed, d.rm_counter, d.rm_salt = drop.rng
-            for i in range(len(self.insts)):
-                d.Mk[i] = ptr(drop.mk[i]) if drop.mk is not None else None
+        if drop is not None:
+            self.fill_drop(d, drop)
         d.H, d.D, d.slope, d.B, d.dynB = self.H, self.D, self.slope, self.B, ptr(self.dynB)
         d.p16 = CONST['SREC_HG_P16_BF16'] if P and P[0].dtype == torch.bfloat16 else 0      # (P = None: the view srec_hg_fold reads)
         d.n_types, d.n_mods, d.n_blocks, d.n_inst = len(self.types), len(self.modules), len(self.blocks), len(self.insts)
@@ -137,9 +150,10 @@ def gemm_strategy(mode, D, ldx, n_mods, w_contiguous):
     return 'g16' if D % 64 == 0 and w_contiguous else 'grouped'
 
 
-def _drop_prep(x, plan, drop, strategy):
+def _drop_prep(x, plan, drop, strategy, live=None):
     """-> (DropState, x16 or None): both convs' feature masks and every instance's attention mask in ONE launch (counter-based
-    hash: no generator state, replay-safe); the 'g16' strategy reads bf16(xc), written by the same pass"""
+    hash: no generator state, replay-safe); the 'g16' strategy reads bf16(xc), written by the same pass.  live = (desc, lists,
+    counts): the live-source row lists of the call ride in the same launch ('g16' only)"""
     (pf, pa), (NT, D), dev, tap = drop, x.shape, x.device, ops.DROP_TAP
     cnt = _inst_counts(plan, NT, dev)                     # (depends on the plan only: cached)
     ms = torch.empty(2, NT, D, device=dev, dtype=torch.float32) if tap is not None else None
@@ -152,7 +166,10 @@ def _drop_prep(x, plan, drop, strategy):
     salt = 101 + 2 * plan.layer_id                        # (rm = cnt0 m0 + cnt1 m1 is never stored: NULL, the backward recomputes it)
     args = (ptr(x), ptr(cnt), NT, D, float(pf), seed, rc, salt, ptr(ms), ptr(xcs), None, ptr(xres), float(pa), na, ptr(allm))
     x16 = torch.empty(2, NT, D, device=dev, dtype=torch.bfloat16) if strategy == 'g16' else None
-    if x16 is not None:
+    if x16 is not None and live is not None:
+        la = ptr_array(live[1])
+        lib.srec_hg_drop_prep16_live(*args, ptr(x16), _ct.addressof(live[0]), _ct.addressof(la), ptr(live[2]), stream())
+    elif x16 is not None:
         lib.srec_hg_drop_prep16(*args, ptr(x16), stream())
     else:
         lib.srec_hg_drop_prep(*args, stream())
@@ -161,29 +178,36 @@ def _drop_prep(x, plan, drop, strategy):
     return DropState([xcs[0], xcs[1]], xres, mk, ms, (float(pf), seed, rc, salt), cnt), x16
 
 
-def _project(xin, x16, plan, params, strategy, dev):
-    """P[m] = xin[m][rows of m] fc_m^T for every module -> (P, (bf16 inputs per module, wt16): what the 'g16' backward reads, or None)"""
+def _project(xin, x16, plan, params, strategy, P, live=None):
+    """P[m] = xin[m][rows of m] fc_m^T for every module -> (bf16 inputs per module, wt16): what the 'g16' backward reads, or None.
+    live = (lists, counts) of HgPlan.live_rows ('g16'): only the listed rows of a projection block are computed and written"""
     D, HD, nm = plan.D, plan.H * plan.D, len(plan.modules)
-    # bf16 strategies: the projections (and their gradients) are STORED as bf16 too - every pass over them is HBM bound
-    P = [torch.empty(nr, HD, device=dev, dtype=torch.float32 if strategy == 'plain' else torch.bfloat16)
-         for (r0, nr, dyn) in plan.modules]
     if strategy == 'g16':
         # the small weights as bf16 once per call (+ transposed copies for the backward-data product)
         w16, wt16 = ops.weights_bf16([params[4 * m] for m in range(nm)])
         xin16 = [x16[cv] for cv in plan.mod_conv] if x16 is not None else [ops.rows_bf16(xin[0])] * nm
-        probs = [GemmProb(nc, HD, D, [(xin16[m][t0:t0 + nc], w16[m])], P[m][o:o + nc], dyn_t, mhint=plan.live.get(t0, 0))
-                 for m in range(nm) for (o, t0, nc, dyn_t) in plan.pieces(m)]
+        type_of = {tp[0]: t for t, tp in enumerate(plan.types)}
+        probs = []
+        for m in range(nm):
+            for (o, t0, nc, dyn_t) in plan.pieces(m):
+                rows = None
+                if live is not None and (m, type_of[t0]) in plan.blocks:      # (a piece no instance uses keeps the dense product)
+                    b = plan.blocks.index((m, type_of[t0]))
+                    rows, dyn_t = live[0][b], live[1][b:b + 1]
+                probs.append(GemmProb(nc, HD, D, [(xin16[m][t0:t0 + nc], w16[m])], P[m][o:o + nc], dyn_t,
+                                      mhint=plan.live.get(t0, 0), rows=rows))
         for i in range(0, len(probs), ops.G16_MAXP):
-            # rows past a type's live count are never read (every hgat.hip kernel walks the live prefix only)
+            # rows past a type's live count are never read (every hgat.hip kernel walks the live prefix only), and of the live
+            # rows only those some edge reads as its source (DESIGN.md, MSHGNN layer: who reads P)
             ops.gemm16('nt', probs[i:i + ops.G16_MAXP], D, D, HD, c16=True, keep_dead=True)
-        return P, (xin16, wt16)
+        return xin16, wt16
     if strategy == 'grouped':
         ops.gemm_group(0, [(nr, HD, D, [(xin[m][r0:r0 + nr], params[4 * m])], P[m], dyn)
                            for m, (r0, nr, dyn) in enumerate(plan.modules)], D, D, HD, c16=True)
     else:
         for m, (r0, nr, dyn) in enumerate(plan.modules):
             ops.gemm_nt(xin[m][r0:r0 + nr], _rows(params[4 * m]), P[m], None, dyn, 1 if dyn is not None else 0)
-    return P, None
+    return None
 
 
 def _backward_graph(ctx, x, g, small, arg, P, params, late_dx):
@@ -297,19 +321,28 @@ class HGATLayer(torch.autograd.Function):
         (NT, D), dev, nm = x.shape, x.device, len(plan.modules)
         strategy = gemm_strategy(ops.PRECISION['matmul'], D, _ld(x), nm, all(params[4 * m].is_contiguous() for m in range(nm)))
         dstate, x16 = None, None
-        if drop is not None and (drop[0] > 0 or drop[1] > 0):
-            x = x.contiguous()          # srec_hg_fwd / srec_hg_bwd read the dropped copies (xin, xres: [NT, D]) with x's row stride
-            dstate, x16 = _drop_prep(x, plan, drop, strategy)
-        xin = [dstate.xc[cv] for cv in plan.mod_conv] if dstate is not None else [x] * nm      # what each module projects
-        P, g16 = _project(xin, x16, plan, params, strategy, dev)
         fold = plan.take_fold()                      # the prologue launch of this forward already folded the weights (step_prologue)
         small, lay = fold or plan.scratch(dev)
-        out = torch.empty(NT, D, device=dev, dtype=torch.float32)
-        arg = torch.empty(NT, D, device=dev, dtype=torch.uint8)
+        # bf16 strategies: the projections (and their gradients) are STORED as bf16 too - every pass over them is HBM bound
+        P = [torch.empty(nr, plan.H * D, device=dev, dtype=torch.float32 if strategy == 'plain' else torch.bfloat16)
+             for (r0, nr, dyn) in plan.modules]
         flat = [p.reshape(-1) if i % 4 else p for i, p in enumerate(params)]
-        desc = plan.fill(HgDesc(), small, lay, P, None, flat, None, dstate)
+        desc = plan.fill(HgDesc(), small, lay, P, None, flat, None, None)
         if fold is not None:
             desc.p16 |= CONST['SREC_HG_FOLDED']
+        live = plan.live_rows(small, lay) if strategy == 'g16' and ops.HG_LIVE_ROWS and plan.blocks else None
+        dropping = drop is not None and (drop[0] > 0 or drop[1] > 0)
+        if dropping:
+            x = x.contiguous()          # srec_hg_fwd / srec_hg_bwd read the dropped copies (xin, xres: [NT, D]) with x's row stride
+            dstate, x16 = _drop_prep(x, plan, drop, strategy, (desc,) + live if live is not None else None)
+            plan.fill_drop(desc, dstate)
+        elif live is not None:                       # (the lists ride in the dropout launch when there is one)
+            la = ptr_array(live[0])
+            lib.srec_hg_live_rows(_ct.addressof(desc), _ct.addressof(la), ptr(live[1]), stream())
+        xin = [dstate.xc[cv] for cv in plan.mod_conv] if dstate is not None else [x] * nm      # what each module projects
+        g16 = _project(xin, x16, plan, params, strategy, P, live)
+        out = torch.empty(NT, D, device=dev, dtype=torch.float32)
+        arg = torch.empty(NT, D, device=dev, dtype=torch.uint8)
         lib.srec_hg_fwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(out), D, ptr(arg), stream())
         ctx.save_for_backward(x, small, arg, *P, *params)
         ctx.plan, ctx.lay, ctx.strategy, ctx.drop, ctx.g16 = plan, lay, strategy, dstate, g16

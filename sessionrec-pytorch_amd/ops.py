@@ -1833,8 +1833,9 @@ def edge_agg(x, coef, fwd_csr, bwd_csr, dyn=None):
 # ------------------------------------------------------------------------------------------ MSHGNN layer (batched)
 # one problem of a grouped GEMM launch: C [M, N] from the segments [(A, B), ...], dyn = device live count; a plain 6-tuple is the
 # same problem.  gemm16 only: koff (tn: first reduction row of this piece of a row-split product), nsplit (tn: in-kernel row
-# split, C = [nsplit, M, N] slabs), ld = per-problem (lda, ldb, ldc), mhint (nt: expected live rows of a capacity-padded problem)
-GemmProb = namedtuple('GemmProb', 'M N K segs C dyn koff nsplit ld mhint', defaults=(0, 1, None, 0))
+# split, C = [nsplit, M, N] slabs), ld = per-problem (lda, ldb, ldc), mhint (nt: expected live rows of a capacity-padded problem),
+# rows (nt, bf16 output: int32 device list of the rows to compute, dyn = its device count; the other rows of C stay unwritten)
+GemmProb = namedtuple('GemmProb', 'M N K segs C dyn koff nsplit ld mhint rows', defaults=(0, 1, None, 0, None))
 
 
 def gemm_group(mode, probs, lda, ldb, ldc, beta=0.0, a16=False, c16=False):
@@ -1868,6 +1869,12 @@ def gemm16(kind, probs, lda, ldb, ldc, beta=0.0, c16=False, keep_dead=False):
     """one grouped launch of the bf16-in-HBM GEMMs (csrc/gemm16.hip) over probs.  kind 'nt': C [M, N] (+)= sum_s A_s [M, K] B_s [N, K]^T
     (c16: bf16 output);  'tn': C [M, N] = sum_s A_s [K, M]^T B_s [K, N] (reduction over the K rows, clamped by dyn)."""
     g = gemm16_desc(probs, lda, ldb, ldc, beta, c16, keep_dead)
+    rows = [GemmProb(*q).rows for q in probs]
+    if any(r is not None for r in rows):
+        assert kind == 'nt', 'row lists: nt launches only'
+        ra = ptr_array(rows)                             # (host array: alive across the call)
+        lib.srec_gemm16_nt_rows(_ct.addressof(g), _ct.addressof(ra), stream())
+        return
     (lib.srec_gemm16_nt if kind == 'nt' else lib.srec_gemm16_tn)(_ct.addressof(g), stream())
 
 
@@ -1953,6 +1960,9 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
         plan.put_fold(small, lay)
 
 
+# MSHGNN 'g16' forward: project only the rows some edge reads as its source (csrc/hgat.hip live-source rows + the row lists of
+# csrc/gemm16.hip); 0 = every live row (tests / A-B runs)
+HG_LIVE_ROWS = os.environ.get('SREC_HG_LIVE_ROWS', '1') != '0'
 DROP_TAP = None      # tests: set to a list to receive {'ms': [2, NT, D], 'mk': [per instance (E*H,)]} of every dropout layer call
 
 from .hgat import HgPlan, HGATLayer, hgat_layer  # noqa: E402,F401  (the MSHGNN layer: hgat.py imports this module)
