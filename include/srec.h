@@ -616,6 +616,37 @@ int srec_score_norm(const float* sr, int ld_sr, long comp_stride, const float* E
                     long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
                     const int* group, int G, float* out, void* ws, void* stream);
 
+/* ---- serving: DRAW K distinct items per session from the served distribution (recommend.hip, NOISE instances) ------------
+ * The selection of srec_score_select_biased over the SAMPLED key of every eligible (session b, row v) pair,
+ *   key[b,v] = s'[b,v] * inv_temperature + g(seed, q[b], id_lo + v),
+ * s' the biased served score and the eligibility those of srec_score_select_biased, inv_temperature = 1 / T > 0 and finite,
+ * q[b] = session_keys[b] (any 32-bit value; NULL: the row index b), g independent Gumbel(0, 1) noise.  By the Gumbel-top-k
+ * identity the K best keys, in order, are a draw WITHOUT replacement (Plackett-Luce) from p(v) ~ exp(s'[b,v] / T) over the
+ * eligible rows.  out_key [B, K] fp32 descending, out_idx [B, K] int32 global ids in draw order; ties towards the lower id;
+ * (-INFINITY, -1) slots where fewer than K rows are eligible; K <= SREC_SELECT_MAXK; all layouts and limits of
+ * srec_score_select_biased; ws: srec_score_sample_ws() bytes.
+ * The noise is counter-based - a pure function of (seed, q, GLOBAL id), csrc/sample_noise.h; nothing (B, V)-sized exists:
+ *   h32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16       (32-bit, "lowbias32")
+ *   skey = h32(lo ^ h32(q * 0x9E3779B9 + hi * 0x85EBCA6B + 0x165667B1))      lo / hi: the 32-bit words of seed; per session
+ *   h    = h32(skey ^ ((unsigned)gid * 0x9E3779B1 + 0x7F4A7C15))             per pair; a bijection of gid for a fixed session
+ *   w    = fminf(fmaf((float)h, 0x1p-32f, 0x1p-33f), 0x1.fffffep-1f)         in (0, 1)
+ *   g    = -logf(-log1pf(-w))                                                in [-2.82, 22.9], always finite
+ * so a call is reproducible, a session's draw does not depend on the batch it is in (give it the same key), and the lists
+ * of disjoint row shards - every shard with its id_lo - merge by (key, id) to the bits of the single-device call.
+ * Nonzero and no launch for the reasons of srec_score_select_biased, for inv_temperature that is not positive and finite
+ * (zero, negative, infinite, NaN) and for session_keys not aligned to 4 bytes.
+ * srec_sample_uniform: HOST function, no GPU - h_out / w_out [n_b, n_v] (either may be NULL, not both) are h and w of the
+ * formula for the keys session_keys[0 .. n_b) (NULL: 0 .. n_b - 1) and the global ids ids[0 .. n_v) (NULL: 0 .. n_v - 1):
+ * the stream pinned for tests and for users who restate a draw. */
+int srec_score_sample_ws(int B, int V, int d, int C, int L, int K, long* bytes);
+int srec_score_sample(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                      long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                      const int* group, int G, float inv_temperature, unsigned long long seed, const int* session_keys,
+                      float* out_key, int* out_idx, void* ws, void* stream);
+int srec_sample_uniform(unsigned long long seed, const int* session_keys, int n_b, const int* ids, int n_v,
+                        unsigned* h_out, float* w_out);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

@@ -18,7 +18,16 @@
 // LDS (part_lds): the pass's 1.6 KB of offsets, mask and counts, 32 L ids (and 256 bytes of bias row offsets with G rows) +
 // 0.5 KB of survivor masks + 32 K (value, id) pairs + 17 KB candidates + the session tiles when the sum stays within 160 KB
 // (C = 3, d = 256, K = 128, L = 64: 160 384 bytes = 156.6 KB; with G rows 156.9 KB), else the tiles are read through the cache.
+//
+// srec_score_sample: the same two passes over the SAMPLED key  s' / T + g(seed, q[b], id_lo + v)  (NOISE = true instances;
+// sample_noise.h is the noise): by the Gumbel-top-k identity the K best keys, in order, are a draw without replacement from
+// softmax(s' / T) over the eligible rows.  The 32 sessions' hashed keys are staged in LDS once (128 bytes more, noisy
+// instances only: 160 512 bytes in the case above, 160 768 with G rows - placed by the same rule); the lane that owns item v
+// forms the item's half of the hash once per chunk and the key after the score, and the key takes the score's place in the
+// threshold test, in cand and in both merges.  The noise is a function of GLOBAL ids, so row shards merge to the bits of one
+// device, and a session's draw does not depend on the batch it came in.
 #include "common.h"
+#include "sample_noise.h"
 #include "score_pass.h"
 
 namespace {
@@ -32,6 +41,9 @@ constexpr int EMPTY = 0x7fffffff;   // id of an unfilled list slot: behind every
 struct SelArgs : PassArgs {
     int K;
     float* pv; int* pi;             // [R][B][K] per-range lists (local rows; EMPTY = unfilled)
+    float inv_t;                    // NOISE instances only: 1 / T, the seed and the session keys (NULL: the row index)
+    unsigned long long seed;
+    const int* qkeys;
 };
 
 __device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
@@ -87,11 +99,12 @@ __device__ __forceinline__ void merge_sorted(float* lv, int* li, int K, const fl
     __builtin_amdgcn_wave_barrier();
 }
 
-inline size_t part_lds(int C, int d, int K, int L, bool sr_lds, bool grouped = false) {
-    return pass_lds(L, grouped) + (size_t)SB * 4 * 4 + (size_t)SB * K * 8 + (size_t)SB * CST * 4 + (sr_lds ? tile_bytes(C, d) : 0);
+inline size_t part_lds(int C, int d, int K, int L, bool sr_lds, bool grouped = false, bool noisy = false) {
+    return pass_lds(L, grouped) + (size_t)SB * 4 * 4 + (size_t)SB * K * 8 + (size_t)SB * CST * 4 + (noisy ? (size_t)SB * 4 : 0) +
+           (sr_lds ? tile_bytes(C, d) : 0);
 }
 
-template <int C, bool SR_LDS, int BIAS>
+template <int C, bool SR_LDS, int BIAS, bool NOISE>
 __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int d = a.d, K = a.K, L = a.L;
@@ -105,7 +118,8 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     float* cand = reinterpret_cast<float*>(li + SB * K);            // [SB][CST] scores of this chunk's survivors
     int* lst = reinterpret_cast<int*>(cand + SB * CST);
     unsigned long long* goff = reinterpret_cast<unsigned long long*>(lst + SB * L);
-    float* Ss = reinterpret_cast<float*>(goff + (BIAS == 2 ? SB : 0));  // [C][SB][LD] (SR_LDS); 16-byte aligned: all counts above are multiples of 4
+    unsigned* skey = reinterpret_cast<unsigned*>(goff + (BIAS == 2 ? SB : 0));   // [SB] hashed session keys (NOISE)
+    float* Ss = reinterpret_cast<float*>(skey + (NOISE ? SB : 0));  // [C][SB][LD] (SR_LDS); 16-byte aligned: all counts above are multiples of 4
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
@@ -116,6 +130,12 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     SCORE_PASS_STAGE_OFFSETS(C, a, ps, b0, tid)
     for (int i = tid; i < SB * K; i += 256) { lv[i] = -INFINITY; li[i] = EMPTY; }
     SCORE_PASS_PROLOGUE(BIAS, a, ps, b0, v0, v1, tid, lane, wave)
+    if constexpr (NOISE) {
+        if (tid < SB) {
+            const int b = b0 + tid;
+            skey[tid] = srec_sample_skey(a.seed, b < a.B ? (unsigned)(a.qkeys != nullptr ? a.qkeys[b] : b) : 0u);
+        }
+    }
     if (SR_LDS) stage_tiles<C>(Ss, a.sr, a.ld_sr, a.comp_stride, b0, a.B, d, tid);
     __syncthreads();
 
@@ -130,9 +150,11 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
         __syncthreads();              // membership bits written; the merges of the previous chunk are done
 
         // per-lane epilogue: item v (this lane's column) against 16 sessions
+        [[maybe_unused]] const unsigned gmix = (unsigned)(a.id_lo + it.v) * 0x9E3779B1u + 0x7F4A7C15u;   // srec_sample_hash, the item's half
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             SCORE_PASS_ITEM_SCORE(C, BIAS, it, acc, r, ps, wave, l31, half, sl, in, s, bias_ok)
+            if constexpr (NOISE) s = fmaf(s, a.inv_t, srec_sample_gumbel(srec_sample_h32(skey[sl] ^ gmix)));   // the sampled key
             const bool hit = SCORE_PASS_ELIGIBLE(it, in, ps, b0 + sl < a.B, bias_ok) && better(s, it.v, lv[sl * K + K - 1], li[sl * K + K - 1]);
             const unsigned long long mk = __ballot(hit);
             if (hit) cand[sl * CST + wave * 32 + l31] = s;
@@ -208,7 +230,9 @@ __global__ __launch_bounds__(256) void select_merge_kernel(const float* __restri
 }
 
 template <int C, bool SR_LDS, int BIAS>
-struct SelectPart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS>; };
+struct SelectPart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, false>; };
+template <int C, bool SR_LDS, int BIAS>
+struct SamplePart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, true>; };
 
 inline int ranges(int B, int V) { return pick_ranges(B, V, 512, 4); }   // the lists and tiles leave room for one or two
                                                                         // workgroups per CU; the first chunk fills the list
@@ -221,10 +245,14 @@ extern "C" int srec_score_select_ws(int B, int V, int d, int C, int L, int K, lo
     return 0;
 }
 
-extern "C" int srec_score_select_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                        const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                        long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                                        const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream) {
+namespace {
+
+// both entry points: NOISE = false is srec_score_select_biased as it always was (inv_t / seed / qkeys are not read)
+template <bool NOISE>
+int select_launch(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs, const float* off_ex,
+                  const float* off_in, const int* listed, int L, int listed_mode, long id_lo, int B, int V, int d, int C, int K,
+                  const float* bias, long ld_bias, const int* group, int G, float inv_t, unsigned long long seed,
+                  const int* qkeys, float* out_val, int* out_idx, void* ws, void* stream) {
     if (B <= 0) return 0;
     SelArgs a{};
     if (pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias, ld_bias,
@@ -236,12 +264,59 @@ extern "C" int srec_score_select_biased(const float* sr, int ld_sr, long comp_st
     a.K = K;
     a.pv = (float*)ws;
     a.pi = (int*)(a.pv + (size_t)R * B * K);
+    a.inv_t = inv_t; a.seed = seed; a.qkeys = qkeys;
     hipStream_t st = (hipStream_t)stream;
-    const auto lds = [&](int c, bool sr_lds, bool grouped) { return part_lds(c, d, K, a.L, sr_lds, grouped); };
-    if (int rc = switch_c(C, [&](auto c) { return launch_pass<SelectPart, true, c.value>(a, grid, lds, st); })) return rc;
+    const auto lds = [&](int c, bool sr_lds, bool grouped) { return part_lds(c, d, K, a.L, sr_lds, grouped, NOISE); };
+    if (int rc = switch_c(C, [&](auto c) {
+            if constexpr (NOISE) return launch_pass<SamplePart, true, c.value>(a, grid, lds, st);
+            else return launch_pass<SelectPart, true, c.value>(a, grid, lds, st);
+        }))
+        return rc;
     hipLaunchKernelGGL(select_merge_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, a.pv, a.pi, (int)grid.x, B, K, id_lo, out_val,
                        out_idx);
     SREC_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int srec_score_select_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                        const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                                        long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                                        const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream) {
+    return select_launch<false>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
+                                bias, ld_bias, group, G, 1.f, 0ull, nullptr, out_val, out_idx, ws, stream);
+}
+
+// ws: as srec_score_select_ws (the per-range lists hold keys where that call's hold scores)
+extern "C" int srec_score_sample_ws(int B, int V, int d, int C, int L, int K, long* bytes) {
+    return srec_score_select_ws(B, V, d, C, L, K, bytes);
+}
+
+extern "C" int srec_score_sample(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                 const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode, long id_lo,
+                                 int B, int V, int d, int C, int K, const float* bias, long ld_bias, const int* group, int G,
+                                 float inv_temperature, unsigned long long seed, const int* session_keys, float* out_key,
+                                 int* out_idx, void* ws, void* stream) {
+    if (B <= 0) return 0;
+    if (!(inv_temperature > 0.f) || !(inv_temperature <= 3.402823466e+38f) || ((uintptr_t)session_keys & 3)) return SREC_BAD_ARG;
+    return select_launch<true>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
+                               bias, ld_bias, group, G, inv_temperature, seed, session_keys, out_key, out_idx, ws, stream);
+}
+
+// HOST: h [n_b, n_v] and w [n_b, n_v] of sample_noise.h for the sessions' keys (NULL: 0 .. n_b - 1) and the global ids
+// (NULL: 0 .. n_v - 1); either output may be NULL.  No GPU is touched.
+extern "C" int srec_sample_uniform(unsigned long long seed, const int* session_keys, int n_b, const int* ids, int n_v,
+                                   unsigned* h_out, float* w_out) {
+    if (n_b < 0 || n_v < 0 || (h_out == nullptr && w_out == nullptr)) return SREC_BAD_ARG;
+    for (int b = 0; b < n_b; ++b) {
+        const unsigned sk = srec_sample_skey(seed, (unsigned)(session_keys != nullptr ? session_keys[b] : b));
+        for (int v = 0; v < n_v; ++v) {
+            const unsigned h = srec_sample_hash(sk, (unsigned)(ids != nullptr ? ids[v] : v));
+            if (h_out != nullptr) h_out[(size_t)b * n_v + v] = h;
+            if (w_out != nullptr) w_out[(size_t)b * n_v + v] = srec_sample_w(h);
+        }
+    }
     return 0;
 }
 

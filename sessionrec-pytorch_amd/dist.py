@@ -420,6 +420,12 @@ class HipLocal:
         bias: `bias=` (this shard's columns) and `group=` of ops.score_select, only when there is a bias"""
         return self.ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
+    def sample(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, temperature, seed, session_keys, **bias):
+        """this shard's k best sampled keys (keys, global ids) of ops.score_sample: rows [id_lo, id_lo + n) of the catalog.
+        session_keys: one integer per session (the noise is a function of the key, never of the row).  bias: as in select()"""
+        return self.ops.score_sample(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, temperature=temperature,
+                                     seed=seed, session_keys=session_keys, **bias)
+
     def score_items(self, srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo, **bias):
         """this shard's share of ops.score_items: rows [id_lo, id_lo + n) of the catalog score, every other id gives 0.
         bias: as in select()"""
@@ -885,6 +891,14 @@ class VocabParallel:
         else:
             val = torch.full((B, k), float('-inf'), device=dev)
             idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
+        val, idx = self._merge_lists(val, idx, B, k)
+        if data_parallel:
+            val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
+        return val, idx
+
+    def _merge_lists(self, val, idx, B, k):
+        """the ranks' (value, id) lists [B, k] -> the k best of all of them: ONE all-gather of the pairs, then the order of one
+        device (select() and sample())"""
         if _active(self.group):
             w = self.world
             pair = all_gather_cat(torch.stack([val.view(torch.int32), idx], 0), self.group).view(w, 2, B, k)
@@ -896,6 +910,31 @@ class VocabParallel:
             val, idx = val.gather(1, o), idx.gather(1, o)
             o = torch.argsort(val, dim=1, descending=True, stable=True)[:, :k]
             val, idx = val.gather(1, o).contiguous(), idx.gather(1, o).contiguous()
+        return val, idx
+
+    def sample(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
+               bias=None, group=None, temperature=1.0, seed=0, session_keys=None):
+        """k distinct items per session DRAWN from softmax(score / temperature) over the eligible items of the sharded table
+        (ops.score_sample's contract; the arguments of select()): every rank keeps the k best sampled keys among its own LIVE
+        rows with its id_lo, ONE all-gather carries the (key, id) pairs and select()'s merge orders them.  The noise is a
+        function of (seed, session key, GLOBAL id), so the result is the single-device call's, bit for bit.  session_keys:
+        [B] integers of this rank's sessions; None = the row index - under data_parallel the GLOBAL row index (rank * B + b),
+        and given keys are all-gathered with the sessions."""
+        n_loc = srs[0].shape[0]
+        bkw = self._bias_cols(bias, group, data_parallel)
+        if data_parallel:
+            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
+            if session_keys is not None:
+                session_keys = all_gather_cat(session_keys.reshape(-1).to(torch.int32).contiguous(), self.group)
+        B, dev = srs[0].shape[0], srs[0].device
+        if self.n_live > 0:
+            csl = None if cs is None else cs[:self.n_live]
+            val, idx = self.local.sample(srs, table[:self.n_live], csl, k, off_ex, off_in, listed, drop_listed, self.lo,
+                                         temperature, seed, session_keys, **bkw)
+        else:
+            val = torch.full((B, k), float('-inf'), device=dev)
+            idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
+        val, idx = self._merge_lists(val, idx, B, k)
         if data_parallel:
             val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
         return val, idx

@@ -232,6 +232,7 @@ def score_ce(sr, table, cs, labels, ws, tgrad, dynB=None, cs_inv_scale=1.0, tb=N
 
 _BYTE_WS = {}          # the evaluation / selection kernels: kinds 'topk', 'rank', 'select'
 _NORM_WS = {}          # the log-normaliser of the serving calls: kind 'norm'
+_SAMPLE_WS = {}        # the draws of the serving calls: kind 'sample'
 
 
 def _byte_ws(kind, device, nbytes, cache=None):
@@ -271,6 +272,7 @@ _LISTED_TOO_MANY = {
     'score_select': 'score_select: %d listed items per session; csrc/recommend.hip takes at most 64',
     'score_items': 'score_items: %d listed items per session; csrc/score_items.hip takes at most 64',
     'score_norm': 'score_norm: %d listed items per session; csrc/score_norm.hip takes at most 64',
+    'score_sample': 'score_sample: %d listed items per session; csrc/recommend.hip takes at most 64',
 }
 
 
@@ -446,6 +448,128 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
                                  ptr(a.off_in), ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k,
                                  ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, ptr(val), ptr(idx), ptr(ws), stream())
     return val, idx
+
+
+def _seed_words(who, seed):
+    """a seed as the int the library takes: any integer in [0, 2^64)"""
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError('%s: seed must be an integer in [0, 2^64), got %r' % (who, seed))
+    return seed
+
+
+def _session_keys(who, session_keys, B):
+    """session_keys as int32 [B] on their device (None stays None: the row index).  Keys are 32-bit values: an integer outside
+    [-2^31, 2^31) is taken modulo 2^32"""
+    if session_keys is None:
+        return None
+    q = torch.as_tensor(session_keys).detach()
+    if q.is_floating_point() or q.is_complex() or q.dtype == torch.bool or q.numel() != B:
+        raise ValueError('%s: session_keys must hold %d integers (one per session), got %s %s'
+                         % (who, B, q.dtype, tuple(q.shape)))
+    return q.reshape(B).to(torch.int32).contiguous()
+
+
+def _mul32(x, c):
+    """x * c mod 2^32 for int64 tensors x in [0, 2^32) and an int c in [0, 2^32) - no product leaves int64"""
+    return ((x & 0xffff) * c + ((((x >> 16) * c) & 0xffff) << 16)) & 0xffffffff
+
+
+def _h32(x):
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7feb352d)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846ca68b)
+    return x ^ (x >> 16)
+
+
+_LN2 = 0.6931471805599453
+
+
+def _log64(x):
+    """natural log of positive finite float64 x from +, -, *, / and frexp alone (each correctly rounded everywhere), so that
+    sample_noise gives the same BITS on every host and in every restatement that follows these lines - a library log does
+    not (torch, numpy and libm differ in the last bit).  x = m 2^e with m in [sqrt(1/2), sqrt(2)), t = (m - 1) / (m + 1),
+    log m = 2 t (1 + t^2/3 + ... + t^26/27): |t| <= 0.172, truncation below 2e-22; error a few 1e-16 relative to max(1, |log x|)"""
+    m, e = torch.frexp(x)
+    small = m < 0.7071067811865476
+    m = torch.where(small, m * 2.0, m)
+    e = e.double() - small.double()
+    t = (m - 1.0) / (m + 1.0)
+    t2 = t * t
+    p = torch.full_like(t, 1.0 / 27.0)
+    for n in range(25, 0, -2):
+        p = p * t2 + 1.0 / n
+    return e * _LN2 + 2.0 * t * p
+
+
+def sample_scalars(who, k, temperature, seed):
+    """(k, 1 / temperature, seed) as the library takes them, or ValueError in the words of `who`: k in 1 .. 128, temperature
+    positive and finite (and 1 / temperature finite in fp32), seed an integer in [0, 2^64).  No launch, no library call"""
+    k = int(k)
+    if k < 1 or k > CONST['SREC_SELECT_MAXK']:
+        raise ValueError('%s: k = %d; the selection kernel of csrc/recommend.hip keeps between 1 and %d items per session'
+                         % (who, k, CONST['SREC_SELECT_MAXK']))
+    try:
+        temperature = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError('%s: temperature must be a number, got %r' % (who, temperature)) from None
+    if not (0.0 < temperature < float('inf')) or not (1.0 / temperature < 3.4e38):
+        raise ValueError('%s: temperature = %r; it must be positive and finite' % (who, temperature))
+    return k, 1.0 / temperature, _seed_words(who, seed)
+
+
+def sample_noise(seed, session_keys, ids):
+    """float64 [nb, nv]: the Gumbel noise g(seed, q, id) score_sample adds to score / temperature, for session keys q
+    (integers, taken modulo 2^32) and GLOBAL item ids - the documented way to reproduce a draw: the ids score_sample returns
+    are the k best of  score / T + g  over the eligible items (to the fp32 rounding of the kernel's own score and logs).  Pure
+    torch on the CPU, no library call; the formula is that of include/srec.h (srec_score_sample): w is formed in fp32 exactly
+    as the kernel forms it, the two logarithms are taken in float64 by _log64 (arithmetic only: equal bits on every host)."""
+    seed = _seed_words('sample_noise', seed)
+    m = 0xffffffff
+    q = torch.as_tensor(session_keys).detach().cpu().reshape(-1).to(torch.int64) & m
+    gid = torch.as_tensor(ids).detach().cpu().reshape(-1).to(torch.int64) & m
+    lo, hi = seed & m, seed >> 32
+    skey = _h32(lo ^ _h32((_mul32(q, 0x9E3779B9) + (hi * 0x85EBCA6B + 0x165667B1) % 2 ** 32) & m))
+    h = _h32(skey[:, None] ^ ((_mul32(gid, 0x9E3779B1) + 0x7F4A7C15) & m)[None, :])
+    # fmaf((float)h, 2^-32, 2^-33): the product and the sum are exact in float64, so one rounding to fp32 is the fused result
+    w = (h.to(torch.float32).double() * 2.0 ** -32 + 2.0 ** -33).to(torch.float32).clamp(max=1.0 - 2.0 ** -24)
+    # log1p(-w) by Kahan's identity on the rounded u = 1 - w (u == 1: -w itself), then g = -log(-log1p(-w))
+    w = w.double()
+    u = 1.0 - w
+    one = u == 1.0
+    l1 = torch.where(one, -w, _log64(u) * (-w) / torch.where(one, torch.full_like(u, -1.0), u - 1.0))
+    return -_log64(-l1)
+
+
+def score_sample(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None,
+                 temperature=1.0, seed=0, session_keys=None):
+    """(keys fp32 [B,k] descending, item ids int32 [B,k] in draw order): k DISTINCT rows of `table` per session drawn without
+    replacement (Plackett-Luce) from p(v) ~ exp(s'[b,v] / temperature) over the eligible rows, s' the biased score of
+    score_select and its eligibility - no (B, V) tensor, k <= 128 (csrc/recommend.hip, the selection over the sampled key
+    s' / T + g; Gumbel-top-k).  Arguments as score_select.  temperature: a positive finite scalar.  seed: an integer in
+    [0, 2^64).  session_keys: [B] integers (32-bit values), None = the row index; the noise g is a pure function of (seed,
+    session key, global item id) - sample_noise() restates it - so a call is reproducible, a session with the same key draws
+    the same items in any batch, and row shards (id_lo) merge by (key, id) to the bits of one call over the whole table.  A
+    session with fewer than k eligible rows ends in (-inf, -1) slots.  The keys are NOT log-probabilities: score the ids
+    (score_items) for those."""
+    k, inv_t, seed = sample_scalars('score_sample', k, temperature, seed)
+    a = _mixture_args('score_sample', srs, table, off_ex, None if drop_listed else off_in, listed)
+    bi = _bias_args('score_sample', bias, group, a.B, a.V)
+    B, dev = a.B, a.srs.device
+    q = _session_keys('score_sample', session_keys, B)
+    key = torch.empty(B, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(B, k, device=dev, dtype=torch.int32)
+    if B == 0:
+        return key, idx
+    if q is not None:
+        q = q.to(dev)
+    n = _ct.c_long()
+    lib.srec_score_sample_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
+    ws = _byte_ws('sample', dev, n.value, _SAMPLE_WS)
+    lib.srec_score_sample(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
+                          ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias),
+                          bi.ld_bias, ptr(bi.group), bi.G, inv_t, seed, ptr(q), ptr(key), ptr(idx), ptr(ws), stream())
+    return key, idx
 
 
 def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, checked=False,

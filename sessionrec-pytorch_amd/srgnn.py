@@ -366,6 +366,37 @@ class _ScoringMixin:
                                      data_parallel=self.shard.eval_data_parallel, **bias)
         return ops.score_select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, **bias)
 
+    def sample(self, *inputs, k=1, temperature=1.0, seed=0, session_keys=None, exclude_seen=False, item_bias=None,
+               item_group=None, renormalize=False):
+        """(log_probs fp32 [B,k], item_ids int32 [B,k] in DRAW order): k distinct next items per session drawn without
+        replacement from the model's distribution - p(v) ~ exp((log p_model(v) + bias_v) / temperature) over the items
+        recommend() could return with the same keywords (not the session's own under exclude_seen, item_bias > -inf); k <= 128.
+        One fused pass over the table (csrc/recommend.hip with Gumbel noise; ops.score_sample): no (B, V) matrix, no (B, V)
+        noise, sharded table included.  seed: an integer in [0, 2^64); session_keys: [B] integers, None = the row index of
+        the batch - a session with the same (seed, key) draws the same items in any batch, on any number of shards
+        (ops.sample_noise restates the noise).  The VALUES are not the sampled keys: they are what score_items(items=ids)
+        returns with the same keywords, bit for bit - forward()'s log-probabilities (plus bias; renormalize=True: under the
+        distribution restricted to the eligible catalogue) at temperature 1, the number an off-policy log needs.  A session
+        with fewer than k eligible items ends in (-inf, -1) slots.  Runs in eval mode under torch.no_grad(); item_bias /
+        item_group, k, temperature and seed are checked before anything of the model runs."""
+        bias = self._item_bias('sample', item_bias, item_group)
+        k, _, seed = ops.sample_scalars('sample', k, temperature, seed)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+                if self.shard is not None:
+                    _, ids = self.shard.sample(srs, self._table(), cs, k, off_ex, off_in, listed, exclude_seen,
+                                               data_parallel=self.shard.eval_data_parallel, temperature=temperature, seed=seed,
+                                               session_keys=session_keys, **bias)
+                else:
+                    _, ids = ops.score_sample(srs, self._table(), cs, k, off_ex, off_in, listed, exclude_seen,
+                                              temperature=temperature, seed=seed, session_keys=session_keys, **bias)
+                return self._items_of(srs, cs, ids, off_ex, off_in, listed, exclude_seen, **bias), ids
+        finally:
+            self.train(was_training)
+
     def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """fp32 [B, M]: the log-probability forward() returns at the given items of every session - full-catalog soft-max
         (or mixture), never renormalised over the CANDIDATES (log_softmax over the returned row is the caller's one-liner).  items: [B, M] item ids per session or [M] shared by all

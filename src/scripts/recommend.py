@@ -10,7 +10,11 @@ the item table, no (B, V) score matrix).  --allow FILE / --deny FILE (one item i
 run and --item-bias FILE (`id:value` or `id<TAB>value` per line) is added to the log-probabilities before ranking; the printed
 values are then log-probability + bias (ops.catalog_bias combines the three, the selection kernel applies them).
 --renormalize prints them renormalised over the items that remain eligible (model.recommend(renormalize=True): one more
-fused pass, csrc/score_norm.hip)."""
+fused pass, csrc/score_norm.hip).
+--sample DRAWS the --top items of every session from the model's distribution instead of taking the most probable ones
+(model.sample: without replacement, in draw order; --temperature sharpens or flattens it, --seed fixes the draw).  The
+session key of the noise is the 0-based number of the session in the file (blank lines are not counted), so the output does
+not depend on --batch-size.  The printed values are still the items' log-probabilities, not the sampled keys."""
 import argparse
 import sys
 
@@ -67,6 +71,11 @@ def parser(model):
     p.add_argument('--renormalize', action='store_true',
                    help='print log-probabilities renormalised over the eligible catalogue (--exclude-seen, --allow / --deny, '
                         '--item-bias): per session they sum to one over the items that can be shown')
+    p.add_argument('--sample', action='store_true',
+                   help='draw the --top items from the distribution (without replacement, in draw order) instead of taking '
+                        'the most probable ones')
+    p.add_argument('--temperature', type=float, default=1.0, help='--sample: draw from softmax(log-probability / temperature)')
+    p.add_argument('--seed', type=int, default=0, help='--sample: seed of the draw, in [0, 2^64)')
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -83,6 +92,10 @@ def parse(argv=None):
         p.error('--top must be between 1 and %d (the selection kernel keeps at most %d items per session)' % (MAX_TOP, MAX_TOP))
     if args.batch_size < 1:
         p.error('--batch-size must be positive')
+    if not (0.0 < args.temperature < float('inf')):
+        p.error('--temperature must be positive and finite')
+    if not 0 <= args.seed < 2 ** 64:
+        p.error('--seed must be in [0, 2^64)')
     args.catalog = read_catalog(p, args)
     return args
 
@@ -118,8 +131,14 @@ def main(argv=None):
     try:
         for b in range(0, len(sessions), args.batch_size):
             inputs, _ = collate_fn([(s, 0) for s in sessions[b:b + args.batch_size]])
-            val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen,
-                                       item_bias=item_bias, renormalize=args.renormalize)
+            n = len(sessions[b:b + args.batch_size])
+            if args.sample:
+                val, idx = model.sample(*[x.to(device) for x in inputs], k=args.top, temperature=args.temperature,
+                                        seed=args.seed, session_keys=th.arange(b, b + n, dtype=th.int32),
+                                        exclude_seen=args.exclude_seen, item_bias=item_bias, renormalize=args.renormalize)
+            else:
+                val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen,
+                                           item_bias=item_bias, renormalize=args.renormalize)
             for ids, vals in zip(idx.cpu().tolist(), val.cpu().tolist()):
                 out.write(format_line(ids, vals) + '\n')
     finally:
