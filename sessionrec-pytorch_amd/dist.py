@@ -813,40 +813,51 @@ class VocabParallel:
         sum-all-reduce of `target`), counts its own rows against that common target, and one sum-all-reduce of B integers
         finishes it - no gather of candidate lists, no merge.  data_parallel as in topk(): every rank passes its own B / world
         sessions (session vectors, labels, offsets and lists are all-gathered first) and gets its own sessions' ranks."""
+        def two_passes(tab, mix, labels):
+            if self.n_live > 0:
+                _, target = self.local.rank(*tab, labels, *mix, self.lo, None, True)
+            else:
+                target = torch.zeros(labels.numel(), device=tab[0][0].device, dtype=torch.float32)
+            all_reduce_sum(target, self.group)
+            if self.n_live > 0:
+                rank, _ = self.local.rank(*tab, labels, *mix, self.lo, target, False)
+            else:
+                rank = torch.where(labels < 0, -1, 0).to(torch.int32)
+            if _active(self.group):
+                # sessions without a label carry -1 on every rank: summed as 0, restored afterwards
+                rank = all_reduce_sum(torch.where(labels < 0, torch.zeros_like(rank), rank), self.group)
+            # (a fix-up correction within round-off of the target may overshoot by one: see _ScoringMixin._rank_of)
+            return torch.where(labels < 0, torch.full_like(rank, -1), rank.clamp(min=0))
+        # (no neutral value: the two passes meet in a collective, so a rank without live rows runs the body as well)
+        return self._serve(two_passes, srs, table, cs, off_ex, off_in, listed, data_parallel, extra=labels.to(torch.int64))
+
+    def _serve(self, entry, srs, table, cs, off_ex, off_in, listed, data_parallel, bias=None, group=None, extra=None,
+                neutral=None, combine=None):
+        """The skeleton of every served call over the sharded table (target_rank, select, sample, norm, score_items).  This
+        rank's columns of the bias (_bias_cols); under data_parallel the sessions of all ranks (_gather_sessions) and `extra`,
+        one more per-session tensor [B, ...] (labels, session keys, per-session items); then
+        `entry((srs, live rows, their cs), (off_ex, off_in, listed), extra, **bias keywords)` on a rank with live rows and
+        `neutral(B, device)` - the value `combine` ignores - on a rank without (padding rows are never scored; neutral None:
+        entry runs there too); `combine(result)` over the ranks; under data_parallel this rank's own sessions of the result
+        (a tensor or a tuple of tensors).  The callers' entries splice the two tuples into HipLocal's positional order:
+        (srs, table, cs, [k | items | labels], off_ex, off_in, listed, [drop_listed,] id_lo, ...)."""
         n_loc = srs[0].shape[0]
-        labels = labels.to(torch.int64)
+        bkw = self._bias_cols(bias, group, data_parallel)
         if data_parallel:
-            srs = [all_gather_cat(s.contiguous(), self.group) for s in srs]
-            labels = all_gather_cat(labels.contiguous(), self.group)
-            gat = lambda o: None if o is None else all_gather_cat(o.t().contiguous(), self.group).t().contiguous()
-            off_ex, off_in = gat(off_ex), gat(off_in)
-            if listed is not None:           # lists of different widths on the ranks: pad to the widest
-                w = torch.tensor([listed.shape[1]], dtype=torch.int64, device=listed.device)
-                if _active(self.group):
-                    all_reduce_(w, dist.ReduceOp.MAX, self.group)
-                pad = listed.new_full((listed.shape[0], int(w.item())), -1)
-                pad[:, :listed.shape[1]] = listed
-                listed = all_gather_cat(pad, self.group)
-        live = table[:self.n_live]
-        csl = None if cs is None else cs[:self.n_live]
-        B = srs[0].shape[0]
-        if self.n_live > 0:
-            _, target = self.local.rank(srs, live, csl, labels, off_ex, off_in, listed, self.lo, None, True)
+            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
+            if extra is not None:
+                extra = all_gather_cat(extra.contiguous(), self.group)
+        if neutral is None or self.n_live > 0:
+            csl = None if cs is None else cs[:self.n_live]
+            out = entry((srs, table[:self.n_live], csl), (off_ex, off_in, listed), extra, **bkw)
         else:
-            target = torch.zeros(B, device=srs[0].device, dtype=torch.float32)
-        all_reduce_sum(target, self.group)
-        if self.n_live > 0:
-            rank, _ = self.local.rank(srs, live, csl, labels, off_ex, off_in, listed, self.lo, target, False)
-        else:
-            rank = torch.where(labels < 0, -1, 0).to(torch.int32)
-        if _active(self.group):
-            # sessions without a label carry -1 on every rank: summed as 0, restored afterwards
-            rank = all_reduce_sum(torch.where(labels < 0, torch.zeros_like(rank), rank), self.group)
-        # (a fix-up correction within round-off of the target may overshoot by one: see _ScoringMixin._rank_of)
-        rank = torch.where(labels < 0, torch.full_like(rank, -1), rank.clamp(min=0))
+            out = neutral(srs[0].shape[0], srs[0].device)
+        if combine is not None:
+            out = combine(out)
         if data_parallel:
-            rank = rank[self.rank * n_loc:(self.rank + 1) * n_loc]
-        return rank
+            own = slice(self.rank * n_loc, (self.rank + 1) * n_loc)
+            out = tuple(t[own] for t in out) if isinstance(out, tuple) else out[own]
+        return out
 
     def _bias_cols(self, bias, group, data_parallel):
         """the keywords the local select / score_items take for a bias over GLOBAL ids ([V] or [G, V], the same on every
@@ -880,27 +891,22 @@ class VocabParallel:
         its id_lo (padding rows are never scored), ONE all-gather carries the (value, id) pairs of all ranks, and the lists
         are merged by (value descending, id ascending) - the order of one device.  data_parallel as in topk().  bias ([V] or
         [G, V] over GLOBAL ids, the same on every rank) / group ([B] of this rank's sessions): ops.score_select's."""
-        n_loc = srs[0].shape[0]
-        bkw = self._bias_cols(bias, group, data_parallel)
-        if data_parallel:
-            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
-        B, dev = srs[0].shape[0], srs[0].device
-        if self.n_live > 0:
-            csl = None if cs is None else cs[:self.n_live]
-            val, idx = self.local.select(srs, table[:self.n_live], csl, k, off_ex, off_in, listed, drop_listed, self.lo, **bkw)
-        else:
-            val = torch.full((B, k), float('-inf'), device=dev)
-            idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
-        val, idx = self._merge_lists(val, idx, B, k)
-        if data_parallel:
-            val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
-        return val, idx
+        return self._serve(lambda tab, mix, _, **b: self.local.select(*tab, k, *mix, drop_listed, self.lo, **b),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group,
+                           neutral=self._no_lists(k), combine=self._merge_lists)
 
-    def _merge_lists(self, val, idx, B, k):
+    @staticmethod
+    def _no_lists(k):
+        """the lists of a rank without live rows: k unfilled slots (-inf, -1) per session"""
+        return lambda B, dev: (torch.full((B, k), float('-inf'), device=dev),
+                               torch.full((B, k), -1, device=dev, dtype=torch.int32))
+
+    def _merge_lists(self, pair):
         """the ranks' (value, id) lists [B, k] -> the k best of all of them: ONE all-gather of the pairs, then the order of one
         device (select() and sample())"""
+        val, idx = pair
         if _active(self.group):
-            w = self.world
+            (B, k), w = val.shape, self.world
             pair = all_gather_cat(torch.stack([val.view(torch.int32), idx], 0), self.group).view(w, 2, B, k)
             val = pair[:, 0].permute(1, 0, 2).reshape(B, w * k).view(torch.float32)
             idx = pair[:, 1].permute(1, 0, 2).reshape(B, w * k)
@@ -920,24 +926,12 @@ class VocabParallel:
         function of (seed, session key, GLOBAL id), so the result is the single-device call's, bit for bit.  session_keys:
         [B] integers of this rank's sessions; None = the row index - under data_parallel the GLOBAL row index (rank * B + b),
         and given keys are all-gathered with the sessions."""
-        n_loc = srs[0].shape[0]
-        bkw = self._bias_cols(bias, group, data_parallel)
-        if data_parallel:
-            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
-            if session_keys is not None:
-                session_keys = all_gather_cat(session_keys.reshape(-1).to(torch.int32).contiguous(), self.group)
-        B, dev = srs[0].shape[0], srs[0].device
-        if self.n_live > 0:
-            csl = None if cs is None else cs[:self.n_live]
-            val, idx = self.local.sample(srs, table[:self.n_live], csl, k, off_ex, off_in, listed, drop_listed, self.lo,
-                                         temperature, seed, session_keys, **bkw)
-        else:
-            val = torch.full((B, k), float('-inf'), device=dev)
-            idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
-        val, idx = self._merge_lists(val, idx, B, k)
-        if data_parallel:
-            val, idx = val[self.rank * n_loc:(self.rank + 1) * n_loc], idx[self.rank * n_loc:(self.rank + 1) * n_loc]
-        return val, idx
+        if data_parallel and session_keys is not None:
+            session_keys = session_keys.reshape(-1).to(torch.int32)        # (as they travel)
+        return self._serve(lambda tab, mix, keys, **b: self.local.sample(*tab, k, *mix, drop_listed, self.lo, temperature, seed,
+                                                                         keys, **b),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group, extra=session_keys,
+                           neutral=self._no_lists(k), combine=self._merge_lists)
 
     def norm(self, srs, table, cs, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False, bias=None,
              group=None):
@@ -945,21 +939,10 @@ class VocabParallel:
         contract): every rank takes Z over its own LIVE rows with its id_lo and its columns of the bias (a rank without live
         rows gives -inf), ONE all-gather carries the [world, B] values, and every rank folds them in rank order with the same
         -inf-safe log-sum-exp - equal bits on every rank.  data_parallel, bias and group as in select()."""
-        n_loc = srs[0].shape[0]
-        bkw = self._bias_cols(bias, group, data_parallel)
-        if data_parallel:
-            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
-        B, dev = srs[0].shape[0], srs[0].device
-        if self.n_live > 0:
-            csl = None if cs is None else cs[:self.n_live]
-            z = self.local.norm(srs, table[:self.n_live], csl, off_ex, off_in, listed, drop_listed, self.lo, **bkw)
-        else:
-            z = torch.full((B,), float('-inf'), device=dev, dtype=torch.float32)
-        if _active(self.group):
-            z = lse_fold(all_gather_cat(z.unsqueeze(0), self.group))
-        if data_parallel:
-            z = z[self.rank * n_loc:(self.rank + 1) * n_loc]
-        return z
+        return self._serve(lambda tab, mix, _, **b: self.local.norm(*tab, *mix, drop_listed, self.lo, **b),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group,
+                           neutral=lambda B, dev: torch.full((B,), float('-inf'), device=dev, dtype=torch.float32),
+                           combine=lambda z: lse_fold(all_gather_cat(z.unsqueeze(0), self.group)) if _active(self.group) else z)
 
     def score_items(self, srs, table, cs, items, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
                     bias=None, group=None):
@@ -970,22 +953,15 @@ class VocabParallel:
         passes its own B / world sessions (and their [B / world, M] items; a 1-D list is the same on every rank) and gets its
         own sessions' scores.  bias / group as in select(): the owner of an id adds its bias, so the sum is still one device's
         (the bias holds no +inf: the model-level entry points check it)."""
-        n_loc = srs[0].shape[0]
-        bkw = self._bias_cols(bias, group, data_parallel)
-        if data_parallel:
-            srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
-            if items.dim() == 2:
-                items = all_gather_cat(items.contiguous(), self.group)
-        B = srs[0].shape[0]
-        if self.n_live > 0:
-            csl = None if cs is None else cs[:self.n_live]
-            out = self.local.score_items(srs, table[:self.n_live], csl, items, off_ex, off_in, listed, drop_listed, self.lo, **bkw)
-        else:                                # a rank without live rows owns nothing
-            out = torch.zeros(B, items.shape[-1], device=srs[0].device, dtype=torch.float32)
-        all_reduce_sum(out, self.group)      # (-inf + 0 and -inf + -inf stay -inf: no slot is ever +inf)
-        if data_parallel:
-            out = out[self.rank * n_loc:(self.rank + 1) * n_loc]
-        return out
+        M = items.shape[-1]
+        return self._serve(lambda tab, mix, its, **b: self.local.score_items(*tab, items if its is None else its, *mix,
+                                                                             drop_listed, self.lo, **b),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group,
+                           extra=items if items.dim() == 2 else None,      # (a 1-D list is every rank's already: not gathered)
+                           # a rank without live rows owns nothing
+                           neutral=lambda B, dev: torch.zeros(B, M, device=dev, dtype=torch.float32),
+                           # (-inf + 0 and -inf + -inf stay -inf: no slot is ever +inf)
+                           combine=lambda out: all_reduce_sum(out, self.group))
 
     # ---- replicated-parameter gradients: bucketed all-reduce, launched in backward order ----------------------------------
     N_BUCKETS = 3

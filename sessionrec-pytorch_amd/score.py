@@ -236,9 +236,10 @@ _SAMPLE_WS = {}        # the draws of the serving calls: kind 'sample'
 
 
 def _byte_ws(kind, device, nbytes, cache=None):
-    """never-resized byte scratch, one per (kind, device, size): the kinds never share a buffer, so no two of their launches
-    alias scratch that separate caches kept apart.  cache: the dict that holds it - _BYTE_WS (default) for the evaluation
-    kernels ('topk', 'rank', 'select'), _NORM_WS for score_norm, whose partials live beside them, not among them"""
+    """never-resized byte scratch, one per (kind, device, size): the five kinds never share a buffer, so no two of their
+    launches alias scratch that separate caches kept apart.  cache: the dict that holds it - _BYTE_WS (default) for the
+    evaluation / selection kernels ('topk', 'rank', 'select'), _NORM_WS for score_norm ('norm') and _SAMPLE_WS for
+    score_sample ('sample'), whose scratch lives beside them, not among them"""
     cache = _BYTE_WS if cache is None else cache
     key = (kind, device.index, nbytes)
     ws = cache.get(key)

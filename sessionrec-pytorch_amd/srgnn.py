@@ -22,6 +22,22 @@ import torch.nn.functional as F
 from . import ops
 
 
+class _Serving:
+    """`with _Serving(model):` around a serving entry point: eval mode and torch.no_grad(), the training flag put back"""
+
+    def __init__(self, model):
+        self.model, self.no_grad = model, torch.no_grad()
+
+    def __enter__(self):
+        self.was_training = self.model.training
+        self.model.eval()
+        self.no_grad.__enter__()
+
+    def __exit__(self, *exc):
+        self.no_grad.__exit__(*exc)
+        self.model.train(self.was_training)
+
+
 class _ScoringMixin:
     """Shared scoring head: fused CE for training, materialised log-probs for the forward() API."""
 
@@ -209,11 +225,26 @@ class _ScoringMixin:
             cs, _ = self._col_scale(self._state(sr.shape[0]))
             return self._rank_of([sr], cs, labels, None, None, None)
 
+    # served call of dist.VocabParallel over a row-sharded table <-> (launcher of ops on one device, its own keywords)
+    _ROUTES = {'target_rank': ('score_rank', {}), 'select': ('score_select', {}), 'sample': ('score_sample', {}),
+               'norm': ('score_norm', {}),
+               'score_items': ('score_items', {'checked': True})}   # (model.score_items looked; sample() passes the kernel's ids)
+
+    def _route(self, name):
+        """(callable, its route keywords) of served call `name`: shard.<name> fed as evaluate() feeds the shard
+        (eval_data_parallel) - every shard works on its own rows and ONE small collective combines them (dist.py) - or the
+        launcher of ops on one device.  Both take (srs, table, cs, ...) in the same positional order."""
+        if self.shard is not None:
+            return getattr(self.shard, name), {'data_parallel': self.shard.eval_data_parallel}
+        fn, kw = self._ROUTES[name]
+        return getattr(ops, fn), kw
+
     def _rank_of(self, srs, cs, labels, off_ex, off_in, listed):
-        if self.shard is not None:       # ranks of disjoint row shards add up: one all-reduce of B integers
-            return self.shard.target_rank(srs, self._table(), cs, labels, off_ex, off_in, listed,
-                                          data_parallel=self.shard.eval_data_parallel)
-        rank = ops.score_rank(srs, self._table(), cs, labels, off_ex, off_in, listed)[0]
+        fn, kw = self._route('target_rank')
+        rank = fn(srs, self._table(), cs, labels, off_ex, off_in, listed, **kw)
+        if self.shard is not None:       # (ranks of disjoint row shards add up: the shard's answer is final)
+            return rank
+        rank = rank[0]                   # (one device: (rank, target))
         if listed is not None:
             # the fix-up pass re-scores a listed item in another summation order than the count pass: where its "ex" score is
             # within round-off of the target the two comparisons can disagree and the correction overshoots by one
@@ -278,17 +309,9 @@ class _ScoringMixin:
         pass is skipped instead, the normaliser being taken over the raw logits.  With nothing to renormalise (no item_bias,
         no exclude_seen) the call is the one of renormalize=False, bit for bit."""
         bias = self._item_bias('recommend', item_bias, item_group)
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                return self._recommend(*inputs, k=k, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
-        finally:
-            self.train(was_training)
-
-    def _recommend(self, *inputs, k, exclude_seen, renormalize=False, **bias):
-        srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
-        return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, **bias)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+            return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, **bias)
 
     def _scoring_args(self, *inputs, exclude_seen, raw=False):
         """(srs, cs, off_ex, off_in, listed) under which the score of ops.score_select / score_items / score_norm,
@@ -316,10 +339,8 @@ class _ScoringMixin:
         return srs, cs, off_ex, off_in, listed
 
     def _norm_of(self, srs, cs, off_ex, off_in, listed, drop_listed, **bias):
-        if self.shard is not None:       # every shard over its rows: one all-gather of [W, B] floats, folded in rank order
-            return self.shard.norm(srs, self._table(), cs, off_ex, off_in, listed, drop_listed,
-                                   data_parallel=self.shard.eval_data_parallel, **bias)
-        return ops.score_norm(srs, self._table(), cs, off_ex, off_in, listed, drop_listed, **bias)
+        fn, kw = self._route('norm')
+        return fn(srs, self._table(), cs, off_ex, off_in, listed, drop_listed, **kw, **bias)
 
     def log_mass(self, *inputs, exclude_seen=False, item_bias=None, item_group=None):
         """fp32 [B]: the log of the probability mass, under forward()'s distribution, of the items a filter leaves - the
@@ -329,14 +350,9 @@ class _ScoringMixin:
         over the table (csrc/score_norm.hip), no (B, V) matrix, sharded table included; eval mode under torch.no_grad(),
         item_bias / item_group checked first as in recommend()."""
         bias = self._item_bias('log_mass', item_bias, item_group)
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                srs, cs, off_ex, off_in, listed = self._scoring_args(*inputs, exclude_seen=exclude_seen)
-                return self._norm_of(srs, cs, off_ex, off_in, listed, exclude_seen, **bias)
-        finally:
-            self.train(was_training)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._scoring_args(*inputs, exclude_seen=exclude_seen)
+            return self._norm_of(srs, cs, off_ex, off_in, listed, exclude_seen, **bias)
 
     def _lse(self, sr, cs, inv_scale, st, labels=None):
         """log-sum-exp of every session's logits over the whole catalog: the fused statistics pass (no gradient kept)"""
@@ -361,10 +377,13 @@ class _ScoringMixin:
 
     def _select_of(self, srs, cs, k, off_ex, off_in, listed, drop_listed, **bias):
         """bias: `bias=` / `group=` over global ids (_item_bias), added after the mixture"""
-        if self.shard is not None:       # every shard selects among its rows: one all-gather of [B, k] pairs, one merge
-            return self.shard.select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed,
-                                     data_parallel=self.shard.eval_data_parallel, **bias)
-        return ops.score_select(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, **bias)
+        fn, kw = self._route('select')
+        return fn(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, **kw, **bias)
+
+    def _sample_of(self, srs, cs, k, off_ex, off_in, listed, drop_listed, temperature, seed, session_keys, **bias):
+        fn, kw = self._route('sample')
+        return fn(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, temperature=temperature, seed=seed,
+                  session_keys=session_keys, **kw, **bias)
 
     def sample(self, *inputs, k=1, temperature=1.0, seed=0, session_keys=None, exclude_seen=False, item_bias=None,
                item_group=None, renormalize=False):
@@ -381,21 +400,10 @@ class _ScoringMixin:
         item_group, k, temperature and seed are checked before anything of the model runs."""
         bias = self._item_bias('sample', item_bias, item_group)
         k, _, seed = ops.sample_scalars('sample', k, temperature, seed)
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
-                if self.shard is not None:
-                    _, ids = self.shard.sample(srs, self._table(), cs, k, off_ex, off_in, listed, exclude_seen,
-                                               data_parallel=self.shard.eval_data_parallel, temperature=temperature, seed=seed,
-                                               session_keys=session_keys, **bias)
-                else:
-                    _, ids = ops.score_sample(srs, self._table(), cs, k, off_ex, off_in, listed, exclude_seen,
-                                              temperature=temperature, seed=seed, session_keys=session_keys, **bias)
-                return self._items_of(srs, cs, ids, off_ex, off_in, listed, exclude_seen, **bias), ids
-        finally:
-            self.train(was_training)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+            _, ids = self._sample_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, temperature, seed, session_keys, **bias)
+            return self._items_of(srs, cs, ids, off_ex, off_in, listed, exclude_seen, **bias), ids
 
     def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """fp32 [B, M]: the log-probability forward() returns at the given items of every session - full-catalog soft-max
@@ -415,24 +423,16 @@ class _ScoringMixin:
             lo, hi = (int(x) for x in torch.aminmax(items.detach()))
             if lo < -1 or hi >= n:
                 raise ValueError('score_items: item id %d; ids are in [0, %d), or -1 for a padding slot' % (lo if lo < -1 else hi, n))
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                return self._score_items(*inputs, items=items, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
-        finally:
-            self.train(was_training)
+        with _Serving(self):
+            return self._score_items(*inputs, items=items, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
 
     def _score_items(self, *inputs, items, exclude_seen, renormalize=False, **bias):
         srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
         return self._items_of(srs, cs, items, off_ex, off_in, listed, exclude_seen, **bias)
 
     def _items_of(self, srs, cs, items, off_ex, off_in, listed, drop_listed, **bias):
-        items = items.to(srs[0].device)
-        if self.shard is not None:       # every shard scores the ids it owns, the others give 0: one all-reduce of [B, M] floats
-            return self.shard.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed,
-                                          data_parallel=self.shard.eval_data_parallel, **bias)
-        return ops.score_items(srs, self._table(), cs, items, off_ex, off_in, listed, drop_listed, checked=True, **bias)
+        fn, kw = self._route('score_items')
+        return fn(srs, self._table(), cs, items.to(srs[0].device), off_ex, off_in, listed, drop_listed, **kw, **bias)
 
     def rerank(self, *inputs, items, k=None, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """(log_probs fp32 [B, n], item_ids int32 [B, n]), n = M or min(k, M): the candidates of score_items ordered by
