@@ -647,6 +647,26 @@ int srec_score_sample(const float* sr, int ld_sr, long comp_stride, const float*
 int srec_sample_uniform(unsigned long long seed, const int* session_keys, int n_b, const int* ids, int n_v,
                         unsigned* h_out, float* w_out);
 
+/* ---- serving: diversified top-N - greedy MMR re-rank of a pool, and intra-list diversity (diversify.hip) ------------------
+ * Per session a pool of M slots; slot i has a row index row[b * M + i] into the row source X (fp32, n_rows rows of d columns,
+ * leading dimension ld_x) and a value s[b * M + i].  A slot whose row index is < 0 or >= n_rows is UNFILLED: X is never read
+ * for it and it is never picked.
+ *   sim(i, j) = <X_i, X_j> / (max(|X_i|, 1e-12) * max(|X_j|, 1e-12))        a zero row: 0 to everything, never NaN
+ *   for t = 0 .. K-1:  m_t(i) = s[i] - theta * pen_t(i) over the filled slots not yet picked; pen_0 = 0, and for t >= 1
+ *     pen_t(i) = max of sim(i, j) over the slots j picked so far - the raw maximum, not clamped at 0.  The pick is the slot
+ *     with the largest m_t, ties to the lower slot.
+ * pick [B, K] int32: the slot numbers in pick order, -1 once the filled slots run out.  val [B, K]: s[pick], copied and not
+ * recomputed (the pool's own bits), -INFINITY in the tail.  mmr [B, K] (nullable): the winning m_t, -INFINITY in the tail.
+ * ild [B] (nullable): 1 - mean_{a<b} sim(pick_a, pick_b) over the filled picks, 0 with fewer than two.
+ * theta (the diversity weight) is finite and >= 0; theta == 0 gives m_t = s[i] whatever the rows hold, so equal values come
+ * back as the first K filled slots in slot order.  The similarity does not depend on a positive per-row factor (the column
+ * scale cs of the scoring calls), so there is no cs argument.
+ * One workgroup per session, no atomics, no workspace: a session's result is the same bits in any batch.
+ * SREC_BAD_ARG and no launch unless 1 <= K <= M <= SREC_SELECT_MAXK, d % 4 == 0, 0 < d <= 1024, ld_x % 4 == 0, ld_x >= d,
+ * X 16-byte aligned, n_rows >= 0, theta finite and >= 0 (not negative, NaN or infinite), X / row / s / pick / val non-null. */
+int srec_diversify(const float* X, int ld_x, long n_rows, const int* row, const float* s, int B, int M, int K, int d,
+                   float theta, int* pick, float* val, float* mmr, float* ild, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

@@ -435,6 +435,10 @@ class HipLocal:
         """this shard's log-normaliser of ops.score_norm: rows [id_lo, id_lo + n) of the catalog.  bias: as in select()"""
         return self.ops.score_norm(srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
+    def diversify(self, X, row, val, k, diversity):
+        """ops.diversify over rows the caller has bounded (checked): (val [B,k], pick [B,k], mmr [B,k], ild [B])"""
+        return self.ops.diversify(X, row, val, k, diversity, checked=True)
+
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
 
@@ -833,7 +837,8 @@ class VocabParallel:
 
     def _serve(self, entry, srs, table, cs, off_ex, off_in, listed, data_parallel, bias=None, group=None, extra=None,
                 neutral=None, combine=None):
-        """The skeleton of every served call over the sharded table (target_rank, select, sample, norm, score_items).  This
+        """The skeleton of every served call over the sharded table (target_rank, select, sample, norm, score_items; diversify
+        gathers its pool's rows through it, the ids standing where the session vectors do).  This
         rank's columns of the bias (_bias_cols); under data_parallel the sessions of all ranks (_gather_sessions) and `extra`,
         one more per-session tensor [B, ...] (labels, session keys, per-session items); then
         `entry((srs, live rows, their cs), (off_ex, off_in, listed), extra, **bias keywords)` on a rank with live rows and
@@ -962,6 +967,34 @@ class VocabParallel:
                            neutral=lambda B, dev: torch.zeros(B, M, device=dev, dtype=torch.float32),
                            # (-inf + 0 and -inf + -inf stay -inf: no slot is ever +inf)
                            combine=lambda out: all_reduce_sum(out, self.group))
+
+    def diversify(self, table, ids, val, k, diversity, data_parallel=False):
+        """the greedy MMR re-rank of ops.diversify over the sharded table (val [B,k], pick [B,k], mmr [B,k], ild [B]): ids
+        [B, M] GLOBAL item ids of every session's pool (-1 = unfilled), val [B, M] their values - what select() returned, the
+        same on every rank (data_parallel: this rank's own sessions, as select() returned them).  A cosine needs both rows, and
+        they may live on different shards: every rank writes the rows it owns among the pool's ids into a zeroed [B, M, d]
+        buffer (the owner rule of score_items: an id in [lo, lo + n_live); padding rows are never owners, an unfilled slot has
+        none), ONE sum-all-reduce completes it - x + 0 is exact, so the rows are one device's rows - and the kernel runs on
+        the buffer with row = arange, on every rank or, under data_parallel, on the rank's own sessions: the result is the
+        single-device call's, bit for bit.  The exchange is B * M * d * 4 bytes per call (B: the sessions of all ranks;
+        8 MB at B 64, M 128, d 256) - the price of cosines across shards; through _serve, which gathers the ids of all ranks'
+        sessions under data_parallel and hands back this rank's slice of the buffer."""
+        M, d = ids.shape[1], self.d
+
+        def owned(tab, _mix, _extra):
+            (all_ids,), live = tab[0], tab[1]
+            loc = all_ids.to(torch.int64) - self.lo
+            own = (loc >= 0) & (loc < self.n_live)
+            rows = live.detach().index_select(0, loc.clamp(0, self.n_live - 1).reshape(-1)).view(all_ids.shape[0], M, d)
+            return torch.where(own.unsqueeze(-1), rows, torch.zeros((), device=rows.device, dtype=rows.dtype))
+        # (the ids stand where the session vectors of the other routes do: _serve gathers them with the sessions)
+        buf = self._serve(owned, [ids.contiguous()], table, None, None, None, None, data_parallel,
+                          neutral=lambda B, dev: torch.zeros(B, M, d, device=dev, dtype=torch.float32),
+                          combine=lambda rows: all_reduce_sum(rows.contiguous(), self.group))
+        B = ids.shape[0]
+        row = torch.arange(B * M, device=ids.device, dtype=torch.int32).view(B, M)
+        row = torch.where(ids < 0, torch.full_like(row, -1), row)
+        return self.local.diversify(buf.reshape(B * M, d), row, val, k, diversity)
 
     # ---- replicated-parameter gradients: bucketed all-reduce, launched in backward order ----------------------------------
     N_BUCKETS = 3

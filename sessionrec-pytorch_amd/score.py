@@ -642,6 +642,73 @@ def score_norm(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_liste
     return out
 
 
+def diversify_scalars(who, k, diversity, M=None):
+    """(k, diversity) as the library takes them, or ValueError in the words of `who`: k in 1 .. 128 (and <= M, the pool, when
+    given: M itself in 1 .. 128), diversity a finite number >= 0.  No launch, no library call"""
+    kmax = CONST['SREC_SELECT_MAXK']
+    k = int(k)
+    if M is not None and not 1 <= int(M) <= kmax:
+        raise ValueError('%s: a pool of %d slots per session; csrc/diversify.hip takes between 1 and %d' % (who, M, kmax))
+    if k < 1 or k > (kmax if M is None else int(M)):
+        raise ValueError('%s: k = %d; csrc/diversify.hip picks between 1 and %s items per session'
+                         % (who, k, '%d' % kmax if M is None else 'the pool\'s %d' % M))
+    try:
+        diversity = float(diversity)
+    except (TypeError, ValueError):
+        raise ValueError('%s: diversity must be a number, got %r' % (who, diversity)) from None
+    if not (0.0 <= diversity <= 3.4e38):
+        raise ValueError('%s: diversity = %r; it must be finite and >= 0' % (who, diversity))
+    return k, diversity
+
+
+def diversify(X, row, val, k, diversity, checked=False):
+    """(val fp32 [B,k], pick int32 [B,k], mmr fp32 [B,k], ild fp32 [B]): the greedy MMR re-rank of a pool of M <= 128 slots
+    per session (csrc/diversify.hip, one workgroup per session: no [B, M, d] gather, no [B, M, M] Gram matrix, no loop of
+    launches).  Slot i of session b has the row X[row[b, i]] and the value val[b, i]; row < 0 is an unfilled slot.
+      sim(i, j) = <X_i, X_j> / (max(|X_i|, 1e-12) max(|X_j|, 1e-12))  (a zero row: 0 to everything, never NaN)
+      for t = 0 .. k-1: m_t(i) = val[i] - diversity * pen_t(i) over the filled slots not yet picked, pen_0 = 0, pen_t(i) =
+      the maximum of sim(i, j) over the slots picked so far (raw, not clamped at 0); the pick is the largest m_t, ties to
+      the lower slot.
+    pick: the slot numbers in pick order, -1 once the filled slots run out; the returned val: val[pick] copied bit for bit,
+    -inf in the tail; mmr: the winning m_t; ild: 1 - the mean of sim over the pairs of filled picks, 0 with fewer than two.
+    diversity is finite and >= 0; 0 gives m_t = val[i] whatever the rows are (equal values: the first k filled slots in slot
+    order).  A positive factor per row (the column scale cs) does not change sim, so none is taken.
+    X: fp32 [n, d] (a row-strided view is taken as it is), d % 4 == 0, d <= 1024; row: [B, M] of any integer dtype;
+    val: fp32 [B, M]; 1 <= k <= M <= 128.  Wrong shapes, dtypes and scalars raise ValueError before any launch, and - unless
+    checked=True, the caller has looked - so does a row >= n (one aminmax, one device-to-host read).  The kernel itself
+    treats a row >= n as unfilled and never dereferences it."""
+    who = 'diversify'
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError('%s: X must be a 2-D fp32 tensor of rows, got %s %s' % (who, X.dtype, tuple(X.shape)))
+    n, d = X.shape
+    if d < 4 or d % 4 or d > 1024:
+        raise ValueError('%s: rows of %d columns; csrc/diversify.hip takes d %% 4 == 0, d <= 1024' % (who, d))
+    row, val = row.detach(), val.detach()
+    if row.is_floating_point() or row.is_complex() or row.dtype == torch.bool or row.dim() != 2:
+        raise ValueError('%s: row must be an integer tensor [B, M], got %s %s' % (who, row.dtype, tuple(row.shape)))
+    if val.dtype != torch.float32 or val.shape != row.shape:
+        raise ValueError('%s: val must be fp32 %s like row, got %s %s' % (who, tuple(row.shape), val.dtype, tuple(val.shape)))
+    B, M = row.shape
+    k, diversity = diversify_scalars(who, k, diversity, M)
+    if not checked and B > 0:
+        lo, hi = (int(x) for x in torch.aminmax(row))
+        if hi >= n:
+            raise ValueError('%s: row %d; X has %d rows (a negative row is an unfilled slot)' % (who, hi, n))
+    X = _rows(X.detach())
+    dev = X.device
+    out_val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    pick = torch.empty(B, k, device=dev, dtype=torch.int32)
+    mmr = torch.empty(B, k, device=dev, dtype=torch.float32)
+    ild = torch.empty(B, device=dev, dtype=torch.float32)
+    if B == 0:
+        return out_val, pick, mmr, ild
+    row = row.to(device=dev, dtype=torch.int32).contiguous()
+    val = val.to(dev).contiguous()
+    lib.srec_diversify(ptr(X), _ld(X), n, ptr(row), ptr(val), B, M, k, d, diversity, ptr(pick), ptr(out_val), ptr(mmr),
+                       ptr(ild), stream())
+    return out_val, pick, mmr, ild
+
+
 def _logp_cols(sr, ld_sr, table, cs, lse):
     """[B, V] log-probabilities z[b, v] - lse[b] of the rows of `table` (fp32): a view of a buffer whose rows are padded to
     a multiple of 4 columns"""

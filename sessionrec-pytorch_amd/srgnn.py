@@ -227,7 +227,7 @@ class _ScoringMixin:
 
     # served call of dist.VocabParallel over a row-sharded table <-> (launcher of ops on one device, its own keywords)
     _ROUTES = {'target_rank': ('score_rank', {}), 'select': ('score_select', {}), 'sample': ('score_sample', {}),
-               'norm': ('score_norm', {}),
+               'norm': ('score_norm', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
                'score_items': ('score_items', {'checked': True})}   # (model.score_items looked; sample() passes the kernel's ids)
 
     def _route(self, name):
@@ -312,6 +312,65 @@ class _ScoringMixin:
         with _Serving(self):
             srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
             return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, **bias)
+
+    def recommend_diverse(self, *inputs, k=20, diversity=0.5, pool=None, exclude_seen=False, item_bias=None, item_group=None,
+                          renormalize=False):
+        """(log_probs fp32 [B,k], item_ids int32 [B,k]) in PICK order: a slate of k items that trades a little probability for
+        coverage - the greedy MMR re-rank (csrc/diversify.hip, ops.diversify) of the `pool` most probable items.  The pool is
+        exactly what recommend(k=pool, same keywords) returns (pool: default min(128, max(4 k, k)); k <= pool <= 128), so
+        exclude_seen, item_bias / item_group, renormalize and mixtures mean what they mean there.  With slot i of the pool
+        holding item v_i and value s_i (its log-probability, plus bias), and sim the cosine of two rows of the item table
+        (sim(i, j) = <E_i, E_j> / (max(|E_i|, 1e-12) max(|E_j|, 1e-12)), a zero row: 0), step t picks the slot with the
+        largest  s_i - diversity * max_{j picked} sim(i, j)  (no penalty at t = 0; the raw maximum, not clamped at 0; ties
+        to the better-ranked slot).  The values are the pool's own numbers at the picks, bit for bit; unfilled slots (the
+        pool had fewer than k eligible items) are (-inf, -1).  diversity: finite, >= 0; 0 returns the first k columns of
+        recommend(k=pool).  One more launch, one workgroup per session: no [B, pool, d] gather and no [B, pool, pool] Gram
+        matrix on one device; a row-sharded table exchanges B * pool * d * 4 bytes (dist.VocabParallel.diversify).  Runs in
+        eval mode under torch.no_grad(); k, diversity, pool and item_bias / item_group are checked before anything of the
+        model runs."""
+        k, diversity, pool = self._diverse_args('recommend_diverse', k, diversity, pool)
+        bias = self._item_bias('recommend_diverse', item_bias, item_group)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+            val, ids = self._select_of(srs, cs, pool, off_ex, off_in, listed, exclude_seen, **bias)
+            pval, pick, _, _ = self._diversify_of(ids, val, k, diversity)
+            picked = ids.gather(1, pick.clamp(min=0).long())
+            return pval, torch.where(pick < 0, torch.full_like(picked, -1), picked)
+
+    @staticmethod
+    def _diverse_args(who, k, diversity, pool):
+        """(k, diversity, pool) checked: pool defaults to min(128, max(4 k, k)), k <= pool <= 128 (ValueError otherwise)"""
+        k, diversity = ops.diversify_scalars(who, k, diversity)
+        pool = min(128, max(4 * k, k)) if pool is None else int(pool)
+        if not k <= pool <= 128:
+            raise ValueError('%s: pool = %d; it holds at least the k = %d items asked for and at most 128 (recommend()\'s limit)'
+                             % (who, pool, k))
+        return k, diversity, pool
+
+    def _diversify_of(self, ids, val, k, diversity):
+        """(val, pick, mmr, ild) of ops.diversify over the rows of the item table at the global ids [B, M] (-1: unfilled)"""
+        fn, kw = self._route('diversify')
+        return fn(self._table(), ids, val, k, diversity, **kw)
+
+    def list_diversity(self, item_ids):
+        """fp32 [B]: the intra-list diversity of given lists, 1 - the mean cosine between the item-table rows of every pair of
+        a list's items (the similarity of recommend_diverse; 0 for a list with fewer than two items) - the number that
+        compares a plain top-N with a diversified one.  item_ids: [B, M] integer ids, -1 = padding, M <= 128; an id < -1 or
+        >= num_items raises ValueError before anything is launched.  The kernel of recommend_diverse with diversity 0 and
+        k = M; sharded table included.  Runs under torch.no_grad()."""
+        ids = item_ids.detach()
+        if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() != 2:
+            raise ValueError('list_diversity: item_ids must be an integer tensor [B, M], got %s %s' % (ids.dtype, tuple(ids.shape)))
+        B, M = ids.shape
+        ops.diversify_scalars('list_diversity', M, 0.0, M)
+        n = self.shard.V if self.shard is not None else self._table().shape[0]
+        if ids.numel() > 0:
+            lo, hi = (int(x) for x in torch.aminmax(ids))
+            if lo < -1 or hi >= n:
+                raise ValueError('list_diversity: item id %d; ids are in [0, %d), or -1 for a padding slot' % (lo if lo < -1 else hi, n))
+        with _Serving(self):
+            ids = ids.to(self._table().device)
+            return self._diversify_of(ids, torch.zeros(ids.shape, device=ids.device, dtype=torch.float32), M, 0.0)[3]
 
     def _scoring_args(self, *inputs, exclude_seen, raw=False):
         """(srs, cs, off_ex, off_in, listed) under which the score of ops.score_select / score_items / score_norm,

@@ -14,7 +14,11 @@ fused pass, csrc/score_norm.hip).
 --sample DRAWS the --top items of every session from the model's distribution instead of taking the most probable ones
 (model.sample: without replacement, in draw order; --temperature sharpens or flattens it, --seed fixes the draw).  The
 session key of the noise is the 0-based number of the session in the file (blank lines are not counted), so the output does
-not depend on --batch-size.  The printed values are still the items' log-probabilities, not the sampled keys."""
+not depend on --batch-size.  The printed values are still the items' log-probabilities, not the sampled keys.
+--diversity THETA re-ranks the --pool M most probable items of every session (default min(128, max(4 top, top))) into a slate
+of --top items that trades probability for coverage (model.recommend_diverse: greedy MMR on the cosine of the item rows, one
+more kernel, csrc/diversify.hip); the output has the same format, in PICK order, with the items' own values.  Not together
+with --sample."""
 import argparse
 import sys
 
@@ -76,6 +80,12 @@ def parser(model):
                         'the most probable ones')
     p.add_argument('--temperature', type=float, default=1.0, help='--sample: draw from softmax(log-probability / temperature)')
     p.add_argument('--seed', type=int, default=0, help='--sample: seed of the draw, in [0, 2^64)')
+    p.add_argument('--diversity', type=float, default=None, metavar='THETA',
+                   help='re-rank the --pool most probable items into a diversified slate: each pick maximises value - THETA * '
+                        '(largest cosine to the items picked so far); finite, >= 0; printed in pick order')
+    p.add_argument('--pool', type=int, default=None, metavar='M',
+                   help='--diversity: items per session the slate is picked from, --top <= M <= %d (default: min(%d, 4 * top))'
+                        % (MAX_TOP, MAX_TOP))
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -96,6 +106,15 @@ def parse(argv=None):
         p.error('--temperature must be positive and finite')
     if not 0 <= args.seed < 2 ** 64:
         p.error('--seed must be in [0, 2^64)')
+    if args.diversity is not None:
+        if args.sample:
+            p.error('--diversity re-ranks the most probable items and --sample draws them: give one of the two')
+        if not (0.0 <= args.diversity < float('inf')):
+            p.error('--diversity must be finite and >= 0')
+        if args.pool is not None and not args.top <= args.pool <= MAX_TOP:
+            p.error('--pool must be between --top and %d' % MAX_TOP)
+    elif args.pool is not None:
+        p.error('--pool goes with --diversity')
     args.catalog = read_catalog(p, args)
     return args
 
@@ -136,6 +155,10 @@ def main(argv=None):
                 val, idx = model.sample(*[x.to(device) for x in inputs], k=args.top, temperature=args.temperature,
                                         seed=args.seed, session_keys=th.arange(b, b + n, dtype=th.int32),
                                         exclude_seen=args.exclude_seen, item_bias=item_bias, renormalize=args.renormalize)
+            elif args.diversity is not None:
+                val, idx = model.recommend_diverse(*[x.to(device) for x in inputs], k=args.top, diversity=args.diversity,
+                                                   pool=args.pool, exclude_seen=args.exclude_seen, item_bias=item_bias,
+                                                   renormalize=args.renormalize)
             else:
                 val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen,
                                            item_bias=item_bias, renormalize=args.renormalize)
