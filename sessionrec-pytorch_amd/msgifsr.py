@@ -336,7 +336,7 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         """the operand copies of this step's weights (k-gram GRUs, the first MSHGNN layer's fc weights and its folded attention
         vectors, the read-out head) and the batch intake of a captured step in ONE launch ahead of the lookup (ops.step_prologue,
         csrc/prep.hip) - 5 launches of 5 - 8 us each otherwise, one in front of each reader.  The conditions mirror the
-        readers' (the GRUs' is the readers' own, ops.expand_path); a reader that finds no copies makes its own."""
+        readers' (the GRUs' and the head's are the readers' own, ops.expand_path / ops.head_path); a reader that finds no copies makes its own."""
         K, d = self.order, self.embedding_dim
         bf16 = ops.PRECISION['matmul'] == 'bf16'
         grad = torch.is_grad_enabled() and self.training
@@ -355,7 +355,8 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             if bf16 and d % 64 == 0 and nm <= 8 and all(params[4 * m].is_contiguous() for m in range(nm)):
                 w16 = [params[4 * m] for m in range(nm)]
         live = range(K) if (K == 1 or self.fusion) else (0,)
-        if (bf16 and ops.FUSED_HEAD and self.norm and K > 1 and len(live) <= 4 and d in (128, 256) and 1 < mg.B <= ops.HEAD_FUSED_MAX_B):
+        # (K > 1 is this launch's own condition: an order-1 model's fused head makes its copies itself, as it always did)
+        if K > 1 and ops.head_path(d, len(live), mg.B, self.norm) == 'fused':
             ro = self.readout
             hw = [w for i in live for w in (ro.fc_u[i].weight, ro.fc_v[i].weight, self.fc_sr[i].weight)]
             if all(w.is_contiguous() for w in hw):

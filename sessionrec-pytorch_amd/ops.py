@@ -16,6 +16,9 @@ Re-exported from the modules imported at the end of this file (ops.X stays the w
             score_topk, score_rank, score_select, score_sample, sample_noise, sample_scalars, score_items, score_norm, use_bf16_scoring, sr16_written, sr16_claim, finish_table_grad, MixtureArgs,
             _bf16_dim_ok, _prepare_sr, _ce_fwd, _ce_bwd, _mixture_args, _byte_ws, _logp_cols, _pad_rows, BiasArgs, _bias_args,
             catalog_bias, diversify, diversify_scalars
+  head.py   the attention read-out head: SegAttn, seg_attn, ReadoutHead, ReadoutHeadFused, readout_head, readout_head_fused,
+            readout_head_fused_ok, head_path, head_wfrag, _head_wfrag_args, wfrag_missing, wfrag_put, HeadOrder, head_fwd_desc,
+            head_bwd_desc, HEAD_FUSED_MAX_B
 """
 import ctypes as _ct
 import os
@@ -62,8 +65,6 @@ def _ws(n, device):
 
 
 _GEMM_WS = {}
-
-
 
 
 def _gemm_ws(device):
@@ -119,11 +120,10 @@ def check_limits(mg, deg=None):
                          '(csrc/common.h): truncate sessions' % (m['max_deg'], L[deg]))
 
 
-FUSED_GRU = True        # tests flip these two to compare the fused kernels (gruf.hip / grufb.hip, headf.hip) with the
-FUSED_HEAD = True       # step-by-step / grouped launch sequences they replace; the product path never does
+FUSED_GRU = True        # tests flip this to compare the fused GRU kernels (gruf.hip / grufb.hip) with the step-by-step
+#                         launch sequence they replace; the product path never does
 PRECISION = {'matmul': 'fp32'}      # 'fp32': exact fp32 MFMA everywhere; 'bf16': bf16-operand MFMA for the
                                     # forward / backward-data products and the scoring kernels (config C3)
-_WT_CACHE = {}
 
 
 def set_precision(mode):
@@ -133,9 +133,8 @@ def set_precision(mode):
 
 
 def weights_changed():
-    """called by the optimizer after it updated parameters: cached transposed weight copies are stale"""
-    _WT_CACHE.clear()
-    _HEAD_WF_CACHE.clear()
+    """called by the optimizer after it updated parameters: the per-step operand copies of weights are stale"""
+    _HEAD_WF.clear()
     _WPREP.clear()
 
 
@@ -152,14 +151,6 @@ def _wprep_take(kind, w):
 
 def _wprep_put(kind, w, bufs):
     _WPREP[(kind, w.data_ptr(), tuple(w.shape))] = (w._version, bufs)
-
-
-def _transposed(w):
-    key = (w.data_ptr(), tuple(w.shape), w.stride(0))
-    t = _WT_CACHE.get(key)
-    if t is None:
-        t = _WT_CACHE[key] = w.t().contiguous()
-    return t
 
 
 def _bf16_ok(K, *ts):
@@ -1059,51 +1050,6 @@ def normalize_stack(xs, eps_mode=0, dyns=None):
     return NormalizeStack.apply(eps_mode, dyns, *xs)
 
 
-class SegAttn(torch.autograd.Function):
-    """alpha = softmax_session(fc_e(sigmoid(U + Vq[b])));  out_b = sum_i alpha_i x_i"""
-
-    @staticmethod
-    def forward(ctx, U, Vq, we, X, seg, dynB):
-        U, Vq, X = _rows(U), _rows(Vq), _rows(X)
-        ctx.defer, ctx.wparams = defer_scope(), [we]
-        we = we.reshape(-1).contiguous()
-        B, h = Vq.shape
-        N, D = X.shape
-        alpha = torch.empty(N, device=X.device, dtype=torch.float32)      # live nodes written, padded never read
-        out = torch.empty(B, D, device=X.device, dtype=torch.float32)
-        lib.srec_seg_attn_fwd(ptr(U), _ld(U), ptr(Vq), _ld(Vq), ptr(we), ptr(X), _ld(X), ptr(seg), B, ptr(dynB), h, D,
-                              ptr(alpha), ptr(out), D, stream())
-        ctx.save_for_backward(U, Vq, we, X, alpha, seg)
-        ctx.dynB = dynB
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        U, Vq, we, X, alpha, seg = ctx.saved_tensors
-        gout = _rows(gout)
-        B, h = Vq.shape
-        N, D = X.shape
-        dX = torch.empty(N, D, device=X.device, dtype=torch.float32)      # rows behind the live nodes zeroed in-kernel
-        dU = torch.empty(N, h, device=X.device, dtype=torch.float32)
-        dVq = torch.empty(B, h, device=X.device, dtype=torch.float32)
-        dwp = torch.empty(B, h, device=X.device, dtype=torch.float32)
-        lib.srec_seg_attn_bwd(ptr(gout), _ld(gout), ptr(X), _ld(X), ptr(alpha), ptr(U), _ld(U), ptr(Vq), _ld(Vq),
-                              ptr(we), ptr(seg), B, ptr(ctx.dynB), h, D, N, ptr(dX), D, ptr(dU), h, ptr(dVq), h, ptr(dwp),
-                              h, stream())
-        dwe = torch.empty(h, device=X.device, dtype=torch.float32)
-        if h % 4 == 0 and can_defer(ctx.defer, ctx.wparams):
-            # d fc_e = the column sums of the per-session rows (dead sessions' rows are zeros): a 'tall' task of the ONE
-            # end-of-backward slab-sum launch instead of two launches here
-            defer_slab_sum(dwp, dwe, True, tall=True)
-        else:
-            col_sum(dwp, B, h, dwe, ctx.dynB)
-        return dU, dVq, dwe.view(1, h), dX, None, None
-
-
-def seg_attn(U, Vq, we, X, seg, dynB=None):
-    return SegAttn.apply(U, Vq, we, X, seg, dynB)
-
-
 def gemm_f32_group(probs, split3=False, defer=None):
     """defer: a list of output tensors - the split-K slab sums of the group's weight-gradient ('tn', whole contiguous output
     tensor) problems that write one of them join the end-of-backward slab-sum launch (defer_slab_sum) instead of a reduce
@@ -1166,316 +1112,6 @@ def _ones4(n, device):
     if t is None or t.shape[0] < n:
         t = _ONES4[str(device)] = torch.ones(n, 4, device=device, dtype=torch.float32)
     return t
-
-
-class ReadoutHead(torch.autograd.Function):
-    """Attention read-out + session-vector projection of MSGIFSR (msgifsr.py:127-146 AttnReadout, :272-279 fc_sr) for
-    every live order as grouped launches - exact fp32 in fp32 mode, 3-term hi / lo bf16 splits (fp32-grade, ~2^-17) in
-    bf16 mode, like the fused head of d = 128 / 256:
-        U_i = allf Wu_i^T + bu_i;  Vq_i = v_i Wv_i^T;  alpha_i = softmax_session(we_i . sigmoid(U_i + Vq_i[b]));
-        g_i = sum alpha_i allf;  s_i = [v_i | g_i] Wsr_i^T
-    forward: 1 grouped GEMM (all U, Vq) + per order (read-out kernel, concat) + 1 grouped GEMM (all s);
-    backward: 1 grouped GEMM (d cat, d Wsr) + per order read-out backward + 1 grouped GEMM (+ 1 slab reduce) for
-    d allf += dU Wu, d Wu, d v += dVq Wv, d Wv + the two bias / fc_e column sums.  The same products launched one by one
-    were 9 GEMM + 7 split-K reduce + 2 accumulate nodes of the captured step."""
-
-    @staticmethod
-    def forward(ctx, allf, seg, dT, dB, *flat):
-        n = len(flat) // 6
-        allf = _rows(allf)
-        NT, D = allf.shape
-        dev = allf.device
-        per = []
-        for i in range(n):
-            v, Wu, bu, Wv, we, Wsr = flat[6 * i:6 * i + 6]
-            per.append((_rows(v), _rows(Wu), bu, _rows(Wv), we.reshape(-1).contiguous(), _rows(Wsr)))
-        B = per[0][0].shape[0]
-        h = per[0][1].shape[0]
-        Us = [torch.empty(NT, h, device=dev, dtype=torch.float32) for _ in range(n)]
-        Vqs = [torch.empty(B, h, device=dev, dtype=torch.float32) for _ in range(n)]
-        probs = []
-        for i, (v, Wu, bu, Wv, we, Wsr) in enumerate(per):
-            probs.append(('nt', allf, Wu, Us[i], bu, dT, 0.0))
-            probs.append(('nt', v, Wv, Vqs[i], None, dB, 0.0))
-        gemm_f32_group(probs, split3=PRECISION['matmul'] == 'bf16')
-        alphas, cats, outs, probs = [], [], [], []
-        for i, (v, Wu, bu, Wv, we, Wsr) in enumerate(per):
-            alpha = torch.empty(NT, device=dev, dtype=torch.float32)
-            dv = v.shape[1]
-            cat = None
-            # only a tensor its producer tagged as the left half of a PRIVATE [B, dv + D] buffer (permute_and_pick /
-            # norm_permute_pick): any other column slice of a live [B, 2 d] tensor must not have its right half overwritten
-            if B > 1 and getattr(flat[6 * i], '_srec_cat_left', False) and v.stride(0) == dv + D and v.stride(1) == 1:
-                try:                                       # v already is the left half of a [B, dv + D] buffer (permute_and_pick)
-                    cat = v.as_strided((B, dv + D), (dv + D, 1))
-                except RuntimeError:
-                    cat = None
-            if cat is not None:
-                lib.srec_seg_attn_fwd(ptr(Us[i]), h, ptr(Vqs[i]), h, ptr(we), ptr(allf), _ld(allf), ptr(seg), B, ptr(dB), h, D,
-                                      ptr(alpha), cat[:, dv:].data_ptr(), dv + D, stream())
-            else:
-                srg = torch.empty(B, D, device=dev, dtype=torch.float32)
-                lib.srec_seg_attn_fwd(ptr(Us[i]), h, ptr(Vqs[i]), h, ptr(we), ptr(allf), _ld(allf), ptr(seg), B, ptr(dB), h, D,
-                                      ptr(alpha), ptr(srg), D, stream())
-                cat = torch.empty(B, dv + D, device=dev, dtype=torch.float32)
-                lib.srec_cat_cols(ptr(v), _ld(v), dv, ptr(srg), D, D, B, ptr(cat), stream())
-            out = torch.empty(B, Wsr.shape[0], device=dev, dtype=torch.float32)
-            probs.append(('nt', cat, Wsr, out, None, dB, 0.0))
-            alphas.append(alpha)
-            cats.append(cat)
-            outs.append(out)
-        gemm_f32_group(probs, split3=PRECISION['matmul'] == 'bf16')
-        ctx.save_for_backward(allf, seg, *[t for i in range(n) for t in (per[i][0], per[i][1], per[i][3], per[i][4], per[i][5],
-                                                                        Us[i], Vqs[i], alphas[i], cats[i])])
-        ctx.n, ctx.dT, ctx.dB = n, dT, dB
-        ctx.has_bu = [per[i][2] is not None for i in range(n)]
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        allf, seg, *rest = ctx.saved_tensors
-        return _readout_head_backward(allf, seg, [rest[9 * i:9 * i + 9] for i in range(ctx.n)], ctx.dT, ctx.dB, ctx.has_bu, gs)
-
-
-def _readout_head_backward(allf, seg, per, dT, dB, has_bu, gs):
-    """the grouped backward of the read-out head (ReadoutHead, ReadoutHeadFused): per[i] = (v, Wu, Wv, we, Wsr, U, Vq, alpha,
-    cat) of live order i, gs[i] = gradient of s_i -> (d allf, None, None, None, per order: d v, d Wu, d bu, d Wv, d we, d Wsr)"""
-    n = len(per)
-    NT, D = allf.shape
-    dev = allf.device
-    B = per[0][0].shape[0]
-    h = per[0][1].shape[0]
-    gcats, gWsrs, probs = [], [], []
-    for i, (v, Wu, Wv, we, Wsr, U, Vq, alpha, cat) in enumerate(per):
-        g = _rows(gs[i])
-        gcat = torch.empty_like(cat)
-        gWsr = torch.empty_like(Wsr)
-        probs.append(('nn', g, Wsr, gcat, None, dB, 0.0))
-        probs.append(('tn', g, cat, gWsr, None, dB, 0.0))
-        gcats.append(gcat)
-        gWsrs.append(gWsr)
-    gemm_f32_group(probs, split3=PRECISION['matmul'] == 'bf16')
-    g_allf = None
-    probs, grads, extra = [], [], []
-    for i, (v, Wu, Wv, we, Wsr, U, Vq, alpha, cat) in enumerate(per):
-        dv = v.shape[1]
-        gsrg = gcats[i][:, dv:]
-        dX = torch.empty(NT, D, device=dev, dtype=torch.float32)      # rows behind the live nodes zeroed in-kernel
-        dU = torch.empty(NT, h, device=dev, dtype=torch.float32)
-        dVq = torch.empty(B, h, device=dev, dtype=torch.float32)
-        dwp = torch.empty(B, h, device=dev, dtype=torch.float32)
-        lib.srec_seg_attn_bwd(ptr(gsrg), _ld(gsrg), ptr(allf), _ld(allf), ptr(alpha), ptr(U), h, ptr(Vq), h, ptr(we),
-                              ptr(seg), B, ptr(dB), h, D, NT, ptr(dX), D, ptr(dU), h, ptr(dVq), h, ptr(dwp), h, stream())
-        gWu, gWv = torch.empty_like(Wu), torch.empty_like(Wv)
-        gv = gcats[i][:, :dv]                                         # d v: the concat half, + dVq Wv in place
-        probs.append(('nn', dU, Wu, dX, None, dT, 1.0))               # d allf (this order) = read-out term + dU Wu
-        probs.append(('tn', dU, allf, gWu, None, dT, 0.0))
-        probs.append(('nn', dVq, Wv, gv, None, dB, 1.0))
-        probs.append(('tn', dVq, v, gWv, None, dB, 0.0))
-        # column sums (d bu = sum_n dU, d we = sum_b dwp) as products with a block of ones, inside the same launch:
-        # as col_sum calls they were two kernel nodes each
-        ones = _ones4(max(NT, B), dev)
-        sums = torch.empty(8, h, device=dev, dtype=torch.float32)
-        gbu = None
-        if has_bu[i]:
-            probs.append(('tn', ones[:NT], dU, sums[:4], None, dT, 0.0))
-            gbu = sums[0]
-        probs.append(('tn', ones[:B], dwp, sums[4:], None, dB, 0.0))
-        grads.append((gv, gWu, gbu, gWv, sums[4:5], gWsrs[i]))
-        extra.append(dX)
-    per_launch = 12 if len(probs) > 16 else 16          # whole orders per launch (6 problems each)
-    for c in range(0, len(probs), per_launch):
-        gemm_f32_group(probs[c:c + per_launch], split3=PRECISION['matmul'] == 'bf16')
-    g_allf = extra[0]
-    for dX in extra[1:]:
-        g_allf = g_allf + dX
-    return (g_allf, None, None, None) + tuple(t for gr in grads for t in gr)
-
-
-# ---- fused read-out head (csrc/headf.hip) ----------------------------------------------------------------------------------
-_HEAD_WF_CACHE = {}    # (data_ptr, shape, trans) -> hi / lo fragment-major bf16 copy of this step (dropped by weights_changed)
-
-
-def _head_wfrag_args(ws, trans):
-    """output buffers + the HOST argument arrays of srec_head_wfrag for <= SREC_HEAD_MAXW weights (kept alive by the caller across the call)"""
-    m = len(ws)
-    assert 0 < m <= HEAD_MAXW
-    for w in ws:
-        assert w.is_contiguous() and w.dtype == torch.float32
-    bufs = [torch.empty(2 * w.numel(), device=w.device, dtype=torch.bfloat16) for w in ws]
-    ints = _ct.c_int * m
-    return bufs, (ptr_array(ws), ptr_array(bufs), ints(*[w.shape[0] for w in ws]),
-                  ints(*[w.shape[1] for w in ws]), ints(*[int(t) for t in trans]))
-
-
-def head_wfrag(ws, trans):
-    """hi / lo fragment-major bf16 operand copies of fp32 weights (W_i or W_i^T), computed once per optimizer step, all
-    missing ones in ONE launch (srec_head_wfrag) - normally none: the step's prologue launch made them (step_prologue)"""
-    out, todo = [None] * len(ws), []
-    for i, (w, t) in enumerate(zip(ws, trans)):
-        c = _HEAD_WF_CACHE.get((w.data_ptr(), tuple(w.shape), int(t)))
-        if c is None:
-            todo.append(i)
-        else:
-            out[i] = c
-    for c0 in range(0, len(todo), HEAD_MAXW):
-        ch = todo[c0:c0 + HEAD_MAXW]
-        bufs, args = _head_wfrag_args([ws[i] for i in ch], [trans[i] for i in ch])
-        lib.srec_head_wfrag(len(ch), *[_ct.addressof(a) for a in args], stream())
-        for i, b in zip(ch, bufs):
-            out[i] = _HEAD_WF_CACHE[(ws[i].data_ptr(), tuple(ws[i].shape), int(trans[i]))] = b
-    return out
-
-
-class ReadoutHeadFused(torch.autograd.Function):
-    """ReadoutHead + the normalisation of its outputs (msgifsr.py:124-155, :269-273) with the FORWARD as one launch: a
-    workgroup owns 8 sessions and runs Vq, U, the soft-max read-out, fc_sr and F.normalize on them, every product as a
-    3-term hi / lo bf16 split on the matrix pipe (csrc/headf.hip; results to ~2^-16 of the exact-fp32 grouped head).
-    Returns the NORMALISED session vectors; `ws` (CEWorkspace, optional) receives the bf16 operand copy of head 0.
-    Backward: the normalisation backward + the grouped launches of ReadoutHead."""
-
-    @staticmethod
-    def forward(ctx, allf, seg, dT, dB, ws, eps_mode, *flat):
-        n = len(flat) // 6
-        allf = _rows(allf)
-        NT, D = allf.shape
-        dev = allf.device
-        per = [(flat[6 * i], _rows(flat[6 * i + 1]), flat[6 * i + 2], _rows(flat[6 * i + 3]),
-                flat[6 * i + 4].reshape(-1).contiguous(), _rows(flat[6 * i + 5])) for i in range(n)]
-        B = per[0][0].shape[0]
-        # fragment-major hi / lo copies of fc_u, fc_v, fc_sr - and of fc_sr^T for the backward - in ONE launch per step
-        need_bwd = any(ctx.needs_input_grad)
-        wf = head_wfrag([w for po in per for w in (po[1], po[3], po[5])] + ([po[5] for po in per] if need_bwd else []),
-                        [0] * (3 * n) + ([1] * n if need_bwd else []))
-        ctx.wft = wf[3 * n:] if need_bwd else None
-        q = HeadDesc()
-        q.nh, q.d, q.B, q.NT, q.ld_x, q.eps_mode, q.eps = n, D, B, NT, _ld(allf), int(eps_mode), 1e-12
-        q.X, q.seg, q.dynB = ptr(allf), ptr(seg), ptr(dB)
-        sr16 = getattr(ws, 'sr16', None) if n == 1 else None
-        if sr16 is not None and not (B <= sr16.shape[0] and D <= sr16.shape[1]):
-            sr16 = None
-        q.ld16 = sr16.shape[1] if sr16 is not None else 0
-        keep, ys = [], []
-        for i, (v, Wu, bu, Wv, we, Wsr) in enumerate(per):
-            cat = v.as_strided((B, 2 * D), (2 * D, 1))             # v is the left half of a private [B, 2 D] buffer (checked)
-            alpha = torch.empty(NT, device=dev, dtype=torch.float32)
-            U = torch.empty(NT, D, device=dev, dtype=torch.float32)
-            Vq = torch.empty(B, D, device=dev, dtype=torch.float32)
-            y = torch.empty(B, D, device=dev, dtype=torch.float32)
-            inv = torch.empty(B, device=dev, dtype=torch.float32)
-            q.cat[i], q.Wu_f[i], q.Wv_f[i], q.Wsr_f[i] = ptr(cat), ptr(wf[3 * i]), ptr(wf[3 * i + 1]), ptr(wf[3 * i + 2])
-            q.bu[i], q.we[i], q.alpha[i], q.U[i], q.Vq[i] = ptr(bu), ptr(we), ptr(alpha), ptr(U), ptr(Vq)
-            q.y[i], q.inv[i] = ptr(y), ptr(inv)
-            q.y16[i] = ptr(sr16) if (sr16 is not None and i == 0) else None
-            keep += [v, Wu, Wv, we, Wsr, U, Vq, alpha, cat, y, inv]
-            ys.append(y)
-        lib.srec_head_fwd(_ct.addressof(q), stream())
-        if sr16 is not None:
-            sr16_written(ws, ys[0], B, D)
-        ctx.save_for_backward(allf, seg, *keep)
-        ctx.n, ctx.dT, ctx.dB = n, dT, dB
-        ctx.has_bu = [po[2] is not None for po in per]
-        ctx.defer = defer_scope()
-        ctx.wparams = [flat[6 * i + j] for i in range(n) for j in (1, 2, 3, 4, 5) if flat[6 * i + j] is not None]
-        return tuple(ys)
-
-    @staticmethod
-    def backward(ctx, *gys):
-        """one launch for everything per session (normalise-backward, d cat = g_s Wsr, the attention read-out backward:
-        srec_head_bwd), then the batch-wide products as ONE grouped exact-fp32 launch + its split-K sum:
-        d allf += dU Wu, d v += dVq Wv, d Wu, d Wv, d Wsr and the two column sums (d bu, d we)"""
-        allf, seg, *rest = ctx.saved_tensors
-        n, dT, dB = ctx.n, ctx.dT, ctx.dB
-        NT, D = allf.shape
-        dev = allf.device
-        per = [rest[11 * i:11 * i + 11] for i in range(n)]
-        B = per[0][0].shape[0]
-        wft = ctx.wft if ctx.wft is not None else head_wfrag([po[4] for po in per], [1] * n)   # fc_sr^T [2 D, D], fragment-major
-        q = HeadBwdDesc()
-        gy0 = _rows(gys[0])
-        q.nh, q.d, q.B, q.NT, q.ld_x, q.ld_gy = n, D, B, NT, _ld(allf), _ld(gy0)
-        q.X, q.seg, q.dynB = ptr(allf), ptr(seg), ptr(dB)
-        outs = []
-        for i, (v, Wu, Wv, we, Wsr, U, Vq, alpha, cat, y, inv) in enumerate(per):
-            gy = _rows(gys[i])
-            if _ld(gy) != q.ld_gy:
-                gy = gy.contiguous() if q.ld_gy == D else gy0.new_empty(B, q.ld_gy)[:, :D].copy_(gy)
-            gs, gcat = torch.empty(B, D, device=dev, dtype=torch.float32), torch.empty(B, 2 * D, device=dev, dtype=torch.float32)
-            dX, dU = torch.empty(NT, D, device=dev, dtype=torch.float32), torch.empty(NT, D, device=dev, dtype=torch.float32)
-            dVq, dwp = torch.empty(B, D, device=dev, dtype=torch.float32), torch.empty(B, D, device=dev, dtype=torch.float32)
-            q.gy[i], q.y[i], q.inv[i], q.WsrT_f[i], q.alpha[i] = ptr(gy), ptr(y), ptr(inv), ptr(wft[i]), ptr(alpha)
-            q.U[i], q.Vq[i], q.we[i] = ptr(U), ptr(Vq), ptr(we)
-            q.gs[i], q.gcat[i], q.dX[i], q.dU[i], q.dVq[i], q.dwp[i] = ptr(gs), ptr(gcat), ptr(dX), ptr(dU), ptr(dVq), ptr(dwp)
-            outs.append((gy, gs, gcat, dX, dU, dVq, dwp))
-        lib.srec_head_bwd(_ct.addressof(q), stream())
-        probs, grads, blocks = [], [], []
-        for i, (v, Wu, Wv, we, Wsr, U, Vq, alpha, cat, y, inv) in enumerate(per):
-            gy, gs, gcat, dX, dU, dVq, dwp = outs[i]
-            gWu, gWv, gWsr = grad_buf(Wu), grad_buf(Wv), grad_buf(Wsr)       # (bucket slots when the table is row-sharded)
-            gv = gcat[:, :D]                                              # d v: the concat half, + dVq Wv in place
-            probs.append(('nn', dU, Wu, dX, None, dT, 1.0))               # d allf (this order) = read-out term + dU Wu
-            probs.append(('tn', dU, allf, gWu, None, dT, 0.0))
-            probs.append(('nn', dVq, Wv, gv, None, dB, 1.0))
-            probs.append(('tn', dVq, v, gWv, None, dB, 0.0))
-            probs.append(('tn', gs, cat, gWsr, None, dB, 0.0))
-            # column sums as products with a block of ones inside the same launch: d bu = sum_n dU = sum_b dVq, d we = sum_b dwp
-            ones = _ones4(B, dev)
-            sums = torch.empty(8, D, device=dev, dtype=torch.float32)
-            s_bu, s_we = sums[:4], sums[4:]
-            gbu = None
-            if ctx.has_bu[i]:
-                probs.append(('tn', ones[:B], dVq, s_bu, None, dB, 0.0))
-                gbu = sums[0]
-                blocks.append(s_bu)
-            probs.append(('tn', ones[:B], dwp, s_we, None, dB, 0.0))
-            blocks.append(s_we)
-            grads.append((gv, gWu, gbu, gWv, sums[4:5], gWsr))
-        per_launch = GEMM32_MAXP if len(probs) <= GEMM32_MAXP else GEMM32_MAXP // 7 * 7      # whole orders per launch (7 problems each)
-        later = ([t for gr in grads for t in (gr[1], gr[3], gr[5])] + blocks) if can_defer(ctx.defer, ctx.wparams) else None
-        for c in range(0, len(probs), per_launch):
-            gemm_f32_group(probs[c:c + per_launch], split3=True,       # (the forward's products are 3-term splits too)
-                           defer=later)
-        g_allf = outs[0][3]
-        for o in outs[1:]:
-            g_allf = g_allf + o[3]
-        return (g_allf, None, None, None, None, None) + tuple(t for gr in grads for t in gr)
-
-
-HEAD_FUSED_MAX_B = 8192      # session capacity of the fused read-out head kernels (csrc/headf.hip: srec_head_fwd / srec_head_bwd)
-
-
-def readout_head_fused_ok(allf, per_order):
-    """the fused forward applies: bf16 mode, d = hidden = output in (128, 256), <= 4 heads, contiguous weights, every query
-    tensor the tagged left half of a private [B, 2 d] buffer (norm_permute_pick / permute_and_pick)"""
-    if not (allf.is_cuda and PRECISION['matmul'] == 'bf16' and 1 <= len(per_order) <= HEAD_MAXH and FUSED_HEAD):
-        return False
-    D = allf.shape[1]
-    if D not in (128, 256) or allf.stride(1) != 1 or allf.stride(0) % 4:
-        return False
-    B = per_order[0][0].shape[0]
-    if B > HEAD_FUSED_MAX_B:              # srec_head_fwd / _bwd keep a copy of seg[] in LDS: larger batches take the grouped launches
-        return False
-    for v, Wu, bu, Wv, we, Wsr in per_order:
-        if not (getattr(v, '_srec_cat_left', False) and tuple(v.shape) == (B, D) and v.stride(0) == 2 * D and v.stride(1) == 1):
-            return False
-        if tuple(Wu.shape) != (D, D) or tuple(Wv.shape) != (D, D) or tuple(Wsr.shape) != (D, 2 * D) or we.numel() != D:
-            return False
-        if not (Wu.is_contiguous() and Wv.is_contiguous() and Wsr.is_contiguous()):
-            return False
-    return B > 1
-
-
-def readout_head_fused(allf, seg, dT, dB, per_order, ws=None, eps_mode=0):
-    """-> tuple of NORMALISED session vectors y_i [B, d] (ReadoutHeadFused)"""
-    flat = [t for po in per_order for t in po]
-    return ReadoutHeadFused.apply(allf, seg, dT, dB, ws, eps_mode, *flat)
-
-
-def readout_head(allf, seg, dT, dB, per_order):
-    """per_order: [(v_i, Wu_i, bu_i, Wv_i, we_i, Wsr_i)] -> tuple of s_i [B, d] (before the optional normalisation): the grouped
-    exact-fp32 launches (ReadoutHead).  bf16 mode at d = 128 / 256 takes readout_head_fused instead."""
-    flat = [t for po in per_order for t in po]
-    return ReadoutHead.apply(allf, seg, dT, dB, *flat)
 
 
 class SegMeanAdd(torch.autograd.Function):
@@ -1933,7 +1569,7 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
         q.n_gru, q.gru_d = len(gru), gru[0].shape[1]
         q.gru_W, q.gru_fwd, q.gru_bwd = (_ct.addressof(a) for a in args)
         keep.append(args)
-    head = [(w, int(t)) for w, t in head if (w.data_ptr(), tuple(w.shape), int(t)) not in _HEAD_WF_CACHE][:HEAD_MAXW]
+    head = wfrag_missing(head)
     if head:
         hb, args = _head_wfrag_args([w for w, _ in head], [t for _, t in head])
         q.n_head = len(head)
@@ -1955,7 +1591,7 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
     for w, f, b_ in zip(gru, of if gru else (), ob if gru else ()):
         _wprep_put('gru', w, (f, b_))
     for (w, t), b_ in zip(head, hb if head else ()):
-        _HEAD_WF_CACHE[(w.data_ptr(), tuple(w.shape), t)] = b_
+        wfrag_put(w, t, b_)
     if fold is not None:
         plan.put_fold(small, lay)
 
@@ -1974,3 +1610,7 @@ from .score import (  # noqa: E402,F401  (full-catalog scoring: score.py imports
     BiasArgs, CEWorkspace, MixtureArgs, ScoreCE, ScoreLogProb, ScoreStats, TableBF16, _bf16_dim_ok, _byte_ws, _ce_bwd, _ce_fwd, _logp_cols,
     _bias_args, _mixture_args, _pad_rows, _prepare_sr, catalog_bias, diversify, diversify_scalars, finish_table_grad, score_ce, score_items, score_logp, score_norm, score_rank,
     sample_noise, sample_scalars, score_sample, score_select, score_stats, score_topk, sr16_claim, sr16_written, use_bf16_scoring)
+from .head import (  # noqa: E402,F401  (the attention read-out head: head.py imports this module and score.py)
+    HEAD_FUSED_MAX_B, HeadOrder, ReadoutHead, ReadoutHeadFused, SegAttn, _head_wfrag_args, head_bwd_desc, head_fwd_desc, head_path,
+    head_wfrag, readout_head, readout_head_fused, readout_head_fused_ok, seg_attn, wfrag_missing, wfrag_put)
+from .head import _WF as _HEAD_WF  # noqa: E402  (the head's fragment copies of this step: weights_changed drops them)

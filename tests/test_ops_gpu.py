@@ -1492,9 +1492,10 @@ def test_gemm_f32_group_three_term_split(dev):
     assert rel(gWv, D(dVq[:500]).t() @ D(v[:500])) < 2e-5
 
 
-@pytest.mark.parametrize('n_orders', [1, 2])
+@pytest.mark.parametrize('n_orders', [1, 2, 3, 4])
 def test_readout_head_matches_unfused_ops(dev, n_orders):
-    """ops.readout_head (grouped launches) against the same head assembled from ops.linear / seg_attn / cat_cols"""
+    """ops.readout_head (grouped launches) against the same head assembled from ops.linear / seg_attn / cat_cols.  Every third
+    order has no fc_u bias; 3 and 4 orders: the backward's 17 / 23 batch-wide products leave in two launches"""
     ops = _ops()
     torch.manual_seed(11)
     B, d = 96, 64
@@ -1513,6 +1514,8 @@ def test_readout_head_matches_unfused_ops(dev, n_orders):
                                              torch.randn(d, device=dev) * 0.2, torch.randn(d, d, device=dev) * 0.2,
                                              torch.randn(1, d, device=dev) * 0.2, torch.randn(d, 2 * d, device=dev) * 0.2)]
     per = [params() for _ in range(n_orders)]
+    for po in per[2::3]:
+        po[2] = None
     wts = [torch.randn(B, d, device=dev) for _ in range(n_orders)]
 
     def run(fused):
@@ -1527,26 +1530,30 @@ def test_readout_head_matches_unfused_ops(dev, n_orders):
                 srg = ops.seg_attn(U, Vq, we, allf, seg_d, dB)
                 ss.append(ops.linear(ops.cat_cols(v, srg), Wsr, None, dB, exact=True))
         loss = sum((s * w).sum() for s, w in zip(ss, wts))
-        leaves = [allf] + [t for po in per for t in po]
+        leaves = [allf] + [t for po in per for t in po if t is not None]
         grads = torch.autograd.grad(loss, leaves)
         return [s.detach() for s in ss], grads
     s1, g1 = run(True)
     s0, g0 = run(False)
     for a, b in zip(s1, s0):
         close(a, b, what='s', atol=2e-5)
-    names = ['allf'] + ['%s%d' % (nm, i) for i in range(n_orders) for nm in ('v', 'Wu', 'bu', 'Wv', 'we', 'Wsr')]
+    names = ['allf'] + ['%s%d' % (nm, i) for i in range(n_orders) for nm, t in zip(('v', 'Wu', 'bu', 'Wv', 'we', 'Wsr'), per[i])
+                        if t is not None]
+    assert len(names) == len(g1) == len(g0)
     for nm, a, b in zip(names, g1, g0):
         close(a, b, what='grad ' + nm, rtol=2e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize('n_orders,B,d,maxlen', [(1, 512, 256, 15), (1, 509, 256, 40), (3, 40, 128, 15), (2, 21, 256, 70)])
+@pytest.mark.parametrize('n_orders,B,d,maxlen', [(1, 512, 256, 15), (1, 509, 256, 40), (3, 40, 128, 15), (2, 21, 256, 70),
+                                                 (4, 19, 128, 9)])
 def test_fused_readout_head_matches_the_exact_fp32_grouped_head(dev, n_orders, B, d, maxlen):
     """csrc/headf.hip (ops.ReadoutHeadFused: Vq, U, soft-max read-out, fc_sr, F.normalize of a group of 8 sessions per
     workgroup in ONE launch, every product a 3-term hi / lo bf16 split) against the exact-fp32 grouped head
     (ops.ReadoutHead) followed by ops.normalize, msgifsr.py:124-155 + :269-273: normalised session vectors, the bf16
     operand copy, the saved soft-max weights, and every gradient (the backward shares the grouped launches, fed with the
     fused forward's saved tensors).  Padded layouts: live sessions / rows below capacity, B not a multiple of the group
-    size, sessions longer than one 32-row chunk, sessions of a single node."""
+    size, sessions longer than one 32-row chunk, sessions of a single node.  Four heads (orders 1 and 3 without an fc_u bias):
+    SREC_HEAD_MAXW = 16 fragment copies in one launch, and the backward's 26 batch-wide products cut an order across two launches."""
     ops = _ops()
     torch.manual_seed(5)
     lens = torch.randint(1, maxlen, (B,))
@@ -1573,6 +1580,8 @@ def test_fused_readout_head_matches_the_exact_fp32_grouped_head(dev, n_orders, B
     par = [[((torch.rand(d, d, device=dev) * 2 - 1) * sc), ((torch.rand(d, device=dev) * 2 - 1) * sc),
             ((torch.rand(d, d, device=dev) * 2 - 1) * sc), ((torch.rand(1, d, device=dev) * 2 - 1) * sc),
             ((torch.rand(d, 2 * d, device=dev) * 2 - 1) * sc)] for _ in range(n_orders)]
+    if n_orders == 4:
+        par[1][1] = par[3][1] = None
     gws = [torch.randn(B, d, device=dev) for _ in range(n_orders)]
     for w in gws:
         w[live_B:] = 0
@@ -1591,7 +1600,7 @@ def test_fused_readout_head_matches_the_exact_fp32_grouped_head(dev, n_orders, B
             v = vleaf[:, :d]
             v._srec_cat_left = True
             vs.append(vleaf)
-            per.append([v] + [t.clone().requires_grad_() for t in par[i]])
+            per.append([v] + [t.clone().requires_grad_() if t is not None else None for t in par[i]])
         ws = WS()
         ops.set_precision('bf16' if fused else 'fp32')
         try:
@@ -1603,7 +1612,7 @@ def test_fused_readout_head_matches_the_exact_fp32_grouped_head(dev, n_orders, B
                 ss = ops.ReadoutHead.apply(allf, seg_d, dT, dB, *[t for po in per for t in po])
                 ys = [ops.normalize(s_, 0, dB) for s_ in ss]
             loss = sum((y * w).sum() for y, w in zip(ys, gws))
-            leaves = [allf] + [t for i in range(n_orders) for t in [vs[i]] + per[i][1:]]
+            leaves = [allf] + [t for i in range(n_orders) for t in [vs[i]] + per[i][1:] if t is not None]
             grads = torch.autograd.grad(loss, leaves)
         finally:
             ops.set_precision('fp32')
@@ -1625,7 +1634,9 @@ def test_fused_readout_head_matches_the_exact_fp32_grouped_head(dev, n_orders, B
     if n_orders == 1:
         assert ws1.sr_fresh == (y1[0].data_ptr(), B, d)
         assert torch.equal(ws1.sr16[:B].float(), y1[0].to(torch.bfloat16).float())      # the scoring operand = bf16(y)
-    names = ['allf'] + ['%s%d' % (nm, i) for i in range(n_orders) for nm in ('cat', 'Wu', 'bu', 'Wv', 'we', 'Wsr')]
+    names = ['allf'] + ['%s%d' % (nm, i) for i in range(n_orders) for nm, t in zip(('cat', 'Wu', 'bu', 'Wv', 'we', 'Wsr'), [0] + par[i])
+                        if t is not None]
+    assert len(names) == len(g1) == len(g0)
     for nm, a, b in zip(names, g1, g0):
         if nm.startswith('cat'):
             a, b = a[:live_B, :d], b[:live_B, :d]              # d v (the right half of the buffer is not an input)
