@@ -647,6 +647,94 @@ int srec_score_sample(const float* sr, int ld_sr, long comp_stride, const float*
 int srec_sample_uniform(unsigned long long seed, const int* session_keys, int n_b, const int* ids, int n_v,
                         unsigned* h_out, float* w_out);
 
+/* ---- serving: TRUNCATED sampling - a per-session score cutoff found without the (B, V) matrix (score_cutoff.hip), and a
+ * floor operand in the selection kernel (recommend.hip) ------------------------------------------------------------------
+ * Per session b.  The eligible rows and the biased served score s'[b,v] are exactly those of srec_score_select_biased; layouts,
+ * limits, listed_mode, bias / group and id_lo are the same.  m_b = the largest eligible s';  w_v = exp((s'_v - m_b) * inv_t)
+ * and W_b = sum of w_v over the eligible rows;  inv_t = 1 / T is the temperature the draw will use.
+ * Three criteria, each optional, each evaluated on the FULL eligible distribution (not one after the other):
+ *   top_k (integer >= 1, any size - not limited to SREC_SELECT_MAXK; 0 = absent): tau_k = the k-th largest eligible s',
+ *     counting multiplicity; with fewer than k eligible rows it is -INFINITY.
+ *   top_p (0 < p < 1; p >= 1 = absent): tau_p = the largest eligible score value t with  sum_{s' >= t} w >= p * W  - the last
+ *     value of the shortest descending prefix that reaches p.  Items tied with that value are all inside: the kept set is a
+ *     function of a VALUE alone, ids never break a tie at the boundary.
+ *   min_p (0 < q <= 1): tau_q = m_b - min_gap, in fp32.  The host computes min_gap = -T ln q in double and rounds it once
+ *     to fp32; it is a scalar like inv_temperature.  min_gap = +INFINITY = absent.
+ * Outputs: floor[b] fp32 = the largest of the criteria given, -INFINITY when none is given;  count[b] int32 = #{eligible,
+ * s' >= floor};  log_kept[b] fp32 = log(sum_{s' >= floor} w / W), always <= 0;  top[b] fp32 = m_b.
+ * A session with nothing eligible gives (-inf, 0, -inf, -inf).  A session whose eligible rows all score -inf gives floor =
+ * -inf, count = the number of eligible rows and log_kept = 0.  Never NaN.  An eligible row scoring -inf has weight 0 and is
+ * counted only under floor = -inf.  -0.0 is canonicalised (the comparisons are on s' + 0.0f).  NaN scores are the caller's
+ * error, as elsewhere.
+ * No (B, V)-sized tensor, no float atomics; the outputs are a pure function of the inputs, do not depend on the item-range
+ * split of a launch, and disjoint row shards combine to THE BITS of the single-device result.  The cutoff compares the same
+ * fp32 s' the select / sample kernels form (score_tile.h, SCORE_PASS_ITEM_SCORE), so the boundary item passes its own floor.
+ * How: s' + 0.0f maps to an order-preserving 32-bit key (sign bit flipped for s' >= 0, all bits for s' < 0), searched by
+ * radix, 8 bits per pass of the catalogue (SREC_CUTOFF_PASSES = 4 passes, numbered 0 .. 3: the key is then known to the bit).  Pass j builds,
+ * per session, a 256-bin histogram over digit j of the eligible pairs whose higher digits equal the session's prefix: COUNTS
+ * for top_k, MASS for top_p (the two searches keep separate prefixes).  Mass is fixed-point INTEGER, x = (u64)(w * 2^44),
+ * w in fp32 (expf), clamped to 1: integer sums are order-free, so per-range partials and shards add exactly (quantum 2^-44:
+ * the truncation loses at most V * 2^-44 < 1e-6 of W >= 1 for V <= 2^24).  A bin sum of more than 2^19 items would not fit
+ * 64 bits, so a workgroup never covers more, and outside the workgroup a sum travels as TWO int64 limbs (sum of x mod 2^32,
+ * sum of x >> 32; value = hi * 2^32 + lo, 128-bit arithmetic where they are read).  The pass-0 total is W.  The target of
+ * top_p: p is taken as P / 2^32, P = round(p * 2^32) held in [1, 2^32 - 1], and "mass >= p W" is the exact integer test
+ * mass * 2^32 >= P * W.  After the 4 passes one more pass (the TAIL: the same kernel, the bin is "s' + 0.0f >= floor")
+ * gives count, kept mass and W for the final floor - uniform over the criteria and their combination - and
+ * log_kept = (float) log((double) kept / (double) W) (0 where W = 0 and count > 0).
+ * Shards all-reduce integers between the passes, so the ABI is pass-granular:
+ *   hist  int64 [B][3][256]: counts, mass limb lo, mass limb hi of one pass - ZEROED by the pass entry points, then added to
+ *         with integer atomics (empty bins are skipped); SUM over shards.
+ *   state int64 [B][SREC_CUTOFF_STATE]: prefix of the top_k search, of the top_p search, count above, mass above (lo, hi),
+ *         W (lo, hi), flags (1: fewer than k eligible rows, 2: W = 0) - written by advance, the same on every shard.
+ *   top   fp32 [B]: m_b, from the K = 1 selection (srec_score_select_biased; MAX over shards) - needed ahead of pass 0.
+ * srec_score_cutoff_hist (pass 0 .. 3) reads top and state (pass 0: state is not read); srec_score_cutoff_advance (pass
+ * 0 .. 3, no table access, one workgroup per session) scans the summed bins from the top, fixes the next digit of either
+ * search and, at pass 3, writes floor (and top[b] + 0.0f back into top); pass = SREC_CUTOFF_PASSES does that last step alone
+ * (neither top_k nor top_p given: no histogram is needed).  srec_score_cutoff_tail fills hist bins 0 (below) and 1 (kept);
+ * srec_score_cutoff_finish turns the summed tail bins into count and log_kept.  No host synchronisation anywhere.
+ * srec_score_cutoff chains everything on one device: ws = srec_score_cutoff_ws() bytes (hist, state and the K = 1 selection's
+ * scratch).
+ * All return nonzero and do not launch for the reasons of srec_score_select_biased, for inv_temperature not positive and
+ * finite, top_k < 0, top_p <= 0 or NaN, min_gap < 0 or NaN, pass out of range, a NULL top / state / hist / floor / output. */
+#define SREC_CUTOFF_PASSES 4
+#define SREC_CUTOFF_STATE 8
+int srec_score_cutoff_ws(int B, int V, int d, int C, int L, long* bytes);
+int srec_score_cutoff_hist(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                           const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                           long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
+                           const int* group, int G, float inv_temperature, int top_k, float top_p, int pass,
+                           const float* top, const long long* state, long long* hist, void* stream);
+int srec_score_cutoff_advance(int B, int pass, int top_k, float top_p, float min_gap, const long long* hist,
+                              long long* state, float* top, float* floor, void* stream);
+int srec_score_cutoff_tail(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                           const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                           long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
+                           const int* group, int G, float inv_temperature, const float* top, const float* floor,
+                           long long* hist, void* stream);
+int srec_score_cutoff_finish(int B, const long long* hist, int* count, float* log_kept, void* stream);
+int srec_score_cutoff(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                      long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
+                      const int* group, int G, float inv_temperature, int top_k, float top_p, float min_gap,
+                      float* floor, int* count, float* log_kept, float* top, void* ws, void* stream);
+
+/* ---- serving: the floor in the selection and in the draw (recommend.hip, FLOOR instances) --------------------------------
+ * floor fp32 [B], nullable: a (session b, row v) pair is additionally INELIGIBLE when s'[b,v] < floor[b] - the test is on the
+ * biased served score, before temperature and noise.  With floor == NULL these ARE srec_score_select_biased and
+ * srec_score_sample, bit for bit (the same kernel instances).  A session whose kept set is smaller than K ends in
+ * (-INFINITY, -1) slots.  floor aligned to 4 bytes; everything else as in the two calls. */
+int srec_score_select_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                            const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                            long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                            const int* group, int G, const float* floor, float* out_val, int* out_idx, void* ws,
+                            void* stream);
+int srec_score_sample_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                            const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                            long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                            const int* group, int G, float inv_temperature, unsigned long long seed,
+                            const int* session_keys, const float* floor, float* out_key, int* out_idx, void* ws,
+                            void* stream);
+
 /* ---- serving: diversified top-N - greedy MMR re-rank of a pool, and intra-list diversity (diversify.hip) ------------------
  * Per session a pool of M slots; slot i has a row index row[b * M + i] into the row source X (fp32, n_rows rows of d columns,
  * leading dimension ld_x) and a value s[b * M + i].  A slot whose row index is < 0 or >= n_rows is UNFILLED: X is never read

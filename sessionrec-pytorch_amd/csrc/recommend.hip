@@ -44,6 +44,7 @@ struct SelArgs : PassArgs {
     float inv_t;                    // NOISE instances only: 1 / T, the seed and the session keys (NULL: the row index)
     unsigned long long seed;
     const int* qkeys;
+    const float* floor;             // FLOOR instances only: [B], a pair with s' < floor[b] is ineligible
 };
 
 __device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
@@ -99,12 +100,12 @@ __device__ __forceinline__ void merge_sorted(float* lv, int* li, int K, const fl
     __builtin_amdgcn_wave_barrier();
 }
 
-inline size_t part_lds(int C, int d, int K, int L, bool sr_lds, bool grouped = false, bool noisy = false) {
+inline size_t part_lds(int C, int d, int K, int L, bool sr_lds, bool grouped = false, bool noisy = false, bool floored = false) {
     return pass_lds(L, grouped) + (size_t)SB * 4 * 4 + (size_t)SB * K * 8 + (size_t)SB * CST * 4 + (noisy ? (size_t)SB * 4 : 0) +
-           (sr_lds ? tile_bytes(C, d) : 0);
+           (floored ? (size_t)SB * 4 : 0) + (sr_lds ? tile_bytes(C, d) : 0);
 }
 
-template <int C, bool SR_LDS, int BIAS, bool NOISE>
+template <int C, bool SR_LDS, int BIAS, bool NOISE, bool FLOOR>
 __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int d = a.d, K = a.K, L = a.L;
@@ -119,7 +120,8 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
     int* lst = reinterpret_cast<int*>(cand + SB * CST);
     unsigned long long* goff = reinterpret_cast<unsigned long long*>(lst + SB * L);
     unsigned* skey = reinterpret_cast<unsigned*>(goff + (BIAS == 2 ? SB : 0));   // [SB] hashed session keys (NOISE)
-    float* Ss = reinterpret_cast<float*>(skey + (NOISE ? SB : 0));  // [C][SB][LD] (SR_LDS); 16-byte aligned: all counts above are multiples of 4
+    float* flr = reinterpret_cast<float*>(skey + (NOISE ? SB : 0));  // [SB] the sessions' floors (FLOOR)
+    float* Ss = flr + (FLOOR ? SB : 0);                             // [C][SB][LD] (SR_LDS); 16-byte aligned: all counts above are multiples of 4
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
@@ -135,6 +137,9 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
             const int b = b0 + tid;
             skey[tid] = srec_sample_skey(a.seed, b < a.B ? (unsigned)(a.qkeys != nullptr ? a.qkeys[b] : b) : 0u);
         }
+    }
+    if constexpr (FLOOR) {
+        if (tid < SB) flr[tid] = b0 + tid < a.B ? a.floor[b0 + tid] : -INFINITY;
     }
     if (SR_LDS) stage_tiles<C>(Ss, a.sr, a.ld_sr, a.comp_stride, b0, a.B, d, tid);
     __syncthreads();
@@ -154,8 +159,10 @@ __global__ __launch_bounds__(256) void select_part_kernel(SelArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             SCORE_PASS_ITEM_SCORE(C, BIAS, it, acc, r, ps, wave, l31, half, sl, in, s, bias_ok)
+            [[maybe_unused]] bool kept = true;
+            if constexpr (FLOOR) kept = !(s < flr[sl]);             // on the served score, before temperature and noise
             if constexpr (NOISE) s = fmaf(s, a.inv_t, srec_sample_gumbel(srec_sample_h32(skey[sl] ^ gmix)));   // the sampled key
-            const bool hit = SCORE_PASS_ELIGIBLE(it, in, ps, b0 + sl < a.B, bias_ok) && better(s, it.v, lv[sl * K + K - 1], li[sl * K + K - 1]);
+            const bool hit = SCORE_PASS_ELIGIBLE(it, in, ps, b0 + sl < a.B, bias_ok) && (!FLOOR || kept) && better(s, it.v, lv[sl * K + K - 1], li[sl * K + K - 1]);
             const unsigned long long mk = __ballot(hit);
             if (hit) cand[sl * CST + wave * 32 + l31] = s;
             if (l31 == 0) surv[sl * 4 + wave] = half ? (unsigned)(mk >> 32) : (unsigned)mk;
@@ -230,9 +237,13 @@ __global__ __launch_bounds__(256) void select_merge_kernel(const float* __restri
 }
 
 template <int C, bool SR_LDS, int BIAS>
-struct SelectPart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, false>; };
+struct SelectPart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, false, false>; };
 template <int C, bool SR_LDS, int BIAS>
-struct SamplePart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, true>; };
+struct SamplePart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, true, false>; };
+template <int C, bool SR_LDS, int BIAS>
+struct SelectFloorPart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, false, true>; };
+template <int C, bool SR_LDS, int BIAS>
+struct SampleFloorPart { static constexpr auto kernel = select_part_kernel<C, SR_LDS, BIAS, true, true>; };
 
 inline int ranges(int B, int V) { return pick_ranges(B, V, 512, 4); }   // the lists and tiles leave room for one or two
                                                                         // workgroups per CU; the first chunk fills the list
@@ -247,29 +258,36 @@ extern "C" int srec_score_select_ws(int B, int V, int d, int C, int L, int K, lo
 
 namespace {
 
-// both entry points: NOISE = false is srec_score_select_biased as it always was (inv_t / seed / qkeys are not read)
+// all entry points: NOISE = false is srec_score_select_biased as it always was (inv_t / seed / qkeys are not read); floor ==
+// NULL launches the instances those two calls always launched
 template <bool NOISE>
 int select_launch(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs, const float* off_ex,
                   const float* off_in, const int* listed, int L, int listed_mode, long id_lo, int B, int V, int d, int C, int K,
                   const float* bias, long ld_bias, const int* group, int G, float inv_t, unsigned long long seed,
-                  const int* qkeys, float* out_val, int* out_idx, void* ws, void* stream) {
+                  const int* qkeys, const float* floor, float* out_val, int* out_idx, void* ws, void* stream) {
     if (B <= 0) return 0;
     SelArgs a{};
     if (pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias, ld_bias,
                   group, G, true) ||
-        K < 1 || K > MAXK || out_val == nullptr || out_idx == nullptr || ws == nullptr)
+        K < 1 || K > MAXK || out_val == nullptr || out_idx == nullptr || ws == nullptr || ((uintptr_t)floor & 3))
         return SREC_BAD_ARG;
     const int R = ranges(B, V);
     const dim3 grid(split_ranges(a, R), cdiv(B, SB));
     a.K = K;
     a.pv = (float*)ws;
     a.pi = (int*)(a.pv + (size_t)R * B * K);
-    a.inv_t = inv_t; a.seed = seed; a.qkeys = qkeys;
+    a.inv_t = inv_t; a.seed = seed; a.qkeys = qkeys; a.floor = floor;
     hipStream_t st = (hipStream_t)stream;
-    const auto lds = [&](int c, bool sr_lds, bool grouped) { return part_lds(c, d, K, a.L, sr_lds, grouped, NOISE); };
+    const bool floored = floor != nullptr;
+    const auto lds = [&](int c, bool sr_lds, bool grouped) { return part_lds(c, d, K, a.L, sr_lds, grouped, NOISE, floored); };
     if (int rc = switch_c(C, [&](auto c) {
-            if constexpr (NOISE) return launch_pass<SamplePart, true, c.value>(a, grid, lds, st);
-            else return launch_pass<SelectPart, true, c.value>(a, grid, lds, st);
+            if constexpr (NOISE) {
+                return floored ? launch_pass<SampleFloorPart, true, c.value>(a, grid, lds, st)
+                               : launch_pass<SamplePart, true, c.value>(a, grid, lds, st);
+            } else {
+                return floored ? launch_pass<SelectFloorPart, true, c.value>(a, grid, lds, st)
+                               : launch_pass<SelectPart, true, c.value>(a, grid, lds, st);
+            }
         }))
         return rc;
     hipLaunchKernelGGL(select_merge_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, a.pv, a.pi, (int)grid.x, B, K, id_lo, out_val,
@@ -285,7 +303,16 @@ extern "C" int srec_score_select_biased(const float* sr, int ld_sr, long comp_st
                                         long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
                                         const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream) {
     return select_launch<false>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
-                                bias, ld_bias, group, G, 1.f, 0ull, nullptr, out_val, out_idx, ws, stream);
+                                bias, ld_bias, group, G, 1.f, 0ull, nullptr, nullptr, out_val, out_idx, ws, stream);
+}
+
+extern "C" int srec_score_select_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                       const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                                       long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                                       const int* group, int G, const float* floor, float* out_val, int* out_idx, void* ws,
+                                       void* stream) {
+    return select_launch<false>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
+                                bias, ld_bias, group, G, 1.f, 0ull, nullptr, floor, out_val, out_idx, ws, stream);
 }
 
 // ws: as srec_score_select_ws (the per-range lists hold keys where that call's hold scores)
@@ -293,15 +320,26 @@ extern "C" int srec_score_sample_ws(int B, int V, int d, int C, int L, int K, lo
     return srec_score_select_ws(B, V, d, C, L, K, bytes);
 }
 
+extern "C" int srec_score_sample_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
+                                       const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
+                                       long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
+                                       const int* group, int G, float inv_temperature, unsigned long long seed,
+                                       const int* session_keys, const float* floor, float* out_key, int* out_idx, void* ws,
+                                       void* stream) {
+    if (B <= 0) return 0;
+    if (!(inv_temperature > 0.f) || !(inv_temperature <= 3.402823466e+38f) || ((uintptr_t)session_keys & 3)) return SREC_BAD_ARG;
+    return select_launch<true>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
+                               bias, ld_bias, group, G, inv_temperature, seed, session_keys, floor, out_key, out_idx, ws, stream);
+}
+
 extern "C" int srec_score_sample(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
                                  const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode, long id_lo,
                                  int B, int V, int d, int C, int K, const float* bias, long ld_bias, const int* group, int G,
                                  float inv_temperature, unsigned long long seed, const int* session_keys, float* out_key,
                                  int* out_idx, void* ws, void* stream) {
-    if (B <= 0) return 0;
-    if (!(inv_temperature > 0.f) || !(inv_temperature <= 3.402823466e+38f) || ((uintptr_t)session_keys & 3)) return SREC_BAD_ARG;
-    return select_launch<true>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
-                               bias, ld_bias, group, G, inv_temperature, seed, session_keys, out_key, out_idx, ws, stream);
+    return srec_score_sample_floor(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C,
+                                   K, bias, ld_bias, group, G, inv_temperature, seed, session_keys, nullptr, out_key, out_idx, ws,
+                                   stream);
 }
 
 // HOST: h [n_b, n_v] and w [n_b, n_v] of sample_noise.h for the sessions' keys (NULL: 0 .. n_b - 1) and the global ids

@@ -417,7 +417,8 @@ class HipLocal:
 
     def select(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, **bias):
         """this shard's k best rows (values, global ids) of ops.score_select: rows [id_lo, id_lo + n) of the catalog.
-        bias: `bias=` (this shard's columns) and `group=` of ops.score_select, only when there is a bias"""
+        bias: `bias=` (this shard's columns) and `group=` of ops.score_select, only when there is a bias, and `floor=`
+        ([B], the sessions' cutoff) only when there is one"""
         return self.ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
     def sample(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, temperature, seed, session_keys, **bias):
@@ -425,6 +426,13 @@ class HipLocal:
         session_keys: one integer per session (the noise is a function of the key, never of the row).  bias: as in select()"""
         return self.ops.score_sample(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, temperature=temperature,
                                      seed=seed, session_keys=session_keys, **bias)
+
+    def cutoff(self, srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, crit, reduce_max, reduce_sum, **bias):
+        """(floor, count, log_kept, top) of ops.score_cutoff over the WHOLE catalogue, this shard scoring rows [id_lo, id_lo + n)
+        (n = 0: it only joins the reduces): reduce_max / reduce_sum combine the shards' maxima and integer partials between
+        the passes.  crit: top_k / top_p / min_p / temperature.  bias: as in select()"""
+        return self.ops.score_cutoff(srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, reduce_max=reduce_max,
+                                     reduce_sum=reduce_sum, **crit, **bias)
 
     def score_items(self, srs, table, cs, items, off_ex, off_in, listed, drop_listed, id_lo, **bias):
         """this shard's share of ops.score_items: rows [id_lo, id_lo + n) of the catalog score, every other id gives 0.
@@ -850,7 +858,9 @@ class VocabParallel:
         bkw = self._bias_cols(bias, group, data_parallel)
         if data_parallel:
             srs, off_ex, off_in, listed = self._gather_sessions(srs, off_ex, off_in, listed)
-            if extra is not None:
+            if isinstance(extra, tuple):           # (several per-session tensors; None entries stay None)
+                extra = tuple(None if e is None else all_gather_cat(e.contiguous(), self.group) for e in extra)
+            elif extra is not None:
                 extra = all_gather_cat(extra.contiguous(), self.group)
         if neutral is None or self.n_live > 0:
             csl = None if cs is None else cs[:self.n_live]
@@ -890,15 +900,21 @@ class VocabParallel:
         return srs, off_ex, off_in, listed
 
     def select(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
-               bias=None, group=None):
+               bias=None, group=None, floor=None):
         """the k best items of every session over the sharded table (ops.score_select's contract; srs: list of C [B, d]
         session vectors, off_ex / off_in [C, B], listed [B, L] global ids): every rank selects among its own LIVE rows with
         its id_lo (padding rows are never scored), ONE all-gather carries the (value, id) pairs of all ranks, and the lists
         are merged by (value descending, id ascending) - the order of one device.  data_parallel as in topk().  bias ([V] or
-        [G, V] over GLOBAL ids, the same on every rank) / group ([B] of this rank's sessions): ops.score_select's."""
-        return self._serve(lambda tab, mix, _, **b: self.local.select(*tab, k, *mix, drop_listed, self.lo, **b),
-                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group,
+        [G, V] over GLOBAL ids, the same on every rank) / group ([B] of this rank's sessions): ops.score_select's.  floor ([B]
+        of this rank's sessions, what cutoff() returned): ops.score_select's; under data_parallel it travels with the sessions."""
+        return self._serve(lambda tab, mix, fl, **b: self.local.select(*tab, k, *mix, drop_listed, self.lo, **b, **self._floor_kw(fl)),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group, extra=floor,
                            neutral=self._no_lists(k), combine=self._merge_lists)
+
+    @staticmethod
+    def _floor_kw(floor):
+        """the keyword the local select / sample take for a floor - none at all without one, so the call is then what it was"""
+        return {} if floor is None else {'floor': floor}
 
     @staticmethod
     def _no_lists(k):
@@ -924,19 +940,35 @@ class VocabParallel:
         return val, idx
 
     def sample(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
-               bias=None, group=None, temperature=1.0, seed=0, session_keys=None):
+               bias=None, group=None, temperature=1.0, seed=0, session_keys=None, floor=None):
         """k distinct items per session DRAWN from softmax(score / temperature) over the eligible items of the sharded table
         (ops.score_sample's contract; the arguments of select()): every rank keeps the k best sampled keys among its own LIVE
         rows with its id_lo, ONE all-gather carries the (key, id) pairs and select()'s merge orders them.  The noise is a
         function of (seed, session key, GLOBAL id), so the result is the single-device call's, bit for bit.  session_keys:
         [B] integers of this rank's sessions; None = the row index - under data_parallel the GLOBAL row index (rank * B + b),
-        and given keys are all-gathered with the sessions."""
+        and given keys are all-gathered with the sessions.  floor: as in select() - the draw is inside the kept set of cutoff()."""
         if data_parallel and session_keys is not None:
             session_keys = session_keys.reshape(-1).to(torch.int32)        # (as they travel)
-        return self._serve(lambda tab, mix, keys, **b: self.local.sample(*tab, k, *mix, drop_listed, self.lo, temperature, seed,
-                                                                         keys, **b),
-                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group, extra=session_keys,
+        return self._serve(lambda tab, mix, kf, **b: self.local.sample(*tab, k, *mix, drop_listed, self.lo, temperature, seed,
+                                                                       kf[0], **b, **self._floor_kw(kf[1])),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group, extra=(session_keys, floor),
                            neutral=self._no_lists(k), combine=self._merge_lists)
+
+    def cutoff(self, srs, table, cs, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False, bias=None,
+               group=None, top_k=None, top_p=None, min_p=None, temperature=1.0):
+        """(floor fp32 [B], count int32 [B], log_kept fp32 [B], top fp32 [B]): the cutoff of truncated sampling over the eligible
+        items of the sharded table (ops.score_cutoff's contract; the arguments of select()).  Every rank runs the passes over
+        its own LIVE rows with its id_lo and its columns of the bias; between the passes the ranks all-reduce small tensors -
+        MAX over the [B] fp32 maxima once, SUM over the int64 [B, 3, 256] histogram after each of the up to 5 passes.  The
+        partials are integers, so the result is the single-device call's, bit for bit, on every rank.  A rank without live
+        rows launches no pass and joins every collective with neutral partials (there is no shortcut past the collectives).
+        data_parallel: the sessions are gathered ONCE, ahead of the first pass; every rank gets its own sessions' rows."""
+        crit = dict(top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+        rmax = lambda t: all_reduce_(t, dist.ReduceOp.MAX, self.group)
+        rsum = lambda t: all_reduce_sum(t, self.group)
+        # (neutral None: the entry runs on a rank without live rows too - on an empty table)
+        return self._serve(lambda tab, mix, _, **b: self.local.cutoff(*tab, *mix, drop_listed, self.lo, crit, rmax, rsum, **b),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group)
 
     def norm(self, srs, table, cs, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False, bias=None,
              group=None):

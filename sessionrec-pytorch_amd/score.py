@@ -274,6 +274,7 @@ _LISTED_TOO_MANY = {
     'score_items': 'score_items: %d listed items per session; csrc/score_items.hip takes at most 64',
     'score_norm': 'score_norm: %d listed items per session; csrc/score_norm.hip takes at most 64',
     'score_sample': 'score_sample: %d listed items per session; csrc/recommend.hip takes at most 64',
+    'score_cutoff': 'score_cutoff: %d listed items per session; csrc/score_cutoff.hip takes at most 64',
 }
 
 
@@ -419,7 +420,18 @@ def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id
     return rank, target
 
 
-def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None):
+def _floor_arg(who, floor, B, dev):
+    """floor as fp32 [B] on the device (None stays None: no floor)"""
+    if floor is None:
+        return None
+    f = torch.as_tensor(floor).detach()
+    if not f.is_floating_point() or f.numel() != B:
+        raise ValueError('%s: floor must hold %d floating numbers (one per session), got %s %s' % (who, B, f.dtype, tuple(f.shape)))
+    return f.to(device=dev, dtype=torch.float32).reshape(B).contiguous()
+
+
+def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None,
+                 floor=None):
     """(values fp32 [B,k] descending, item ids int32 [B,k]): the k best rows of `table` per session under the score of
     score_rank, s[b,v] = logsumexp_c(cs[v] <sr_c[b], E_v> + off[c,b]) - no (B, V) tensor, k <= 128 (csrc/recommend.hip).
     Argument conventions as score_rank: srs [B, d], [C, B, d] or a list of C [B, d] tensors, C <= 4; off_ex / off_in [C, B]
@@ -429,7 +441,9 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     bias: fp32 [V] or [G, V] aligned with the rows of `table` (group: [B] row ids in [0, G)), added AFTER the mixture -
     s + bias[group[b], v]; -inf = the item is not in the catalogue for this call and is never returned, the order and the
     values are those of the biased score (_bias_args; no NaN, no +inf, no group id out of range: not checked here).  Without a
-    bias the call and its result are what they were."""
+    bias the call and its result are what they were.
+    floor: fp32 [B] or None - a row whose biased score is below floor[b] is ineligible for session b (score_cutoff finds the
+    floor of a top-k / top-p / min-p truncation); None: the call is what it was, the same kernel instances."""
     k = int(k)
     if k < 1 or k > CONST['SREC_SELECT_MAXK']:
         raise ValueError('score_select: k = %d; the selection kernel of csrc/recommend.hip keeps between 1 and %d items per '
@@ -444,10 +458,14 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     n = _ct.c_long()
     lib.srec_score_select_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
     ws = _byte_ws('select', dev, n.value)
-    # (no bias: bias NULL, G 1 - what srec_score_select passes on, the same kernel instances)
-    lib.srec_score_select_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
-                                 ptr(a.off_in), ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k,
-                                 ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, ptr(val), ptr(idx), ptr(ws), stream())
+    floor = _floor_arg('score_select', floor, B, dev)
+    head = (ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in), ptr(a.listed), a.L,
+            _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G)
+    if floor is None:
+        # (no bias: bias NULL, G 1 - what srec_score_select passes on, the same kernel instances)
+        lib.srec_score_select_biased(*head, ptr(val), ptr(idx), ptr(ws), stream())
+    else:
+        lib.srec_score_select_floor(*head, ptr(floor), ptr(val), ptr(idx), ptr(ws), stream())
     return val, idx
 
 
@@ -543,7 +561,7 @@ def sample_noise(seed, session_keys, ids):
 
 
 def score_sample(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None,
-                 temperature=1.0, seed=0, session_keys=None):
+                 temperature=1.0, seed=0, session_keys=None, floor=None):
     """(keys fp32 [B,k] descending, item ids int32 [B,k] in draw order): k DISTINCT rows of `table` per session drawn without
     replacement (Plackett-Luce) from p(v) ~ exp(s'[b,v] / temperature) over the eligible rows, s' the biased score of
     score_select and its eligibility - no (B, V) tensor, k <= 128 (csrc/recommend.hip, the selection over the sampled key
@@ -552,7 +570,9 @@ def score_sample(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     session key, global item id) - sample_noise() restates it - so a call is reproducible, a session with the same key draws
     the same items in any batch, and row shards (id_lo) merge by (key, id) to the bits of one call over the whole table.  A
     session with fewer than k eligible rows ends in (-inf, -1) slots.  The keys are NOT log-probabilities: score the ids
-    (score_items) for those."""
+    (score_items) for those.
+    floor: fp32 [B] or None - the draw is among the rows with s' >= floor[b] only (tested on s', before temperature and noise:
+    truncated sampling, the floor of score_cutoff); None: the call is what it was, the same kernel instances."""
     k, inv_t, seed = sample_scalars('score_sample', k, temperature, seed)
     a = _mixture_args('score_sample', srs, table, off_ex, None if drop_listed else off_in, listed)
     bi = _bias_args('score_sample', bias, group, a.B, a.V)
@@ -567,9 +587,14 @@ def score_sample(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     n = _ct.c_long()
     lib.srec_score_sample_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
     ws = _byte_ws('sample', dev, n.value, _SAMPLE_WS)
-    lib.srec_score_sample(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                          ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias),
-                          bi.ld_bias, ptr(bi.group), bi.G, inv_t, seed, ptr(q), ptr(key), ptr(idx), ptr(ws), stream())
+    floor = _floor_arg('score_sample', floor, B, dev)
+    head = (ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in), ptr(a.listed), a.L,
+            _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, inv_t, seed,
+            ptr(q))
+    if floor is None:
+        lib.srec_score_sample(*head, ptr(key), ptr(idx), ptr(ws), stream())
+    else:
+        lib.srec_score_sample_floor(*head, ptr(floor), ptr(key), ptr(idx), ptr(ws), stream())
     return key, idx
 
 
@@ -640,6 +665,155 @@ def score_norm(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_liste
                         ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias,
                         ptr(bi.group), bi.G, ptr(out), ptr(ws), stream())
     return out
+
+
+_CUTOFF_WS = {}        # the cutoff of truncated sampling: kind 'cutoff' (and its own 'select' scratch for the K = 1 maximum)
+
+
+def cutoff_scalars(who, top_k, top_p, min_p, temperature):
+    """(top_k, top_p, min_gap, 1 / temperature) as the library takes them, or ValueError in the words of `who`.  top_k: None
+    or an integer in [1, 2^31) (-> 0 = absent); top_p: None or a number > 0, not NaN (>= 1 and None -> 1.0 = absent; a p that
+    rounds to 0 in fp32 is refused); min_p: None or a number q in (0, 1] (-> min_gap = -T ln q, computed in double and rounded
+    once to fp32; None -> inf = absent); temperature positive and finite, as sample_scalars.  No launch, no library call"""
+    try:
+        temperature = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError('%s: temperature must be a number, got %r' % (who, temperature)) from None
+    if not (0.0 < temperature < float('inf')) or not (1.0 / temperature < 3.4e38):
+        raise ValueError('%s: temperature = %r; it must be positive and finite' % (who, temperature))
+    k = 0
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k < 2 ** 31:
+            raise ValueError('%s: top_k = %r; it is an integer >= 1 (any size below 2^31), or None' % (who, top_k))
+        k = top_k
+    p = 1.0
+    if top_p is not None:
+        try:
+            p = float(top_p)
+        except (TypeError, ValueError):
+            raise ValueError('%s: top_p must be a number, got %r' % (who, top_p)) from None
+        if isinstance(top_p, bool) or not p > 0.0 or _ct.c_float(p).value <= 0.0:
+            raise ValueError('%s: top_p = %r; it is a probability mass in (0, 1) (>= 1 or None: no nucleus)' % (who, top_p))
+        p = min(_ct.c_float(p).value, 1.0)          # (as the library sees it: a p that rounds to 1 in fp32 is no criterion)
+    gap = float('inf')
+    if min_p is not None:
+        try:
+            q = float(min_p)
+        except (TypeError, ValueError):
+            raise ValueError('%s: min_p must be a number, got %r' % (who, min_p)) from None
+        if isinstance(min_p, bool) or not 0.0 < q <= 1.0:
+            raise ValueError('%s: min_p = %r; it is a fraction of the best item\'s probability in (0, 1], or None' % (who, min_p))
+        import math
+        gap = _ct.c_float(abs(-temperature * math.log(q))).value
+    return k, p, gap, 1.0 / temperature
+
+
+def score_cutoff(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None,
+                 top_k=None, top_p=None, min_p=None, temperature=1.0, reduce_max=None, reduce_sum=None):
+    """(floor fp32 [B], count int32 [B], log_kept fp32 [B], top fp32 [B]): the score cutoff of TRUNCATED sampling over the
+    eligible rows of `table` under the biased score s' of score_select, at the temperature the draw will use - no (B, V)
+    tensor, no sort, no cumulative sum (csrc/score_cutoff.hip; the contract is in include/srec.h).  With m the largest eligible
+    s', w_v = exp((s'_v - m) / temperature) and W their sum: top_k (any size) - the k-th largest eligible s' (-inf with fewer
+    than k eligible rows); top_p - the largest score value t whose items at or above it hold w >= p W (the nucleus; ties at the
+    boundary are all inside); min_p = q - m + temperature * ln q.  floor is the largest of those given (-inf with none); count
+    the eligible rows with s' >= floor; log_kept = log(their w / W) <= 0; top = m.  Nothing eligible: (-inf, 0, -inf, -inf).
+    Pass floor to score_select / score_sample (floor=) to select or draw inside the kept set.
+    Arguments as score_norm.  The search is exact: an order-preserving 32-bit key of s', 8 bits per pass over the table, integer
+    histograms (counts; fixed-point mass, quantum 2^-44), so the result is a pure function of the inputs - equal bits on
+    every call, for any launch split, and for row shards: reduce_max (on the fp32 [B] maxima) and reduce_sum (on every int64
+    partial between the passes) are the shards' all-reduces (dist.VocabParallel.cutoff); None = one device, one library call.
+    A shard without rows (an empty `table`) joins every reduce with neutral partials and launches no pass.
+    Measured at B 512, V 37 484, d 256 (profiles/score_cutoff_timing.md): C = 1 - 1.17 ms for top_k alone,
+    1.50 ms for top_p alone and 1.60 ms for both (a histogram pass costs 159 - 311 us beside 177 us for the log-mass pass of
+    score_norm) against 1.65 ms for score_logp + torch.sort + cumsum; C = 3 with a [4, V] bias and a 20-item dropped list -
+    2.99 ms for top_p against 2.92 ms materialised: there the materialised route is 2.5 % ahead, and 23 % with both criteria
+    (3.58 ms); at a shard of V 1 250 000 (C = 1) 37.8 ms against 70.1 ms.  min_p alone needs no search: 0.52 ms."""
+    c = _cutoff_operands('score_cutoff', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group, top_k, top_p,
+                         min_p, temperature)
+    if c.B == 0:
+        return c.out
+    if reduce_max is None and reduce_sum is None:
+        n = _ct.c_long()
+        lib.srec_score_cutoff_ws(c.B, c.V, c.d, c.C, c.L, _ct.addressof(n))
+        ws = _byte_ws('cutoff', c.dev, n.value, _CUTOFF_WS)
+        lib.srec_score_cutoff(*c.head, *c.tail, c.inv_t, c.k, c.p, c.gap, *[ptr(t) for t in c.out], ptr(ws), stream())
+        return c.out
+    same = lambda t: t
+    reduce = {'max': reduce_max or same, 'sum': reduce_sum or same}
+    steps = _cutoff_passes(c)
+    try:
+        kind, part = next(steps)
+        while True:
+            kind, part = steps.send(reduce[kind](part).contiguous())
+    except StopIteration as done:
+        return done.value
+
+
+def cutoff_passes(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None,
+                  top_k=None, top_p=None, min_p=None, temperature=1.0):
+    """score_cutoff pass by pass, as a generator - for callers that combine the partials of row shards themselves: it yields
+    ('max', fp32 [B]) once and then ('sum', int64 [B, 3, 256]) after every pass over the table, expects the combined tensor
+    back (generator.send; it may be the yielded tensor itself, reduced in place) and returns score_cutoff's tuple
+    (StopIteration.value).  score_cutoff(reduce_max=, reduce_sum=) is this loop with the two callables."""
+    return _cutoff_passes(_cutoff_operands('cutoff_passes', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group,
+                                           top_k, top_p, min_p, temperature))
+
+
+# what the library calls of one cutoff take: the checked scalars, the leading arguments every pass shares (head: sessions,
+# table, offsets, list, shape; tail: bias), the outputs (floor, count, log_kept, top), and `keep`, the owners of the memory
+# the pointers of head / tail name
+CutoffOperands = namedtuple('CutoffOperands', 'k p gap inv_t head tail out B V d C L dev keep')
+
+
+def _cutoff_operands(who, srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group, top_k, top_p, min_p, temperature):
+    k_, p_, gap, inv_t = cutoff_scalars(who, top_k, top_p, min_p, temperature)
+    a = _mixture_args('score_cutoff', srs, table, off_ex, None if drop_listed else off_in, listed)
+    bi = _bias_args(who, bias, group, a.B, a.V)
+    B, dev = a.B, a.srs.device
+    head = (ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in), ptr(a.listed), a.L,
+            _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C) if B > 0 else None
+    tail = (ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G) if B > 0 else None
+    out = (torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.int32),
+           torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.float32))
+    return CutoffOperands(k_, p_, gap, inv_t, head, tail, out, B, a.V, a.d, a.C, a.L, dev, (a, bi, cs))
+
+
+def _cutoff_passes(c):
+    floor, count, log_kept, top = c.out
+    B, dev = c.B, c.dev
+    if B == 0:
+        return c.out
+    rows = c.V > 0                       # (a shard without rows: neutral partials in EVERY reduce, no pass over a table)
+    if rows:
+        n = _ct.c_long()
+        lib.srec_score_select_ws(B, c.V, c.d, c.C, c.L, 1, _ct.addressof(n))
+        ws = _byte_ws('select', dev, n.value, _CUTOFF_WS)
+        ids = torch.empty(B, device=dev, dtype=torch.int32)
+        lib.srec_score_select_biased(*c.head, 1, *c.tail, ptr(top), ptr(ids), ptr(ws), stream())
+    else:
+        top.fill_(float('-inf'))
+    top = yield 'max', top
+    hist = torch.zeros(B, 3, 256, device=dev, dtype=torch.int64)
+    state = torch.zeros(B, CONST['SREC_CUTOFF_STATE'], device=dev, dtype=torch.int64)
+    passes = CONST['SREC_CUTOFF_PASSES']
+
+    def partial(launch, *args):
+        """this shard's histogram of one pass: the pass entry points zero `hist` themselves; a shard without rows zeroes it
+        here - what came back from the last reduce (possibly in place) is the sum over ALL shards, not a neutral partial"""
+        if rows:
+            launch(*c.head, *c.tail, c.inv_t, *args, ptr(hist), stream())
+        else:
+            hist.zero_()
+        return hist
+    if c.k > 0 or c.p < 1.0:
+        for j in range(passes):
+            hist = yield 'sum', partial(lib.srec_score_cutoff_hist, c.k, c.p, j, ptr(top), ptr(state))
+            lib.srec_score_cutoff_advance(B, j, c.k, c.p, c.gap, ptr(hist), ptr(state), ptr(top), ptr(floor), stream())
+    else:
+        lib.srec_score_cutoff_advance(B, passes, 0, 1.0, c.gap, None, None, ptr(top), ptr(floor), stream())
+    hist = yield 'sum', partial(lib.srec_score_cutoff_tail, ptr(top), ptr(floor))
+    lib.srec_score_cutoff_finish(B, ptr(hist), ptr(count), ptr(log_kept), stream())
+    return floor, count, log_kept, top
 
 
 def diversify_scalars(who, k, diversity, M=None):

@@ -227,7 +227,7 @@ class _ScoringMixin:
 
     # served call of dist.VocabParallel over a row-sharded table <-> (launcher of ops on one device, its own keywords)
     _ROUTES = {'target_rank': ('score_rank', {}), 'select': ('score_select', {}), 'sample': ('score_sample', {}),
-               'norm': ('score_norm', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
+               'norm': ('score_norm', {}), 'cutoff': ('score_cutoff', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
                'score_items': ('score_items', {'checked': True})}   # (model.score_items looked; sample() passes the kernel's ids)
 
     def _route(self, name):
@@ -439,13 +439,48 @@ class _ScoringMixin:
         fn, kw = self._route('select')
         return fn(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, **kw, **bias)
 
+    def _cutoff_of(self, srs, cs, off_ex, off_in, listed, drop_listed, crit, **bias):
+        """(floor, count, log_kept, top) of ops.score_cutoff; crit: top_k / top_p / min_p / temperature"""
+        fn, kw = self._route('cutoff')
+        return fn(srs, self._table(), cs, off_ex, off_in, listed, drop_listed, **crit, **kw, **bias)
+
+    @staticmethod
+    def _cutoff_args(who, top_k, top_p, min_p, temperature):
+        """the criteria as _cutoff_of takes them, checked (ops.cutoff_scalars); None when none of the three is given"""
+        if top_k is None and top_p is None and min_p is None:
+            return None
+        ops.cutoff_scalars(who, top_k, top_p, min_p, temperature)
+        return dict(top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+
+    def cutoff(self, *inputs, top_k=None, top_p=None, min_p=None, temperature=1.0, exclude_seen=False, item_bias=None,
+               item_group=None, renormalize=False):
+        """(floor fp32 [B], count int32 [B], log_kept fp32 [B]): where truncated sampling cuts every session's distribution -
+        what sample(top_k=, top_p=, min_p=, temperature=, same keywords) draws inside.  floor is in the units of recommend()'s
+        values (log-probability plus bias; renormalize=True: under the distribution restricted to the eligible catalogue): an
+        eligible item is kept when its value is >= floor.  top_k: keep the k most probable items (any k, not limited to 128;
+        ties with the k-th are kept); top_p: the smallest set of most probable items holding probability p AT THE GIVEN
+        TEMPERATURE, i.e. under p(v) ~ exp(value_v / temperature) (ties at the boundary are kept); min_p = q: the items at least
+        q times as probable as the best one, at that temperature.  Several criteria: the largest floor.  None: floor = -inf.
+        count: the number of kept items; log_kept: the log of the share of that distribution they hold (<= 0).  At
+        temperature=1, value - log_kept is an item's log-probability INSIDE the kept set.  A session with nothing eligible
+        gives (-inf, 0, -inf).  Fused passes over the table (csrc/score_cutoff.hip; ops.score_cutoff): no (B, V) matrix, no
+        sort, sharded table included.  Runs in eval mode under torch.no_grad(); the arguments are checked before anything of
+        the model runs."""
+        bias = self._item_bias('cutoff', item_bias, item_group)
+        ops.cutoff_scalars('cutoff', top_k, top_p, min_p, temperature)
+        crit = dict(top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+            return self._cutoff_of(srs, cs, off_ex, off_in, listed, exclude_seen, crit, **bias)[:3]
+
     def _sample_of(self, srs, cs, k, off_ex, off_in, listed, drop_listed, temperature, seed, session_keys, **bias):
+        """bias: `bias=` / `group=` as in _select_of, and `floor=` when the draw is truncated"""
         fn, kw = self._route('sample')
         return fn(srs, self._table(), cs, k, off_ex, off_in, listed, drop_listed, temperature=temperature, seed=seed,
                   session_keys=session_keys, **kw, **bias)
 
     def sample(self, *inputs, k=1, temperature=1.0, seed=0, session_keys=None, exclude_seen=False, item_bias=None,
-               item_group=None, renormalize=False):
+               item_group=None, renormalize=False, top_k=None, top_p=None, min_p=None):
         """(log_probs fp32 [B,k], item_ids int32 [B,k] in DRAW order): k distinct next items per session drawn without
         replacement from the model's distribution - p(v) ~ exp((log p_model(v) + bias_v) / temperature) over the items
         recommend() could return with the same keywords (not the session's own under exclude_seen, item_bias > -inf); k <= 128.
@@ -456,12 +491,21 @@ class _ScoringMixin:
         returns with the same keywords, bit for bit - forward()'s log-probabilities (plus bias; renormalize=True: under the
         distribution restricted to the eligible catalogue) at temperature 1, the number an off-policy log needs.  A session
         with fewer than k eligible items ends in (-inf, -1) slots.  Runs in eval mode under torch.no_grad(); item_bias /
-        item_group, k, temperature and seed are checked before anything of the model runs."""
+        item_group, k, temperature and seed are checked before anything of the model runs.
+        top_k / top_p / min_p: TRUNCATED sampling - the draw is among the items cutoff() keeps for the same keywords and
+        temperature (the k most probable, the nucleus of mass p, the items at least q times as probable as the best; several:
+        the smallest set).  The floor is found with the very offsets of the draw (csrc/score_cutoff.hip, no (B, V) matrix).  The
+        values stay what score_items returns - they are NOT renormalised over the kept set (cutoff()'s log_kept is that
+        normaliser) - and a session that keeps fewer than k items ends in (-inf, -1) slots.  With none of the three the call is
+        what it was, bit for bit."""
         bias = self._item_bias('sample', item_bias, item_group)
         k, _, seed = ops.sample_scalars('sample', k, temperature, seed)
+        crit = self._cutoff_args('sample', top_k, top_p, min_p, temperature)
         with _Serving(self):
             srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
-            _, ids = self._sample_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, temperature, seed, session_keys, **bias)
+            cut = {} if crit is None else dict(floor=self._cutoff_of(srs, cs, off_ex, off_in, listed, exclude_seen, crit, **bias)[0])
+            _, ids = self._sample_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, temperature, seed, session_keys, **cut,
+                                     **bias)
             return self._items_of(srs, cs, ids, off_ex, off_in, listed, exclude_seen, **bias), ids
 
     def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):

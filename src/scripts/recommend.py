@@ -15,6 +15,10 @@ fused pass, csrc/score_norm.hip).
 (model.sample: without replacement, in draw order; --temperature sharpens or flattens it, --seed fixes the draw).  The
 session key of the noise is the 0-based number of the session in the file (blank lines are not counted), so the output does
 not depend on --batch-size.  The printed values are still the items' log-probabilities, not the sampled keys.
+--sample-top-k K / --sample-top-p P / --sample-min-p Q truncate the distribution before the draw (model.sample(top_k=, top_p=,
+min_p=): among the K most probable items, inside the nucleus of mass P at the --temperature, among the items at least Q times
+as probable as the best one; several flags: the smallest set - csrc/score_cutoff.hip finds the cutoff without the score
+matrix).  A session that keeps fewer than --top items prints fewer pairs.  Only with --sample.
 --diversity THETA re-ranks the --pool M most probable items of every session (default min(128, max(4 top, top))) into a slate
 of --top items that trades probability for coverage (model.recommend_diverse: greedy MMR on the cosine of the item rows, one
 more kernel, csrc/diversify.hip); the output has the same format, in PICK order, with the items' own values.  Not together
@@ -80,6 +84,13 @@ def parser(model):
                         'the most probable ones')
     p.add_argument('--temperature', type=float, default=1.0, help='--sample: draw from softmax(log-probability / temperature)')
     p.add_argument('--seed', type=int, default=0, help='--sample: seed of the draw, in [0, 2^64)')
+    p.add_argument('--sample-top-k', type=int, default=None, metavar='K',
+                   help='--sample: draw among the K most probable eligible items (any K >= 1; ties with the K-th are kept)')
+    p.add_argument('--sample-top-p', type=float, default=None, metavar='P',
+                   help='--sample: draw inside the smallest set of most probable items holding probability P (0 < P < 1) at '
+                        'the --temperature')
+    p.add_argument('--sample-min-p', type=float, default=None, metavar='Q',
+                   help='--sample: never draw an item less than Q times as probable as the best one (0 < Q <= 1)')
     p.add_argument('--diversity', type=float, default=None, metavar='THETA',
                    help='re-rank the --pool most probable items into a diversified slate: each pick maximises value - THETA * '
                         '(largest cosine to the items picked so far); finite, >= 0; printed in pick order')
@@ -106,6 +117,15 @@ def parse(argv=None):
         p.error('--temperature must be positive and finite')
     if not 0 <= args.seed < 2 ** 64:
         p.error('--seed must be in [0, 2^64)')
+    for flag, val in (('--sample-top-k', args.sample_top_k), ('--sample-top-p', args.sample_top_p), ('--sample-min-p', args.sample_min_p)):
+        if val is not None and not args.sample:
+            p.error('%s truncates the distribution --sample draws from: it goes with --sample' % flag)
+    if args.sample_top_k is not None and not 1 <= args.sample_top_k < 2 ** 31:
+        p.error('--sample-top-k must be an integer >= 1')
+    if args.sample_top_p is not None and not 0.0 < args.sample_top_p < 1.0:
+        p.error('--sample-top-p must be a probability mass in (0, 1)')
+    if args.sample_min_p is not None and not 0.0 < args.sample_min_p <= 1.0:
+        p.error('--sample-min-p must be in (0, 1]')
     if args.diversity is not None:
         if args.sample:
             p.error('--diversity re-ranks the most probable items and --sample draws them: give one of the two')
@@ -154,7 +174,8 @@ def main(argv=None):
             if args.sample:
                 val, idx = model.sample(*[x.to(device) for x in inputs], k=args.top, temperature=args.temperature,
                                         seed=args.seed, session_keys=th.arange(b, b + n, dtype=th.int32),
-                                        exclude_seen=args.exclude_seen, item_bias=item_bias, renormalize=args.renormalize)
+                                        exclude_seen=args.exclude_seen, item_bias=item_bias, renormalize=args.renormalize,
+                                        top_k=args.sample_top_k, top_p=args.sample_top_p, min_p=args.sample_min_p)
             elif args.diversity is not None:
                 val, idx = model.recommend_diverse(*[x.to(device) for x in inputs], k=args.top, diversity=args.diversity,
                                                    pool=args.pool, exclude_seen=args.exclude_seen, item_bias=item_bias,
