@@ -517,114 +517,111 @@ int srec_score_topk_ws(int B, int V, int K, long* bytes);
 int srec_score_topk(const float* sr, int ld_sr, const float* E, int ld_e, const float* cs, int B, int V, int d, int K,
                     float* out_val, int* out_idx, void* ws, void* stream);
 
-/* ---- evaluation: rank of the label among ALL items, any cutoff, mixtures of soft-maxes too (rank.hip) ---------------
- * Replaces `logits = model(...); logits.topk(20)` of train.py:36-55 by the one integer every HR / MRR / NDCG @k is a function
- * of, also where the score mixes several soft-maxes (msgifsr.py:281-321: order fusion, repeat / explore gate):
- *   s[b,v] = logsumexp_{c<C}( cs[v] * <sr_c[b], E_v> + off[c,b] ),  off = off_in if v is in listed[b,:] else off_ex
- * sr: C blocks [B, d] (row stride ld_sr, block stride comp_stride); off_ex / off_in [C, B] (NULL = 0); listed [B, L] item
- * ids, -1 = empty slot, every id at most once per session (NULL / L = 0: none); labels[b] global id (< 0: rank -1);
- * id_lo: global id of local row 0 (row-sharded tables).  rank[b] = # local rows v with id_lo + v != labels[b] and
- * (s > target[b] or (s == target[b] and id_lo + v < labels[b])): ties towards the lower id, as srec_score_topk.
- * target [B]: written here (the label's score where this table owns the label, else 0) unless target_given.  Ranks and
- * targets of disjoint row shards add up; rank == NULL runs the target pass alone (a shard's share, ahead of that sum).
- * 1 <= C <= 4, d % 4 == 0, d <= 1024, L <= 64; fp32 MFMA, no (B, V) tensor. */
-int srec_score_rank_ws(int B, int V, int d, int C, int L, long* bytes);
-int srec_score_rank(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                    const float* off_ex, const float* off_in, const int* listed, int L, const int* labels, long id_lo,
-                    int B, int V, int d, int C, float* target, int target_given, int* rank, void* ws, void* stream);
-
-/* ---- serving: the K best items per session under the score of srec_score_rank (recommend.hip) --------------------------
- * The score is EXACTLY that of srec_score_rank, with the same layouts and limits (sr: C blocks [B, d]; off_ex / off_in [C, B],
- * NULL = 0; listed [B, L] global ids, -1 = empty slot; cs / off_* / listed nullable; 1 <= C <= 4, d % 4 == 0, d <= 1024,
- * L <= 64; fp32 MFMA, no (B, V) tensor):
- *   s[b,v] = logsumexp_{c<C}( cs[v] * <sr_c[b], E_v> + off[c,b] )      (C == 1: z + off, no exp / log)
- * listed_mode SREC_LISTED_SCORE: an item of listed[b,:] scores with off_in, as in srec_score_rank; SREC_LISTED_DROP: an item
- * of listed[b,:] is never returned for session b and off_in is ignored.
- * out_val [B, K] fp32 descending, out_idx [B, K] int32 global ids id_lo + row; ties towards the lower id (srec_score_topk,
- * srec_score_rank); a session with fewer than K eligible rows gets (-INFINITY, -1) in the remaining slots, so K > V is
- * allowed.  1 <= K <= SREC_SELECT_MAXK.  The output is a pure function of the inputs (no atomics; lists are ordered by
- * (value, id), never by arrival).  ws: srec_score_select_ws() bytes (per-range partial lists). */
-#define SREC_SELECT_MAXK 128
+/* ---- serving and evaluation: THE SERVED SCORE and its operands (score_pass.h) ----------------------------------------------
+ * Every entry point of the sections below scores the rows of one table under the same score, and takes its operands as ONE
+ * host struct, `const void* served` -> srec_served (the convention of srec_head_fwd(const void* desc, ...); the pointers
+ * inside are DEVICE pointers; the struct is read during the call only):
+ *   s[b,v]  = logsumexp_{c<C}( cs[v] * <sr_c[b], E_v> + off[c,b] ),  off = off_in if v is in listed[b,:] else off_ex
+ *             (C == 1: s = z + off, no exp / log)
+ *   s'[b,v] = s[b,v] + bias[group[b] * ld_bias + v]     the BIASED served score: one more operand, added AFTER the mixture
+ * (msgifsr.py:281-321: order fusion, repeat / explore gate, also where the score mixes several soft-maxes).
+ * Layouts: sr: C blocks [B, d] (row stride ld_sr, block stride comp_stride); E [V, d] (row stride ld_e); cs [V]; off_ex /
+ * off_in [C, B] (NULL = 0); listed [B, L] global item ids, -1 = empty slot, every id at most once per session (NULL / L = 0:
+ * none; L > 0 with listed == NULL is taken as L = 0); id_lo: global id of local row 0 (row-sharded tables).  cs / off_* /
+ * listed / bias / group nullable.  Limits: 1 <= C <= 4, d % 4 == 0, d <= 1024, 0 <= L <= 64, ids below 2^31 (id_lo + V <=
+ * INT_MAX; srec_score_rank, which never forms such an id, does not ask for it); fp32 MFMA, no (B, V) tensor.
+ * listed_mode SREC_LISTED_SCORE: an item of listed[b,:] scores with off_in; SREC_LISTED_DROP: an item of listed[b,:] is not
+ * eligible for session b and off_in is ignored.
+ * bias - a log-prior correction, a boost or a penalty; -INFINITY means "item v is not in the catalogue for this call".  fp32,
+ * indexed by the LOCAL row like cs (a row shard passes the pointer to its first column and the full row stride ld_bias), G
+ * rows; group [B] picks the row of every session, group == NULL means row 0 for every session and is legal only with G == 1
+ * (ld_bias is not read then).  bias == NULL (the plain call carries G = 1 and group = NULL beside it; a G > 1
+ * with its group is accepted and not read) IS the unbiased case of every entry point, bit for bit, the same kernel instances.  NaN or +INFINITY in bias and a group id outside [0, G) are the CALLER's
+ * error: nothing here looks for them, the kernels assume neither occurs (a group id is held inside [0, G), nothing else is
+ * promised for it).  An all-zero bias returns the ids and (by ==) the values of the unbiased call.
+ * ELIGIBLE: a (session b, row v) pair with v in [0, V) of this call (global id id_lo + v, a row shard), unless the item is
+ * listed under SREC_LISTED_DROP or its bias is -INFINITY (eligibility is tested by itself: an eligible item that merely scores
+ * -INFINITY is still eligible).
+ * Every entry point returns SREC_BAD_ARG for served == NULL, ahead of everything; then 0 and no launch for B <= 0, ahead of
+ * every other check of the descriptor.  Nonzero and no launch for: sr or E not aligned to 16 bytes, ld_sr / ld_e /
+ * comp_stride not multiples of 4, d % 4 != 0, V, d, C or L out of range, id_lo < 0, ids that do not fit (above), a listed_mode
+ * other than the two; G < 1; group == NULL with G > 1; bias != NULL with ld_bias < V and G > 1; bias or group not aligned to 4
+ * bytes.  The *_ws functions take the shape alone. */
 #define SREC_LISTED_SCORE 0
 #define SREC_LISTED_DROP 1
+typedef struct srec_served {
+    const float* sr; int ld_sr; long comp_stride;   /* the session vectors */
+    const float* E; int ld_e;                       /* the table */
+    const float* cs;                                /* the column scale */
+    const float* off_ex; const float* off_in;
+    const int* listed; int L; int listed_mode;
+    long id_lo;
+    int B, V, d, C;
+    const float* bias; long ld_bias;
+    const int* group; int G;
+} srec_served;
+
+/* ---- evaluation: rank of the label among ALL items, any cutoff, mixtures of soft-maxes too (rank.hip) ---------------
+ * Replaces `logits = model(...); logits.topk(20)` of train.py:36-55 by the one integer every HR / MRR / NDCG @k is a function
+ * of.  The score is s of the served score; the rank kernels know neither a bias nor SREC_LISTED_DROP: a descriptor with
+ * bias != NULL or listed_mode != SREC_LISTED_SCORE is refused (SREC_BAD_ARG), never ignored.
+ * labels[b] global id (< 0: rank -1).  rank[b] = # local rows v with id_lo + v != labels[b] and
+ * (s > target[b] or (s == target[b] and id_lo + v < labels[b])): ties towards the lower id, as srec_score_topk.
+ * target [B]: written here (the label's score where this table owns the label, else 0) unless target_given.  Ranks and
+ * targets of disjoint row shards add up; rank == NULL runs the target pass alone (a shard's share, ahead of that sum). */
+int srec_score_rank_ws(int B, int V, int d, int C, int L, long* bytes);
+int srec_score_rank(const void* served, const int* labels, float* target, int target_given, int* rank, void* ws,
+                    void* stream);
+
+/* ---- serving: the K best ELIGIBLE items per session under the biased served score (recommend.hip) -----------------------
+ * out_val [B, K] fp32 descending (the biased scores), out_idx [B, K] int32 global ids id_lo + row; ties towards the lower id
+ * (srec_score_topk, srec_score_rank); a session with fewer than K eligible rows gets (-INFINITY, -1) in the remaining slots,
+ * so K > V is allowed - an ineligible item (listed and dropped, bias -INFINITY) is NEVER returned, while an eligible item that
+ * merely scores -INFINITY still precedes an unfilled slot.  1 <= K <= SREC_SELECT_MAXK.  The output is a pure function of the
+ * inputs (no atomics; lists are ordered by (value descending, id ascending), never by arrival).
+ * floor fp32 [B], nullable (the floor of srec_score_cutoff): a (session b, row v) pair is additionally INELIGIBLE when
+ * s'[b,v] < floor[b] - the test is on the biased served score, before temperature and noise.  floor == NULL IS the call
+ * without a floor, bit for bit (the same kernel instances).  A session whose kept set is smaller than K ends in
+ * (-INFINITY, -1) slots.  floor aligned to 4 bytes.
+ * ws: srec_score_select_ws() bytes (per-range partial lists), with or without a bias or a floor.  Nonzero and no launch,
+ * beyond the descriptor's reasons: K out of range, a NULL output or ws, floor misaligned. */
+#define SREC_SELECT_MAXK 128
 int srec_score_select_ws(int B, int V, int d, int C, int L, int K, long* bytes);
-int srec_score_select(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                      long id_lo, int B, int V, int d, int C, int K,
-                      float* out_val, int* out_idx, void* ws, void* stream);
+int srec_score_select(const void* served, int K, const float* floor, float* out_val, int* out_idx, void* ws, void* stream);
 
 /* ---- serving: the score of GIVEN items per session (score_items.hip) ---------------------------------------------------
  * Replaces `logits = model(...); logits.gather(1, items)` (msgifsr.py:306-321 / srgnn.py:145-147) for re-ranking, allow-lists,
- * sampled-negative evaluation and lists longer than SREC_SELECT_MAXK: out[b,m] (fp32 [B, M]) is the score of srec_score_rank /
- * srec_score_select at the global id items[b * ld_items + m], with the same layouts and limits (1 <= C <= 4, d % 4 == 0,
- * d <= 1024, L <= 64; cs / off_* / listed nullable; C == 1: z + off, no exp / log).  ld_items == 0: one list of M ids shared
- * by all sessions.  Per slot: an id < 0 (padding) gives -INFINITY; a row outside [id_lo, id_lo + V) belongs to another shard
- * and gives 0.0f without any memory read, so the results of disjoint row ranges ADD UP (as the targets of srec_score_rank);
- * SREC_LISTED_SCORE: an item of listed[b,:] scores with off_in; SREC_LISTED_DROP: the shard that owns it gives -INFINITY
- * (off_in is ignored).  Duplicate ids in a list are legal and scored independently.  The output is a pure function of the
- * inputs: the summation order depends on (d, C) alone, no atomics, no workspace.  Nonzero and no launch for: pointers not
- * aligned (sr, E: 16 bytes), d % 4 != 0, C or L out of range, M < 1, id_lo < 0, 0 < ld_items < M. */
-int srec_score_items(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                     const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                     const int* items, long ld_items, int M, long id_lo,
-                     int B, int V, int d, int C, float* out, void* stream);
-
-/* ---- serving: per-item bias and catalogue filters in the two calls above (recommend.hip, score_items.hip) --------------------
- * One more operand, added AFTER the mixture:  s'[b,v] = s[b,v] + bias[group[b] * ld_bias + v]  - a log-prior correction, a
- * boost or a penalty; -INFINITY means "item v is not in the catalogue for this call".  bias: fp32, indexed by the LOCAL row
- * like cs (a row shard passes the pointer to its first column and the full row stride ld_bias), G rows; group [B] picks the
- * row of every session, group == NULL means row 0 for every session and is legal only with G == 1 (ld_bias is not read
- * then).  bias == NULL: srec_score_select / srec_score_items, which ARE that case of these entry points, bit for bit.  NaN or
- * +INFINITY in bias and a group id outside [0, G) are the CALLER's error: nothing here looks for them, the kernels assume
- * neither occurs (a group id is held inside [0, G), nothing else is promised for it).  All other arguments, layouts and
- * limits are those of the unbiased calls.
- * Select: an item whose bias is -INFINITY is ineligible for that session and is NEVER returned, also when fewer than K items
- * are eligible - the list then ends in (-INFINITY, -1) slots (eligibility is tested by itself: an eligible item that merely
- * scores -INFINITY still precedes an unfilled slot, as in srec_score_select).  Lists are ordered by (biased value descending,
- * id ascending), out_val holds the biased scores, and the output stays a pure function of the inputs (no atomics, no
- * arrival order).  ws: srec_score_select_ws() bytes, as without a bias.
- * Items: the shard that owns the id adds the bias, and -INFINITY stays -INFINITY; a padding slot (-1) gives -INFINITY; a
- * foreign id gives 0.0f without a read of the table OR of the bias, so disjoint shards still add up, to the bits of one
- * device; an item dropped by SREC_LISTED_DROP gives -INFINITY.
- * An all-zero bias returns the ids and (by ==) the values of the unbiased call.
- * Nonzero and no launch, beyond the unbiased calls' reasons: G < 1; group == NULL with G > 1; bias != NULL with ld_bias < V
- * and G > 1; bias or group not aligned to 4 bytes. */
-int srec_score_select_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                             const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                             long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                             const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream);
-int srec_score_items_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                            const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                            const int* items, long ld_items, int M, long id_lo,
-                            int B, int V, int d, int C, const float* bias, long ld_bias,
-                            const int* group, int G, float* out, void* stream);
+ * sampled-negative evaluation and lists longer than SREC_SELECT_MAXK: out[b,m] (fp32 [B, M]) is the biased served score at
+ * the global id items[b * ld_items + m].  ld_items == 0: one list of M ids shared by all sessions.  Per slot: an id < 0
+ * (padding) gives -INFINITY; a row outside [id_lo, id_lo + V) belongs to another shard and gives 0.0f without any read of the
+ * table OR of the bias, so the results of disjoint row ranges ADD UP (as the targets of srec_score_rank), to the bits of one
+ * device; the shard that owns the id adds the bias, and -INFINITY stays -INFINITY; SREC_LISTED_SCORE: an item of listed[b,:]
+ * scores with off_in; SREC_LISTED_DROP: the shard that owns it gives -INFINITY (off_in is ignored).  Duplicate ids in a list
+ * are legal and scored independently.  The output is a pure function of the inputs: the summation order depends on (d, C)
+ * alone, no atomics, no workspace.  Nonzero and no launch, beyond the descriptor's reasons: ld_sr < d or ld_e < d, M < 1,
+ * 0 < ld_items < M, items or out NULL or not aligned to 4 bytes. */
+int srec_score_items(const void* served, const int* items, long ld_items, int M, float* out, void* stream);
 
 /* ---- serving: the log-normaliser of the served score over the ELIGIBLE catalogue (score_norm.hip) -----------------------
- * out[b] (fp32 [B]) = logsumexp over the eligible rows v of s'[b,v], the biased score of srec_score_select_biased, with its
- * layouts, limits (1 <= C <= 4, d % 4 == 0, d <= 1024, L <= 64, ids below 2^31) and eligibility: rows [0, V) of this call
- * (global ids id_lo + row, a row shard); an item whose bias is -INFINITY does not contribute; SREC_LISTED_SCORE: an item of
- * listed[b,:] contributes with off_in; SREC_LISTED_DROP: it does not contribute and off_in is ignored.  bias == NULL: no
- * bias.  A session without an eligible row (or whose eligible rows all score -INFINITY) gives exactly -INFINITY, never NaN.
- * Subtracting out[b] from off_ex[:, b] and off_in[:, b] renormalises what srec_score_select* / srec_score_items* return:
+ * out[b] (fp32 [B]) = logsumexp over the eligible rows v of s'[b,v]: an item whose bias is -INFINITY does not contribute;
+ * SREC_LISTED_SCORE: an item of listed[b,:] contributes with off_in; SREC_LISTED_DROP: it does not contribute and off_in is
+ * ignored.  A session without an eligible row (or whose eligible rows all score -INFINITY) gives exactly -INFINITY, never NaN.
+ * Subtracting out[b] from off_ex[:, b] and off_in[:, b] renormalises what srec_score_select / srec_score_items return:
  * logsumexp_c(z_c + off_c - Z) = s - Z.  The disjoint row ranges of shards combine by log-sum-exp of their results.
  * No (B, V) tensor, no float atomics: one (max, sum) pair per (item range, session) in ws, folded in range order - the
- * output is a pure function of the inputs.  ws: srec_score_norm_ws() bytes.  Nonzero and no launch for the reasons of
- * srec_score_select_biased. */
+ * output is a pure function of the inputs.  ws: srec_score_norm_ws() bytes.  Nonzero and no launch, beyond the descriptor's
+ * reasons: a NULL out or ws. */
 int srec_score_norm_ws(int B, int V, int d, int C, int L, long* bytes);
-int srec_score_norm(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                    const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                    long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
-                    const int* group, int G, float* out, void* ws, void* stream);
+int srec_score_norm(const void* served, float* out, void* ws, void* stream);
 
 /* ---- serving: DRAW K distinct items per session from the served distribution (recommend.hip, NOISE instances) ------------
- * The selection of srec_score_select_biased over the SAMPLED key of every eligible (session b, row v) pair,
+ * The selection of srec_score_select over the SAMPLED key of every eligible (session b, row v) pair,
  *   key[b,v] = s'[b,v] * inv_temperature + g(seed, q[b], id_lo + v),
- * s' the biased served score and the eligibility those of srec_score_select_biased, inv_temperature = 1 / T > 0 and finite,
- * q[b] = session_keys[b] (any 32-bit value; NULL: the row index b), g independent Gumbel(0, 1) noise.  By the Gumbel-top-k
- * identity the K best keys, in order, are a draw WITHOUT replacement (Plackett-Luce) from p(v) ~ exp(s'[b,v] / T) over the
- * eligible rows.  out_key [B, K] fp32 descending, out_idx [B, K] int32 global ids in draw order; ties towards the lower id;
- * (-INFINITY, -1) slots where fewer than K rows are eligible; K <= SREC_SELECT_MAXK; all layouts and limits of
- * srec_score_select_biased; ws: srec_score_sample_ws() bytes.
+ * inv_temperature = 1 / T > 0 and finite, q[b] = session_keys[b] (any 32-bit value; NULL: the row index b), g independent
+ * Gumbel(0, 1) noise.  By the Gumbel-top-k identity the K best keys, in order, are a draw WITHOUT replacement (Plackett-Luce)
+ * from p(v) ~ exp(s'[b,v] / T) over the eligible rows.  out_key [B, K] fp32 descending, out_idx [B, K] int32 global ids in
+ * draw order; ties towards the lower id; (-INFINITY, -1) slots where fewer than K rows are eligible; K <= SREC_SELECT_MAXK;
+ * floor as in srec_score_select (NULL: no floor, the same kernel instances); ws: srec_score_sample_ws() bytes.
  * The noise is counter-based - a pure function of (seed, q, GLOBAL id), csrc/sample_noise.h; nothing (B, V)-sized exists:
  *   h32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16       (32-bit, "lowbias32")
  *   skey = h32(lo ^ h32(q * 0x9E3779B9 + hi * 0x85EBCA6B + 0x165667B1))      lo / hi: the 32-bit words of seed; per session
@@ -633,25 +630,22 @@ int srec_score_norm(const float* sr, int ld_sr, long comp_stride, const float* E
  *   g    = -logf(-log1pf(-w))                                                in [-2.82, 22.9], always finite
  * so a call is reproducible, a session's draw does not depend on the batch it is in (give it the same key), and the lists
  * of disjoint row shards - every shard with its id_lo - merge by (key, id) to the bits of the single-device call.
- * Nonzero and no launch for the reasons of srec_score_select_biased, for inv_temperature that is not positive and finite
+ * Nonzero and no launch for the reasons of srec_score_select, for inv_temperature that is not positive and finite
  * (zero, negative, infinite, NaN) and for session_keys not aligned to 4 bytes.
  * srec_sample_uniform: HOST function, no GPU - h_out / w_out [n_b, n_v] (either may be NULL, not both) are h and w of the
  * formula for the keys session_keys[0 .. n_b) (NULL: 0 .. n_b - 1) and the global ids ids[0 .. n_v) (NULL: 0 .. n_v - 1):
  * the stream pinned for tests and for users who restate a draw. */
 int srec_score_sample_ws(int B, int V, int d, int C, int L, int K, long* bytes);
-int srec_score_sample(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                      long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                      const int* group, int G, float inv_temperature, unsigned long long seed, const int* session_keys,
-                      float* out_key, int* out_idx, void* ws, void* stream);
+int srec_score_sample(const void* served, int K, float inv_temperature, unsigned long long seed, const int* session_keys,
+                      const float* floor, float* out_key, int* out_idx, void* ws, void* stream);
 int srec_sample_uniform(unsigned long long seed, const int* session_keys, int n_b, const int* ids, int n_v,
                         unsigned* h_out, float* w_out);
 
-/* ---- serving: TRUNCATED sampling - a per-session score cutoff found without the (B, V) matrix (score_cutoff.hip), and a
- * floor operand in the selection kernel (recommend.hip) ------------------------------------------------------------------
- * Per session b.  The eligible rows and the biased served score s'[b,v] are exactly those of srec_score_select_biased; layouts,
- * limits, listed_mode, bias / group and id_lo are the same.  m_b = the largest eligible s';  w_v = exp((s'_v - m_b) * inv_t)
- * and W_b = sum of w_v over the eligible rows;  inv_t = 1 / T is the temperature the draw will use.
+/* ---- serving: TRUNCATED sampling - a per-session score cutoff found without the (B, V) matrix (score_cutoff.hip); its
+ * result is the floor operand of srec_score_select / srec_score_sample ---------------------------------------------------
+ * Per session b, over the eligible rows and the biased served score s'[b,v] of the descriptor.  m_b = the largest eligible
+ * s';  w_v = exp((s'_v - m_b) * inv_t) and W_b = sum of w_v over the eligible rows;  inv_t = 1 / T is the temperature the
+ * draw will use.
  * Three criteria, each optional, each evaluated on the FULL eligible distribution (not one after the other):
  *   top_k (integer >= 1, any size - not limited to SREC_SELECT_MAXK; 0 = absent): tau_k = the k-th largest eligible s',
  *     counting multiplicity; with fewer than k eligible rows it is -INFINITY.
@@ -686,7 +680,7 @@ int srec_sample_uniform(unsigned long long seed, const int* session_keys, int n_
  *         with integer atomics (empty bins are skipped); SUM over shards.
  *   state int64 [B][SREC_CUTOFF_STATE]: prefix of the top_k search, of the top_p search, count above, mass above (lo, hi),
  *         W (lo, hi), flags (1: fewer than k eligible rows, 2: W = 0) - written by advance, the same on every shard.
- *   top   fp32 [B]: m_b, from the K = 1 selection (srec_score_select_biased; MAX over shards) - needed ahead of pass 0.
+ *   top   fp32 [B]: m_b, from the K = 1 selection (srec_score_select; MAX over shards) - needed ahead of pass 0.
  * srec_score_cutoff_hist (pass 0 .. 3) reads top and state (pass 0: state is not read); srec_score_cutoff_advance (pass
  * 0 .. 3, no table access, one workgroup per session) scans the summed bins from the top, fixes the next digit of either
  * search and, at pass 3, writes floor (and top[b] + 0.0f back into top); pass = SREC_CUTOFF_PASSES does that last step alone
@@ -694,46 +688,20 @@ int srec_sample_uniform(unsigned long long seed, const int* session_keys, int n_
  * srec_score_cutoff_finish turns the summed tail bins into count and log_kept.  No host synchronisation anywhere.
  * srec_score_cutoff chains everything on one device: ws = srec_score_cutoff_ws() bytes (hist, state and the K = 1 selection's
  * scratch).
- * All return nonzero and do not launch for the reasons of srec_score_select_biased, for inv_temperature not positive and
+ * All return nonzero and do not launch for the reasons of srec_score_select, for inv_temperature not positive and
  * finite, top_k < 0, top_p <= 0 or NaN, min_gap < 0 or NaN, pass out of range, a NULL top / state / hist / floor / output. */
 #define SREC_CUTOFF_PASSES 4
 #define SREC_CUTOFF_STATE 8
 int srec_score_cutoff_ws(int B, int V, int d, int C, int L, long* bytes);
-int srec_score_cutoff_hist(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                           const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                           long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
-                           const int* group, int G, float inv_temperature, int top_k, float top_p, int pass,
-                           const float* top, const long long* state, long long* hist, void* stream);
+int srec_score_cutoff_hist(const void* served, float inv_temperature, int top_k, float top_p, int pass, const float* top,
+                           const long long* state, long long* hist, void* stream);
 int srec_score_cutoff_advance(int B, int pass, int top_k, float top_p, float min_gap, const long long* hist,
                               long long* state, float* top, float* floor, void* stream);
-int srec_score_cutoff_tail(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                           const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                           long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
-                           const int* group, int G, float inv_temperature, const float* top, const float* floor,
-                           long long* hist, void* stream);
+int srec_score_cutoff_tail(const void* served, float inv_temperature, const float* top, const float* floor, long long* hist,
+                           void* stream);
 int srec_score_cutoff_finish(int B, const long long* hist, int* count, float* log_kept, void* stream);
-int srec_score_cutoff(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                      long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
-                      const int* group, int G, float inv_temperature, int top_k, float top_p, float min_gap,
-                      float* floor, int* count, float* log_kept, float* top, void* ws, void* stream);
-
-/* ---- serving: the floor in the selection and in the draw (recommend.hip, FLOOR instances) --------------------------------
- * floor fp32 [B], nullable: a (session b, row v) pair is additionally INELIGIBLE when s'[b,v] < floor[b] - the test is on the
- * biased served score, before temperature and noise.  With floor == NULL these ARE srec_score_select_biased and
- * srec_score_sample, bit for bit (the same kernel instances).  A session whose kept set is smaller than K ends in
- * (-INFINITY, -1) slots.  floor aligned to 4 bytes; everything else as in the two calls. */
-int srec_score_select_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                            const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                            long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                            const int* group, int G, const float* floor, float* out_val, int* out_idx, void* ws,
-                            void* stream);
-int srec_score_sample_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                            const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                            long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                            const int* group, int G, float inv_temperature, unsigned long long seed,
-                            const int* session_keys, const float* floor, float* out_key, int* out_idx, void* ws,
-                            void* stream);
+int srec_score_cutoff(const void* served, float inv_temperature, int top_k, float top_p, float min_gap, float* floor,
+                      int* count, float* log_kept, float* top, void* ws, void* stream);
 
 /* ---- serving: diversified top-N - greedy MMR re-rank of a pool, and intra-list diversity (diversify.hip) ------------------
  * Per session a pool of M slots; slot i has a row index row[b * M + i] into the row source X (fp32, n_rows rows of d columns,

@@ -1,7 +1,8 @@
 """ctypes binding of libsrec_hip.so.
 
 The prototypes are parsed from include/srec.h, so every symbol the header declares
-is bound (and a missing export fails at import).  The host descriptor structs and the
+is bound (and a missing export fails at import) and takes exactly the declared number of
+arguments (TypeError ahead of the call otherwise).  The host descriptor structs and the
 SREC_* capacity constants are bound from include/srec.h and include/srec_hg.h in the same
 way (STRUCTS, CONST): to extend a struct, edit the header only.  There is NO fallback: if
 the HIP library is absent, or a tensor is not on the GPU, the product path raises.
@@ -101,9 +102,14 @@ class _Lib:
                 'There is no CPU fallback for the product path.' % LIB_PATH)
         dll = ctypes.CDLL(LIB_PATH)
         for name, args in self.protos.items():
-            fn = getattr(dll, name)            # AttributeError if the export is missing
-            fn.restype = ctypes.c_int
-            fn.argtypes = [_CT[t] for t, _ in args]
+            getattr(dll, name)                 # AttributeError if the export is missing
+            # bound WITH parameter flags: ctypes then takes exactly the declared number of arguments (TypeError otherwise,
+            # ahead of the call).  A plain cdecl binding lets surplus arguments through, and a caller written against an
+            # older positional prototype would hand its first pointer to a `const void* desc` / `served`, which is followed
+            types = [_CT[t] for t, _ in args]
+            fn = ctypes.CFUNCTYPE(ctypes.c_int, *types)((name, dll), tuple((1, n) for _, n in args))
+            fn.argtypes = types
+            setattr(dll, name, fn)
         self._dll = dll
         return dll
 

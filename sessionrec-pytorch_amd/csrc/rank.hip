@@ -213,18 +213,18 @@ extern "C" int srec_score_rank_ws(int B, int V, int d, int C, int L, long* bytes
     return 0;
 }
 
-extern "C" int srec_score_rank(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                               const float* off_ex, const float* off_in, const int* listed, int L, const int* labels,
-                               long id_lo, int B, int V, int d, int C, float* target, int target_given, int* rank, void* ws,
+// the kernels here know neither a bias nor SREC_LISTED_DROP: a descriptor that carries one is refused, not half obeyed
+extern "C" int srec_score_rank(const void* served, const int* labels, float* target, int target_given, int* rank, void* ws,
                                void* stream) {
     (void)ws;
-    if (B <= 0) return 0;
+    const srec_served* s = (const srec_served*)served;
+    if (s == nullptr) return SREC_BAD_ARG;
+    if (s->B <= 0) return 0;
     RankArgs a{};
-    if (pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, 0, id_lo, B, V, d, C, nullptr, 0, nullptr, 1,
-                  false) ||
-        labels == nullptr || target == nullptr || (rank == nullptr && target_given))
+    if (pass_args(a, *s, false) || s->bias != nullptr || s->listed_mode != SREC_LISTED_SCORE || labels == nullptr ||
+        target == nullptr || (rank == nullptr && target_given))
         return SREC_BAD_ARG;
     a.labels = labels; a.target = target; a.target_given = target_given; a.rank = rank;
     hipStream_t st = (hipStream_t)stream;
-    return switch_c(C, [&](auto c) { return run<c.value>(a, st); });
+    return switch_c(s->C, [&](auto c) { return run<c.value>(a, st); });
 }

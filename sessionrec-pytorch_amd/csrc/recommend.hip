@@ -258,19 +258,16 @@ extern "C" int srec_score_select_ws(int B, int V, int d, int C, int L, int K, lo
 
 namespace {
 
-// all entry points: NOISE = false is srec_score_select_biased as it always was (inv_t / seed / qkeys are not read); floor ==
-// NULL launches the instances those two calls always launched
+// both entry points (s: not NULL, B > 0): NOISE = false is the selection as it always was (inv_t / seed / qkeys are not
+// read); floor == NULL launches the instances the calls without a floor always launched
 template <bool NOISE>
-int select_launch(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs, const float* off_ex,
-                  const float* off_in, const int* listed, int L, int listed_mode, long id_lo, int B, int V, int d, int C, int K,
-                  const float* bias, long ld_bias, const int* group, int G, float inv_t, unsigned long long seed,
-                  const int* qkeys, const float* floor, float* out_val, int* out_idx, void* ws, void* stream) {
-    if (B <= 0) return 0;
+int select_launch(const srec_served& s, int K, float inv_t, unsigned long long seed, const int* qkeys, const float* floor,
+                  float* out_val, int* out_idx, void* ws, void* stream) {
     SelArgs a{};
-    if (pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias, ld_bias,
-                  group, G, true) ||
-        K < 1 || K > MAXK || out_val == nullptr || out_idx == nullptr || ws == nullptr || ((uintptr_t)floor & 3))
+    if (pass_args(a, s, true) || K < 1 || K > MAXK || out_val == nullptr || out_idx == nullptr || ws == nullptr ||
+        ((uintptr_t)floor & 3))
         return SREC_BAD_ARG;
+    const int B = s.B, V = s.V, d = s.d, C = s.C;
     const int R = ranges(B, V);
     const dim3 grid(split_ranges(a, R), cdiv(B, SB));
     a.K = K;
@@ -290,7 +287,7 @@ int select_launch(const float* sr, int ld_sr, long comp_stride, const float* E, 
             }
         }))
         return rc;
-    hipLaunchKernelGGL(select_merge_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, a.pv, a.pi, (int)grid.x, B, K, id_lo, out_val,
+    hipLaunchKernelGGL(select_merge_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, a.pv, a.pi, (int)grid.x, B, K, s.id_lo, out_val,
                        out_idx);
     SREC_LAUNCH_CHECK();
     return 0;
@@ -298,21 +295,12 @@ int select_launch(const float* sr, int ld_sr, long comp_stride, const float* E, 
 
 }  // namespace
 
-extern "C" int srec_score_select_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                        const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                        long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                                        const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream) {
-    return select_launch<false>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
-                                bias, ld_bias, group, G, 1.f, 0ull, nullptr, nullptr, out_val, out_idx, ws, stream);
-}
-
-extern "C" int srec_score_select_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                       const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                       long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                                       const int* group, int G, const float* floor, float* out_val, int* out_idx, void* ws,
-                                       void* stream) {
-    return select_launch<false>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
-                                bias, ld_bias, group, G, 1.f, 0ull, nullptr, floor, out_val, out_idx, ws, stream);
+extern "C" int srec_score_select(const void* served, int K, const float* floor, float* out_val, int* out_idx, void* ws,
+                                 void* stream) {
+    const srec_served* s = (const srec_served*)served;
+    if (s == nullptr) return SREC_BAD_ARG;
+    if (s->B <= 0) return 0;
+    return select_launch<false>(*s, K, 1.f, 0ull, nullptr, floor, out_val, out_idx, ws, stream);
 }
 
 // ws: as srec_score_select_ws (the per-range lists hold keys where that call's hold scores)
@@ -320,26 +308,14 @@ extern "C" int srec_score_sample_ws(int B, int V, int d, int C, int L, int K, lo
     return srec_score_select_ws(B, V, d, C, L, K, bytes);
 }
 
-extern "C" int srec_score_sample_floor(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                       const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                       long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                                       const int* group, int G, float inv_temperature, unsigned long long seed,
-                                       const int* session_keys, const float* floor, float* out_key, int* out_idx, void* ws,
-                                       void* stream) {
-    if (B <= 0) return 0;
+extern "C" int srec_score_sample(const void* served, int K, float inv_temperature, unsigned long long seed,
+                                 const int* session_keys, const float* floor, float* out_key, int* out_idx, void* ws,
+                                 void* stream) {
+    const srec_served* s = (const srec_served*)served;
+    if (s == nullptr) return SREC_BAD_ARG;
+    if (s->B <= 0) return 0;
     if (!(inv_temperature > 0.f) || !(inv_temperature <= 3.402823466e+38f) || ((uintptr_t)session_keys & 3)) return SREC_BAD_ARG;
-    return select_launch<true>(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, K,
-                               bias, ld_bias, group, G, inv_temperature, seed, session_keys, floor, out_key, out_idx, ws, stream);
-}
-
-extern "C" int srec_score_sample(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                 const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode, long id_lo,
-                                 int B, int V, int d, int C, int K, const float* bias, long ld_bias, const int* group, int G,
-                                 float inv_temperature, unsigned long long seed, const int* session_keys, float* out_key,
-                                 int* out_idx, void* ws, void* stream) {
-    return srec_score_sample_floor(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C,
-                                   K, bias, ld_bias, group, G, inv_temperature, seed, session_keys, nullptr, out_key, out_idx, ws,
-                                   stream);
+    return select_launch<true>(*s, K, inv_temperature, seed, session_keys, floor, out_key, out_idx, ws, stream);
 }
 
 // HOST: h [n_b, n_v] and w [n_b, n_v] of sample_noise.h for the sessions' keys (NULL: 0 .. n_b - 1) and the global ids
@@ -356,12 +332,4 @@ extern "C" int srec_sample_uniform(unsigned long long seed, const int* session_k
         }
     }
     return 0;
-}
-
-extern "C" int srec_score_select(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                 const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                 long id_lo, int B, int V, int d, int C, int K, float* out_val, int* out_idx, void* ws,
-                                 void* stream) {
-    return srec_score_select_biased(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d,
-                                    C, K, nullptr, 0, nullptr, 1, out_val, out_idx, ws, stream);
 }

@@ -27,12 +27,6 @@
 #include "common.h"
 #include "score_pass.h"
 
-extern "C" int srec_score_select_ws(int B, int V, int d, int C, int L, int K, long* bytes);
-extern "C" int srec_score_select_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                        const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                        long id_lo, int B, int V, int d, int C, int K, const float* bias, long ld_bias,
-                                        const int* group, int G, float* out_val, int* out_idx, void* ws, void* stream);
-
 namespace {
 
 using namespace score_tile;
@@ -322,16 +316,14 @@ inline bool bad_inv_t(float inv_t) { return !(inv_t > 0.f) || !(inv_t <= 3.40282
 inline bool bad_criteria(int top_k, float top_p, float gap) { return top_k < 0 || !(top_p > 0.f) || !(gap >= 0.f); }
 inline bool has_p(float top_p) { return top_p < 1.f; }
 
-int hist_launch(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs, const float* off_ex,
-                const float* off_in, const int* listed, int L, int listed_mode, long id_lo, int B, int V, int d, int C,
-                const float* bias, long ld_bias, const int* group, int G, float inv_t, bool do_k, bool do_p, int pass,
-                const float* top, const long long* state, const float* floor, long long* hist, void* stream) {
-    if (B <= 0) return 0;
+// s: not NULL
+int hist_launch(const srec_served& s, float inv_t, bool do_k, bool do_p, int pass, const float* top, const long long* state,
+                const float* floor, long long* hist, void* stream) {
+    if (s.B <= 0) return 0;
     CutArgs a{};
     const bool tail = pass == NPASS;
-    if (pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias, ld_bias,
-                  group, G, true) ||
-        bad_inv_t(inv_t) || pass < 0 || pass > NPASS || top == nullptr || hist == nullptr || (tail && floor == nullptr) ||
+    const int B = s.B, V = s.V, d = s.d, C = s.C;
+    if (pass_args(a, s, true) || bad_inv_t(inv_t) || pass < 0 || pass > NPASS || top == nullptr || hist == nullptr || (tail && floor == nullptr) ||
         (!tail && pass > 0 && state == nullptr) || (!do_k && !do_p) || ((uintptr_t)top & 3) || ((uintptr_t)floor & 3) ||
         ((uintptr_t)state & 7) || ((uintptr_t)hist & 7))
         return SREC_BAD_ARG;
@@ -363,23 +355,17 @@ extern "C" int srec_score_cutoff_ws(int B, int V, int d, int C, int L, long* byt
     return 0;
 }
 
-extern "C" int srec_score_cutoff_hist(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                      long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias, const int* group,
-                                      int G, float inv_temperature, int top_k, float top_p, int pass, const float* top,
-                                      const long long* state, long long* hist, void* stream) {
-    if (bad_criteria(top_k, top_p, 0.f) || pass < 0 || pass >= NPASS) return SREC_BAD_ARG;
-    return hist_launch(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias,
-                       ld_bias, group, G, inv_temperature, top_k > 0, has_p(top_p), pass, top, state, nullptr, hist, stream);
+extern "C" int srec_score_cutoff_hist(const void* served, float inv_temperature, int top_k, float top_p, int pass,
+                                      const float* top, const long long* state, long long* hist, void* stream) {
+    if (served == nullptr || bad_criteria(top_k, top_p, 0.f) || pass < 0 || pass >= NPASS) return SREC_BAD_ARG;
+    return hist_launch(*(const srec_served*)served, inv_temperature, top_k > 0, has_p(top_p), pass, top, state, nullptr, hist,
+                       stream);
 }
 
-extern "C" int srec_score_cutoff_tail(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                      const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                      long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias, const int* group,
-                                      int G, float inv_temperature, const float* top, const float* floor, long long* hist,
-                                      void* stream) {
-    return hist_launch(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias,
-                       ld_bias, group, G, inv_temperature, true, true, NPASS, top, nullptr, floor, hist, stream);
+extern "C" int srec_score_cutoff_tail(const void* served, float inv_temperature, const float* top, const float* floor,
+                                      long long* hist, void* stream) {
+    if (served == nullptr) return SREC_BAD_ARG;
+    return hist_launch(*(const srec_served*)served, inv_temperature, true, true, NPASS, top, nullptr, floor, hist, stream);
 }
 
 extern "C" int srec_score_cutoff_advance(int B, int pass, int top_k, float top_p, float min_gap, const long long* hist,
@@ -411,16 +397,14 @@ extern "C" int srec_score_cutoff_finish(int B, const long long* hist, int* count
     return 0;
 }
 
-extern "C" int srec_score_cutoff(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                 const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode, long id_lo,
-                                 int B, int V, int d, int C, const float* bias, long ld_bias, const int* group, int G,
-                                 float inv_temperature, int top_k, float top_p, float min_gap, float* floor, int* count,
-                                 float* log_kept, float* top, void* ws, void* stream) {
+extern "C" int srec_score_cutoff(const void* served, float inv_temperature, int top_k, float top_p, float min_gap, float* floor,
+                                 int* count, float* log_kept, float* top, void* ws, void* stream) {
+    const srec_served* s = (const srec_served*)served;
+    if (s == nullptr) return SREC_BAD_ARG;
+    const int B = s->B;
     if (B <= 0) return 0;
     PassArgs chk{};
-    if (pass_args(chk, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias,
-                  ld_bias, group, G, true) ||
-        bad_inv_t(inv_temperature) || bad_criteria(top_k, top_p, min_gap) || floor == nullptr || count == nullptr ||
+    if (pass_args(chk, *s, true) || bad_inv_t(inv_temperature) || bad_criteria(top_k, top_p, min_gap) || floor == nullptr || count == nullptr ||
         log_kept == nullptr || top == nullptr || ws == nullptr || ((uintptr_t)ws & 15) || ((uintptr_t)floor & 3) ||
         ((uintptr_t)top & 3) || ((uintptr_t)count & 3) || ((uintptr_t)log_kept & 3))
         return SREC_BAD_ARG;
@@ -429,22 +413,15 @@ extern "C" int srec_score_cutoff(const float* sr, int ld_sr, long comp_stride, c
     int* top_id = (int*)(state + (size_t)B * NSTATE);
     void* sel_ws = (char*)top_id + align16((size_t)B * 4);
     // m_b: the value of the K = 1 selection (an eligible row that scores -inf, and nothing eligible, both give -inf)
-    if (int rc = srec_score_select_biased(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V,
-                                          d, C, 1, bias, ld_bias, group, G, top, top_id, sel_ws, stream))
-        return rc;
+    if (int rc = srec_score_select(served, 1, nullptr, top, top_id, sel_ws, stream)) return rc;
     if (top_k > 0 || has_p(top_p)) {
         for (int pass = 0; pass < NPASS; ++pass) {
-            if (int rc = srec_score_cutoff_hist(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo,
-                                                B, V, d, C, bias, ld_bias, group, G, inv_temperature, top_k, top_p, pass, top,
-                                                state, hist, stream))
-                return rc;
+            if (int rc = srec_score_cutoff_hist(served, inv_temperature, top_k, top_p, pass, top, state, hist, stream)) return rc;
             if (int rc = srec_score_cutoff_advance(B, pass, top_k, top_p, min_gap, hist, state, top, floor, stream)) return rc;
         }
     } else if (int rc = srec_score_cutoff_advance(B, NPASS, 0, 1.f, min_gap, nullptr, nullptr, top, floor, stream)) {
         return rc;
     }
-    if (int rc = srec_score_cutoff_tail(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d,
-                                        C, bias, ld_bias, group, G, inv_temperature, top, floor, hist, stream))
-        return rc;
+    if (int rc = srec_score_cutoff_tail(served, inv_temperature, top, floor, hist, stream)) return rc;
     return srec_score_cutoff_finish(B, hist, count, log_kept, stream);
 }

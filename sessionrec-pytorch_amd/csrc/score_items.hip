@@ -21,7 +21,7 @@
 //     (d, C) alone - never on M, the slot, the shard or the view.
 // No atomics, no workspace, no scratch memory; every out[b,m] is written by exactly one lane.  Sessions run along grid.x.
 //
-// srec_score_items_biased (template parameter BIAS; false: the instances of srec_score_items, unchanged): the owning shard
+// a bias in the descriptor (template parameter BIAS; false: the instances of the call without one, unchanged): the owning shard
 // adds bias[group[b], local row] after the mixture.  The lookup sits where thread i resolves slot i: a bias of -INFINITY
 // turns the slot into a padding slot (no row is read for it), any other value goes to a third LDS word per slot that the
 // writing lane adds - no memory instruction joins the hot loop, and a foreign id reads neither the table nor the bias.
@@ -192,28 +192,18 @@ int run(const ItemArgs& a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int srec_score_items_biased(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                       const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                       const int* items, long ld_items, int M, long id_lo, int B, int V, int d, int C,
-                                       const float* bias, long ld_bias, const int* group, int G, float* out, void* stream) {
-    if (B <= 0) return 0;
+extern "C" int srec_score_items(const void* served, const int* items, long ld_items, int M, float* out, void* stream) {
+    const srec_served* s = (const srec_served*)served;
+    if (s == nullptr) return SREC_BAD_ARG;
+    if (s->B <= 0) return 0;
     ItemArgs a{};
-    if (score_tile::pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, listed_mode == 1 ? nullptr : off_in, listed, L,
-                              listed_mode, id_lo, B, V, d, C, bias, ld_bias, group, G, true) ||
-        M < 1 || ld_sr < d || ld_e < d || ((uintptr_t)items & 3) || ((uintptr_t)out & 3) || items == nullptr || out == nullptr ||
-        (ld_items != 0 && ld_items < (long)M))
+    if (score_tile::pass_args(a, *s, true) || M < 1 || s->ld_sr < s->d || s->ld_e < s->d || ((uintptr_t)items & 3) ||
+        ((uintptr_t)out & 3) || items == nullptr || out == nullptr || (ld_items != 0 && ld_items < (long)M))
         return SREC_BAD_ARG;
-    if (G == 1) a.group = nullptr;
+    if (s->listed_mode == SREC_LISTED_DROP) a.off_in = nullptr;     // (ItemArgs)
+    if (s->G == 1) a.group = nullptr;
     a.items = items; a.ld_items = ld_items; a.M = M; a.out = out;
-    while ((4 << a.logT) < d && a.logT < 6) ++a.logT;               // the smallest power of two of lanes that covers a row
+    while ((4 << a.logT) < s->d && a.logT < 6) ++a.logT;            // the smallest power of two of lanes that covers a row
     hipStream_t st = (hipStream_t)stream;
-    return score_tile::switch_c(C, [&](auto c) { return run<c.value>(a, st); });
-}
-
-extern "C" int srec_score_items(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                                const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                                const int* items, long ld_items, int M, long id_lo, int B, int V, int d, int C, float* out,
-                                void* stream) {
-    return srec_score_items_biased(sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, items, ld_items,
-                                   M, id_lo, B, V, d, C, nullptr, 0, nullptr, 1, out, stream);
+    return score_tile::switch_c(s->C, [&](auto c) { return run<c.value>(a, st); });
 }

@@ -146,16 +146,13 @@ extern "C" int srec_score_norm_ws(int B, int V, int d, int C, int L, long* bytes
     return 0;
 }
 
-extern "C" int srec_score_norm(const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                               const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode,
-                               long id_lo, int B, int V, int d, int C, const float* bias, long ld_bias,
-                               const int* group, int G, float* out, void* ws, void* stream) {
-    if (B <= 0) return 0;
+extern "C" int srec_score_norm(const void* served, float* out, void* ws, void* stream) {
+    const srec_served* s = (const srec_served*)served;
+    if (s == nullptr) return SREC_BAD_ARG;
+    if (s->B <= 0) return 0;
     NormArgs a{};
-    if (pass_args(a, sr, ld_sr, comp_stride, E, ld_e, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias, ld_bias,
-                  group, G, true) ||
-        out == nullptr || ws == nullptr)
-        return SREC_BAD_ARG;
+    if (pass_args(a, *s, true) || out == nullptr || ws == nullptr) return SREC_BAD_ARG;
+    const int B = s->B, V = s->V, d = s->d, C = s->C;
     const dim3 grid(split_ranges(a, ranges(B, V)), cdiv(B, SB));
     a.part = (float*)ws;
     hipStream_t st = (hipStream_t)stream;

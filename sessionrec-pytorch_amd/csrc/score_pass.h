@@ -17,6 +17,7 @@
 #pragma once
 #include <type_traits>
 #include "score_tile.h"
+#include "../../include/srec.h"
 
 namespace score_tile {
 
@@ -37,20 +38,20 @@ inline bool bad_shape(int B, int V, int d, int C, int L) {
     return B <= 0 || V <= 0 || d <= 0 || (d & 3) || d > 1024 || C < 1 || C > MAXCOMP || L < 0 || L > MAXL;
 }
 
-// The checks every entry point makes, then the argument block (items_per_range: split_ranges).  ids_fit_int: refuse a
-// shard whose last global id does not fit an int (every entry point but srec_score_rank, which never forms such an id).
-inline int pass_args(PassArgs& a, const float* sr, int ld_sr, long comp_stride, const float* E, int ld_e, const float* cs,
-                     const float* off_ex, const float* off_in, const int* listed, int L, int listed_mode, long id_lo, int B,
-                     int V, int d, int C, const float* bias, long ld_bias, const int* group, int G, bool ids_fit_int) {
-    if (bad_shape(B, V, d, C, L) || (ld_sr & 3) || (ld_e & 3) || (comp_stride & 3) || ((uintptr_t)E & 15) ||
-        ((uintptr_t)sr & 15) || id_lo < 0 || (ids_fit_int && id_lo + (long)V > 0x7fffffffL) ||
-        (listed_mode != 0 && listed_mode != 1) || G < 1 || (group == nullptr && G > 1) ||
-        (bias != nullptr && G > 1 && ld_bias < (long)V) || ((uintptr_t)bias & 3) || ((uintptr_t)group & 3))
+// The checks every entry point makes on its descriptor (include/srec.h: srec_served, a HOST struct), then the argument block
+// (items_per_range: split_ranges).  An entry point has refused a NULL descriptor and returned 0 for B <= 0 before it comes
+// here.  ids_fit_int: refuse a shard whose last global id does not fit an int (every entry point but srec_score_rank, which
+// never forms such an id).
+inline int pass_args(PassArgs& a, const srec_served& s, bool ids_fit_int) {
+    if (bad_shape(s.B, s.V, s.d, s.C, s.L) || (s.ld_sr & 3) || (s.ld_e & 3) || (s.comp_stride & 3) || ((uintptr_t)s.E & 15) ||
+        ((uintptr_t)s.sr & 15) || s.id_lo < 0 || (ids_fit_int && s.id_lo + (long)s.V > 0x7fffffffL) ||
+        (s.listed_mode != SREC_LISTED_SCORE && s.listed_mode != SREC_LISTED_DROP) || s.G < 1 || (s.group == nullptr && s.G > 1) ||
+        (s.bias != nullptr && s.G > 1 && s.ld_bias < (long)s.V) || ((uintptr_t)s.bias & 3) || ((uintptr_t)s.group & 3))
         return SREC_BAD_ARG;
-    a.sr = sr; a.ld_sr = ld_sr; a.comp_stride = comp_stride; a.E = E; a.ld_e = ld_e; a.cs = cs;
-    a.off_ex = off_ex; a.off_in = off_in; a.listed = L > 0 ? listed : nullptr; a.L = a.listed != nullptr ? L : 0;
-    a.drop = listed_mode; a.id_lo = id_lo; a.B = B; a.V = V; a.d = d; a.items_per_range = 0;
-    a.bias = bias; a.ld_bias = ld_bias; a.group = group; a.G = G;
+    a.sr = s.sr; a.ld_sr = s.ld_sr; a.comp_stride = s.comp_stride; a.E = s.E; a.ld_e = s.ld_e; a.cs = s.cs;
+    a.off_ex = s.off_ex; a.off_in = s.off_in; a.listed = s.L > 0 ? s.listed : nullptr; a.L = a.listed != nullptr ? s.L : 0;
+    a.drop = s.listed_mode; a.id_lo = s.id_lo; a.B = s.B; a.V = s.V; a.d = s.d; a.items_per_range = 0;
+    a.bias = s.bias; a.ld_bias = s.ld_bias; a.group = s.group; a.G = s.G;
     return 0;
 }
 

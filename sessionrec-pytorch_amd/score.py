@@ -7,7 +7,7 @@ from collections import namedtuple
 import torch
 
 from . import ops                    # (ops.py imports this module at its end: import the package or ops first, never score alone)
-from ._lib import CONST, lib, ptr, stream
+from ._lib import CONST, STRUCTS, lib, ptr, stream
 from .ops import _ld, _rows, gemm_nn, gemm_tn
 
 
@@ -248,14 +248,20 @@ def _byte_ws(kind, device, nbytes, cache=None):
     return ws
 
 
+def _scratch(kind, device, ws_fn, *shape, cache=None):
+    """the scratch of one launch: ask the library's *_ws entry point for the bytes of this shape (it refuses a shape outside
+    the contract up front), take the never-resized buffer of that kind (_byte_ws)"""
+    n = _ct.c_long()
+    ws_fn(*shape, _ct.addressof(n))
+    return _byte_ws(kind, device, n.value, cache)
+
+
 def score_topk(sr, table, cs, k):
     """(values [B,k], item ids [B,k]) of the k largest z[b,v] = cs[v] <sr_b, E_v> - no (B, V) tensor (evaluation)"""
     sr = _rows(sr.detach())
     B, d = sr.shape
     V = table.shape[0]
-    n = _ct.c_long()
-    lib.srec_score_topk_ws(B, V, k, _ct.addressof(n))
-    ws = _byte_ws('topk', sr.device, n.value)
+    ws = _scratch('topk', sr.device, lib.srec_score_topk_ws, B, V, k)
     val = torch.empty(B, k, device=sr.device, dtype=torch.float32)
     idx = torch.empty(B, k, device=sr.device, dtype=torch.int32)
     lib.srec_score_topk(ptr(sr), _ld(sr), ptr(table), table.stride(0), ptr(cs), B, V, d, k, ptr(val), ptr(idx), ptr(ws),
@@ -276,6 +282,7 @@ _LISTED_TOO_MANY = {
     'score_sample': 'score_sample: %d listed items per session; csrc/recommend.hip takes at most 64',
     'score_cutoff': 'score_cutoff: %d listed items per session; csrc/score_cutoff.hip takes at most 64',
 }
+_LISTED_TOO_MANY['cutoff_passes'] = _LISTED_TOO_MANY['score_cutoff']      # (score_cutoff's generator speaks of lists in its words)
 
 
 def _mixture_args(who, srs, table, off_ex, off_in, listed):
@@ -318,10 +325,6 @@ BiasArgs = namedtuple('BiasArgs', 'bias ld_bias group G')
 _NO_BIAS = BiasArgs(None, 0, None, 1)
 
 
-def _listed_mode(drop_listed):
-    return CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
-
-
 def _bias_args(who, bias, group, B, V):
     """The per-item bias of score_select and score_items as one BiasArgs.  bias: floating [V] (one row for all sessions) or
     [G, V] with group [B] integer row ids in [0, G) (a [1, V] bias needs none); None = no bias.  A tensor with unit column
@@ -357,6 +360,33 @@ def _bias_args(who, bias, group, B, V):
     if bias.dtype != torch.float32 or bias.stride(-1) != 1 or (bias.dim() == 2 and G > 1 and bias.stride(0) < V):
         bias = bias.to(torch.float32).contiguous()
     return BiasArgs(bias, bias.stride(0) if bias.dim() == 2 else V, group if G > 1 else None, G)
+
+
+_Served = STRUCTS['srec_served']           # bound from include/srec.h (_lib.parse_structs), never retyped
+
+
+class ServedArgs(namedtuple('ServedArgs', 'srs ld_sr comp table cs off_ex off_in listed L listed_mode id_lo B V d C '
+                                          'bias ld_bias group G')):
+    """The operands of the served score as every score_* call launches with them: the members of srec_served (include/srec.h)
+    in its order, tensors where the struct has pointers - the record owns what the pointers will name."""
+    __slots__ = ()
+
+    def struct(self):
+        """the host srec_served of one library call (keep it, and this record, alive across the call).  ptr(): a CPU tensor
+        raises here, after every argument check"""
+        srs, ld_sr, comp, table, cs, off_ex, off_in, listed, L, listed_mode, id_lo, B, V, d, C, bias, ld_bias, group, G = self
+        return _Served(ptr(srs), ld_sr, comp, ptr(table), table.stride(0), ptr(cs), ptr(off_ex), ptr(off_in), ptr(listed), L,
+                       listed_mode, id_lo, B, V, d, C, ptr(bias), ld_bias, ptr(group), G)
+
+
+def _served_args(who, srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group):
+    """_mixture_args and _bias_args as one ServedArgs, errors in the words of `who`.  THE place where drop_listed becomes the
+    listed mode and off_in is ignored under it.  Pure torch (no launch, no library call): it checks CPU tensors as well."""
+    srs, ld_sr, comp, C, B, d, table, V, off_ex, off_in, listed, L = _mixture_args(who, srs, table, off_ex,
+                                                                                  None if drop_listed else off_in, listed)
+    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
+    return ServedArgs(srs, ld_sr, comp, table, cs, off_ex, off_in, listed, L, mode, int(id_lo), B, V, d, C,
+                      *_bias_args(who, bias, group, B, V))
 
 
 def catalog_bias(num_items, allow=None, deny=None, boost=None, device=None):
@@ -400,7 +430,7 @@ def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id
     global item ids (< 0: rank -1); id_lo: global id of table row 0 (a row shard).  target: the labels' scores when they
     are already known (the sharded case: summed over the shards) - else computed here, 0 for labels other shards own.
     target_only: (None, target) from the target pass alone - a shard's share ahead of that sum."""
-    a = _mixture_args('score_rank', srs, table, off_ex, off_in, listed)
+    a = _served_args('score_rank', srs, table, cs, off_ex, off_in, listed, False, id_lo, None, None)
     B, dev = a.B, a.srs.device
     if B == 0:
         return torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.float32)
@@ -408,15 +438,12 @@ def score_rank(srs, table, cs, labels, off_ex=None, off_in=None, listed=None, id
     assert labels.numel() == B, (labels.shape, B)
     # the C ABI carries a workspace (partial counts per range are one legal implementation); the current kernels meet in
     # integer atomics and ask for a token size only - the call still validates the shape contract up front
-    n = _ct.c_long()
-    lib.srec_score_rank_ws(B, a.V, a.d, a.C, a.L, _ct.addressof(n))
-    ws = _byte_ws('rank', dev, n.value)
+    ws = _scratch('rank', dev, lib.srec_score_rank_ws, B, a.V, a.d, a.C, a.L)
     given = target is not None
     target = target.detach().to(torch.float32).contiguous() if given else torch.empty(B, device=dev, dtype=torch.float32)
     rank = None if target_only else torch.empty(B, device=dev, dtype=torch.int32)
-    lib.srec_score_rank(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                        ptr(a.listed), a.L, ptr(labels), int(id_lo), B, a.V, a.d, a.C, ptr(target), int(given), ptr(rank),
-                        ptr(ws), stream())
+    desc = a.struct()
+    lib.srec_score_rank(_ct.addressof(desc), ptr(labels), ptr(target), int(given), ptr(rank), ptr(ws), stream())
     return rank, target
 
 
@@ -448,24 +475,17 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     if k < 1 or k > CONST['SREC_SELECT_MAXK']:
         raise ValueError('score_select: k = %d; the selection kernel of csrc/recommend.hip keeps between 1 and %d items per '
                          'session' % (k, CONST['SREC_SELECT_MAXK']))
-    a = _mixture_args('score_select', srs, table, off_ex, None if drop_listed else off_in, listed)
-    bi = _bias_args('score_select', bias, group, a.B, a.V)
+    a = _served_args('score_select', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
     B, dev = a.B, a.srs.device
     val = torch.empty(B, k, device=dev, dtype=torch.float32)
     idx = torch.empty(B, k, device=dev, dtype=torch.int32)
     if B == 0:
         return val, idx
-    n = _ct.c_long()
-    lib.srec_score_select_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
-    ws = _byte_ws('select', dev, n.value)
+    ws = _scratch('select', dev, lib.srec_score_select_ws, B, a.V, a.d, a.C, a.L, k)
     floor = _floor_arg('score_select', floor, B, dev)
-    head = (ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in), ptr(a.listed), a.L,
-            _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G)
-    if floor is None:
-        # (no bias: bias NULL, G 1 - what srec_score_select passes on, the same kernel instances)
-        lib.srec_score_select_biased(*head, ptr(val), ptr(idx), ptr(ws), stream())
-    else:
-        lib.srec_score_select_floor(*head, ptr(floor), ptr(val), ptr(idx), ptr(ws), stream())
+    desc = a.struct()
+    # (no bias: bias NULL, G 1; no floor: NULL - the plain call, the same kernel instances)
+    lib.srec_score_select(_ct.addressof(desc), k, ptr(floor), ptr(val), ptr(idx), ptr(ws), stream())
     return val, idx
 
 
@@ -574,8 +594,7 @@ def score_sample(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     floor: fp32 [B] or None - the draw is among the rows with s' >= floor[b] only (tested on s', before temperature and noise:
     truncated sampling, the floor of score_cutoff); None: the call is what it was, the same kernel instances."""
     k, inv_t, seed = sample_scalars('score_sample', k, temperature, seed)
-    a = _mixture_args('score_sample', srs, table, off_ex, None if drop_listed else off_in, listed)
-    bi = _bias_args('score_sample', bias, group, a.B, a.V)
+    a = _served_args('score_sample', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
     B, dev = a.B, a.srs.device
     q = _session_keys('score_sample', session_keys, B)
     key = torch.empty(B, k, device=dev, dtype=torch.float32)
@@ -584,17 +603,10 @@ def score_sample(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
         return key, idx
     if q is not None:
         q = q.to(dev)
-    n = _ct.c_long()
-    lib.srec_score_sample_ws(B, a.V, a.d, a.C, a.L, k, _ct.addressof(n))
-    ws = _byte_ws('sample', dev, n.value, _SAMPLE_WS)
+    ws = _scratch('sample', dev, lib.srec_score_sample_ws, B, a.V, a.d, a.C, a.L, k, cache=_SAMPLE_WS)
     floor = _floor_arg('score_sample', floor, B, dev)
-    head = (ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in), ptr(a.listed), a.L,
-            _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, k, ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G, inv_t, seed,
-            ptr(q))
-    if floor is None:
-        lib.srec_score_sample(*head, ptr(key), ptr(idx), ptr(ws), stream())
-    else:
-        lib.srec_score_sample_floor(*head, ptr(floor), ptr(key), ptr(idx), ptr(ws), stream())
+    desc = a.struct()
+    lib.srec_score_sample(_ct.addressof(desc), k, inv_t, seed, ptr(q), ptr(floor), ptr(key), ptr(idx), ptr(ws), stream())
     return key, idx
 
 
@@ -616,8 +628,7 @@ def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, dr
     soft-max needs ahead of it, this route beats score_logp(...).gather(1, items) up to M = 2000 (342 against 352 us) and
     loses at M = 4000 (462 against 370 us) - for lists of several thousand items per session materialise instead; a C = 3
     mixture stays 2.6x ahead of forward().gather at M = 4000."""
-    a = _mixture_args('score_items', srs, table, off_ex, None if drop_listed else off_in, listed)
-    bi = _bias_args('score_items', bias, group, a.B, a.V)
+    a = _served_args('score_items', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
     B, dev = a.B, a.srs.device
     items = items.detach()
     if items.is_floating_point() or items.is_complex() or items.dtype == torch.bool or items.dim() not in (1, 2):
@@ -631,10 +642,8 @@ def score_items(srs, table, cs, items, off_ex=None, off_in=None, listed=None, dr
     if not checked and int(items.min()) < -1:
         raise ValueError('score_items: item id %d; ids are >= 0, or -1 for a padding slot' % int(items.min()))
     items = items.to(torch.int32).contiguous()
-    lib.srec_score_items_biased(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex),
-                                ptr(a.off_in), ptr(a.listed), a.L, _listed_mode(drop_listed), ptr(items),
-                                M if items.dim() == 2 else 0, M, int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias,
-                                ptr(bi.group), bi.G, ptr(out), stream())
+    desc = a.struct()
+    lib.srec_score_items(_ct.addressof(desc), ptr(items), M if items.dim() == 2 else 0, M, ptr(out), stream())
     return out
 
 
@@ -652,18 +661,14 @@ def score_norm(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_liste
     for score_logp(...) + torch.logsumexp and 203 us for the statistics pass (score_stats); 506 - 552 us at C = 3 (a [4, V]
     bias, a 20-item list scored or dropped) against 1.7 - 3.2 ms for the three-matrix mixture - no row in which materialising
     is faster."""
-    a = _mixture_args('score_norm', srs, table, off_ex, None if drop_listed else off_in, listed)
-    bi = _bias_args('score_norm', bias, group, a.B, a.V)
+    a = _served_args('score_norm', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
     B, dev = a.B, a.srs.device
     out = torch.empty(B, device=dev, dtype=torch.float32)
     if B == 0:
         return out
-    n = _ct.c_long()
-    lib.srec_score_norm_ws(B, a.V, a.d, a.C, a.L, _ct.addressof(n))
-    ws = _byte_ws('norm', dev, n.value, _NORM_WS)
-    lib.srec_score_norm(ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in),
-                        ptr(a.listed), a.L, _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C, ptr(bi.bias), bi.ld_bias,
-                        ptr(bi.group), bi.G, ptr(out), ptr(ws), stream())
+    ws = _scratch('norm', dev, lib.srec_score_norm_ws, B, a.V, a.d, a.C, a.L, cache=_NORM_WS)
+    desc = a.struct()
+    lib.srec_score_norm(_ct.addressof(desc), ptr(out), ptr(ws), stream())
     return out
 
 
@@ -730,13 +735,12 @@ def score_cutoff(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_lis
     (3.58 ms); at a shard of V 1 250 000 (C = 1) 37.8 ms against 70.1 ms.  min_p alone needs no search: 0.52 ms."""
     c = _cutoff_operands('score_cutoff', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group, top_k, top_p,
                          min_p, temperature)
-    if c.B == 0:
+    a = c.a
+    if a.B == 0:
         return c.out
     if reduce_max is None and reduce_sum is None:
-        n = _ct.c_long()
-        lib.srec_score_cutoff_ws(c.B, c.V, c.d, c.C, c.L, _ct.addressof(n))
-        ws = _byte_ws('cutoff', c.dev, n.value, _CUTOFF_WS)
-        lib.srec_score_cutoff(*c.head, *c.tail, c.inv_t, c.k, c.p, c.gap, *[ptr(t) for t in c.out], ptr(ws), stream())
+        ws = _scratch('cutoff', a.srs.device, lib.srec_score_cutoff_ws, a.B, a.V, a.d, a.C, a.L, cache=_CUTOFF_WS)
+        lib.srec_score_cutoff(_ct.addressof(c.desc), c.inv_t, c.k, c.p, c.gap, *[ptr(t) for t in c.out], ptr(ws), stream())
         return c.out
     same = lambda t: t
     reduce = {'max': reduce_max or same, 'sum': reduce_sum or same}
@@ -759,37 +763,33 @@ def cutoff_passes(srs, table, cs, off_ex=None, off_in=None, listed=None, drop_li
                                            top_k, top_p, min_p, temperature))
 
 
-# what the library calls of one cutoff take: the checked scalars, the leading arguments every pass shares (head: sessions,
-# table, offsets, list, shape; tail: bias), the outputs (floor, count, log_kept, top), and `keep`, the owners of the memory
-# the pointers of head / tail name
-CutoffOperands = namedtuple('CutoffOperands', 'k p gap inv_t head tail out B V d C L dev keep')
+# what the library calls of one cutoff take: the checked scalars, the served operands (a: the ServedArgs, which owns the
+# tensors; desc: its srec_served, None for an empty batch) and the outputs (floor, count, log_kept, top)
+CutoffOperands = namedtuple('CutoffOperands', 'k p gap inv_t a desc out')
 
 
 def _cutoff_operands(who, srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group, top_k, top_p, min_p, temperature):
     k_, p_, gap, inv_t = cutoff_scalars(who, top_k, top_p, min_p, temperature)
-    a = _mixture_args('score_cutoff', srs, table, off_ex, None if drop_listed else off_in, listed)
-    bi = _bias_args(who, bias, group, a.B, a.V)
+    a = _served_args(who, srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
     B, dev = a.B, a.srs.device
-    head = (ptr(a.srs), a.ld_sr, a.comp, ptr(a.table), a.table.stride(0), ptr(cs), ptr(a.off_ex), ptr(a.off_in), ptr(a.listed), a.L,
-            _listed_mode(drop_listed), int(id_lo), B, a.V, a.d, a.C) if B > 0 else None
-    tail = (ptr(bi.bias), bi.ld_bias, ptr(bi.group), bi.G) if B > 0 else None
+    desc = a.struct() if B > 0 else None
     out = (torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.int32),
            torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.float32))
-    return CutoffOperands(k_, p_, gap, inv_t, head, tail, out, B, a.V, a.d, a.C, a.L, dev, (a, bi, cs))
+    return CutoffOperands(k_, p_, gap, inv_t, a, desc, out)
 
 
 def _cutoff_passes(c):
     floor, count, log_kept, top = c.out
-    B, dev = c.B, c.dev
+    a = c.a
+    B, dev = a.B, a.srs.device
     if B == 0:
         return c.out
-    rows = c.V > 0                       # (a shard without rows: neutral partials in EVERY reduce, no pass over a table)
+    served = _ct.addressof(c.desc)
+    rows = a.V > 0                       # (a shard without rows: neutral partials in EVERY reduce, no pass over a table)
     if rows:
-        n = _ct.c_long()
-        lib.srec_score_select_ws(B, c.V, c.d, c.C, c.L, 1, _ct.addressof(n))
-        ws = _byte_ws('select', dev, n.value, _CUTOFF_WS)
+        ws = _scratch('select', dev, lib.srec_score_select_ws, B, a.V, a.d, a.C, a.L, 1, cache=_CUTOFF_WS)
         ids = torch.empty(B, device=dev, dtype=torch.int32)
-        lib.srec_score_select_biased(*c.head, 1, *c.tail, ptr(top), ptr(ids), ptr(ws), stream())
+        lib.srec_score_select(served, 1, None, ptr(top), ptr(ids), ptr(ws), stream())
     else:
         top.fill_(float('-inf'))
     top = yield 'max', top
@@ -801,7 +801,7 @@ def _cutoff_passes(c):
         """this shard's histogram of one pass: the pass entry points zero `hist` themselves; a shard without rows zeroes it
         here - what came back from the last reduce (possibly in place) is the sum over ALL shards, not a neutral partial"""
         if rows:
-            launch(*c.head, *c.tail, c.inv_t, *args, ptr(hist), stream())
+            launch(served, c.inv_t, *args, ptr(hist), stream())
         else:
             hist.zero_()
         return hist

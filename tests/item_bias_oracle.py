@@ -1,4 +1,4 @@
-"""float64 restatement of the per-item bias contract (include/srec.h: srec_score_select_biased, srec_score_items_biased),
+"""float64 restatement of the per-item bias contract (include/srec.h: the bias of srec_served in srec_score_select and srec_score_items),
 shared by tests/test_item_bias_cpu.py, tests/test_item_bias_gpu.py and tests/item_bias_gpu_worker.py.  It builds on
 select_oracle and items_oracle: the biased score is scores64(...) + bias[group], and bias == -inf goes to select64 / items64
 as `drop`.  Everything is materialised: this is the yardstick, not the product."""

@@ -133,8 +133,20 @@ def test_score_cutoff_checks_before_any_launch():
 def test_header_declares_what_the_library_exports_for_the_cutoff():
     L = pkg('_lib')
     want = {'srec_score_cutoff_ws', 'srec_score_cutoff_hist', 'srec_score_cutoff_advance', 'srec_score_cutoff_tail',
-            'srec_score_cutoff_finish', 'srec_score_cutoff', 'srec_score_select_floor', 'srec_score_sample_floor'}
-    assert want <= set(L.lib.protos)
+            'srec_score_cutoff_finish', 'srec_score_cutoff', 'srec_score_select', 'srec_score_sample'}
+    protos = L.lib.protos
+    assert want <= set(protos)
+    # the floor is an operand of the selection and of the draw themselves: no _floor variants
+    assert not {'srec_score_select_floor', 'srec_score_sample_floor'} & set(protos)
+    assert ('const float*', 'floor') in protos['srec_score_select'] and ('const float*', 'floor') in protos['srec_score_sample']
+    served, t = [('const void*', 'served')], ('float', 'inv_temperature')
+    assert protos['srec_score_cutoff_hist'] == served + [t, ('int', 'top_k'), ('float', 'top_p'), ('int', 'pass'), ('const float*', 'top'),
+                                                         ('const long long*', 'state'), ('long long*', 'hist'), ('void*', 'stream')]
+    assert protos['srec_score_cutoff_tail'] == served + [t, ('const float*', 'top'), ('const float*', 'floor'), ('long long*', 'hist'),
+                                                         ('void*', 'stream')]
+    assert protos['srec_score_cutoff'] == served + [t, ('int', 'top_k'), ('float', 'top_p'), ('float', 'min_gap'), ('float*', 'floor'),
+                                                    ('int*', 'count'), ('float*', 'log_kept'), ('float*', 'top'), ('void*', 'ws'),
+                                                    ('void*', 'stream')]
     assert L.CONST['SREC_CUTOFF_PASSES'] == 4 and L.CONST['SREC_CUTOFF_STATE'] == 8
     if os.path.exists(L.LIB_PATH):
         out = subprocess.run(['nm', '-D', '--defined-only', L.LIB_PATH], capture_output=True, text=True, check=True).stdout

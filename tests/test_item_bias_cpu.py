@@ -1,13 +1,13 @@
 """CPU half of the per-item bias of the serving calls: the bias normaliser of ops.score_select / ops.score_items
-(score._bias_args), ops.catalog_bias, the launchers' catalogue readers and parser errors, the C ABI of the two biased entry
-points (declared with the expected argument types beside the two unchanged ones, exported, bad arguments refused without a
-launch) and the float64 oracle (tests/item_bias_oracle.py) against a brute-force loop."""
+(score._bias_args), ops.catalog_bias, the launchers' catalogue readers and parser errors, the C ABI of the bias in the two serving
+entry points (the members of the srec_served descriptor both take, exported, bad arguments refused without a launch) and the float64 oracle (tests/item_bias_oracle.py) against a brute-force loop."""
 import os
 import sys
 
 import pytest
 import torch
 
+import served_abi
 from item_bias_oracle import NINF, bias_rows, exact_bias, items_biased64, select_biased64
 from select_oracle import drop_mask
 from util import ROOT, pkg
@@ -162,26 +162,22 @@ def test_launchers_parse_catalogue_flags_and_refuse_before_a_model_is_built(tmp_
 
 
 # ------------------------------------------------------------------------------------------- C ABI
-SELECT = ['sr', 'ld_sr', 'comp_stride', 'E', 'ld_e', 'cs', 'off_ex', 'off_in', 'listed', 'L', 'listed_mode', 'id_lo', 'B', 'V', 'd',
-          'C', 'K']
-ITEMS = ['sr', 'ld_sr', 'comp_stride', 'E', 'ld_e', 'cs', 'off_ex', 'off_in', 'listed', 'L', 'listed_mode', 'items', 'ld_items', 'M',
-         'id_lo', 'B', 'V', 'd', 'C']
-BIAS = [('const float*', 'bias'), ('long', 'ld_bias'), ('const int*', 'group'), ('int', 'G')]
-SELECT_TAIL = [('float*', 'out_val'), ('int*', 'out_idx'), ('void*', 'ws'), ('void*', 'stream')]
-ITEMS_TAIL = [('float*', 'out'), ('void*', 'stream')]
+SELECT = [('int', 'K'), ('const float*', 'floor'), ('float*', 'out_val'), ('int*', 'out_idx'), ('void*', 'ws'), ('void*', 'stream')]
+ITEMS = [('const int*', 'items'), ('long', 'ld_items'), ('int', 'M'), ('float*', 'out'), ('void*', 'stream')]
 
 
 def test_header_declares_the_biased_entry_points_beside_the_unchanged_ones():
+    """the bias is a member of the descriptor every serving entry point takes: one entry point each, no _biased variant"""
     L = pkg('_lib')
     protos = L.parse_header()
-    for old, new, head, tail in (('srec_score_select', 'srec_score_select_biased', SELECT, SELECT_TAIL),
-                                 ('srec_score_items', 'srec_score_items_biased', ITEMS, ITEMS_TAIL)):
-        assert [n for _, n in protos[old]] == head + [n for _, n in tail], old
-        assert protos[old][len(head):] == tail, old
-        assert protos[new] == protos[old][:len(head)] + BIAS + tail, new     # the old arguments up to K / C, the bias, the old tail
+    assert protos['srec_score_select'] == [('const void*', 'served')] + SELECT
+    assert protos['srec_score_items'] == [('const void*', 'served')] + ITEMS
+    assert L.STRUCTS['srec_served']._fields_ == served_abi.MEMBERS
+    assert [n for n, _ in served_abi.MEMBERS[-4:]] == ['bias', 'ld_bias', 'group', 'G']      # behind the unbiased operands
+    assert not {'srec_score_select_biased', 'srec_score_items_biased'} & set(protos)
     dll = L.lib.load()                                  # binds every declared symbol: a missing export raises here
-    assert len(dll.srec_score_select_biased.argtypes) == len(SELECT) + 8
-    assert len(dll.srec_score_items_biased.argtypes) == len(ITEMS) + 6
+    assert len(dll.srec_score_select.argtypes) == 1 + len(SELECT)
+    assert len(dll.srec_score_items.argtypes) == 1 + len(ITEMS)
 
 
 def test_biased_c_entries_refuse_bad_arguments_without_a_launch():
@@ -190,16 +186,20 @@ def test_biased_c_entries_refuse_bad_arguments_without_a_launch():
     dll = pkg('_lib').lib.load()
     common = dict(sr=0x1000, ld_sr=32, comp_stride=0, E=0x2000, ld_e=32, cs=None, off_ex=None, off_in=None, listed=None, L=0,
                   listed_mode=0, id_lo=0, B=2, V=10, d=32, C=1, bias=0x6000, ld_bias=10, group=0x7000, G=3, stream=None)
-    sel = dict(common, K=5, out_val=0x4000, out_idx=0x5000, ws=0x8000)
+    sel = dict(common, K=5, floor=None, out_val=0x4000, out_idx=0x5000, ws=0x8000)
     itm = dict(common, items=0x3000, ld_items=7, M=7, out=0x4000)
     bad = [dict(G=0), dict(G=-1), dict(group=None), dict(ld_bias=9), dict(bias=0x6002), dict(group=0x7001),
            dict(bias=None, group=None, G=2), dict(bias=None, G=0), dict(d=30), dict(C=5)]
-    for fn, good, names in ((dll.srec_score_select_biased, sel, SELECT + [n for _, n in BIAS + SELECT_TAIL]),
-                            (dll.srec_score_items_biased, itm, ITEMS + [n for _, n in BIAS + ITEMS_TAIL])):
+    # select: without a floor and with an aligned one (the two entry points this one replaced)
+    for fn, good, rest in ((dll.srec_score_select, sel, [n for _, n in SELECT]),
+                           (dll.srec_score_select, dict(sel, floor=0xa000), [n for _, n in SELECT]),
+                           (dll.srec_score_items, itm, [n for _, n in ITEMS])):
         for change in bad:
-            assert fn(*[{**good, **change}[n] for n in names]) == 1001, (fn, change)
-        assert fn(*[{**good, 'B': 0, 'G': 0}[n] for n in names]) == 0          # no sessions: nothing to do
-    assert dll.srec_score_select_biased(*[{**sel, 'K': 129}[n] for n in SELECT + [n for _, n in BIAS + SELECT_TAIL]]) == 1001
+            assert served_abi.call(fn, rest, {**good, **change}) == 1001, (fn, change)
+        assert served_abi.call(fn, rest, {**good, 'B': 0, 'G': 0}) == 0         # no sessions: nothing to do
+        assert served_abi.call(fn, rest, good, null=True) == 1001              # no descriptor
+    assert served_abi.call(dll.srec_score_select, [n for _, n in SELECT], {**sel, 'K': 129}) == 1001
+    assert served_abi.call(dll.srec_score_select, [n for _, n in SELECT], {**sel, 'floor': 0xa002}) == 1001   # floor misaligned
 
 
 # ------------------------------------------------------------------------------------------- oracle against a loop

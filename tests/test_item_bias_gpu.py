@@ -427,7 +427,8 @@ def test_models_refuse_a_bad_item_bias_before_anything_runs(dev, monkeypatch):
     for fn in ('score_select', 'score_items'):
         monkeypatch.setattr(_ops(), fn, never)
     lib = pkg('_lib').lib
-    for fn in ('srec_score_select', 'srec_score_select_biased', 'srec_score_items', 'srec_score_items_biased'):
+    for fn in ('srec_score_rank', 'srec_score_select', 'srec_score_sample', 'srec_score_items', 'srec_score_norm',
+               'srec_score_cutoff_hist', 'srec_score_cutoff_tail', 'srec_score_cutoff'):
         monkeypatch.setitem(lib.__dict__, fn, never)
     ok = torch.zeros(V, device=dev)
     nan, pinf = ok.clone(), ok.clone()

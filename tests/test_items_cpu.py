@@ -8,6 +8,7 @@ import sys
 import pytest
 import torch
 
+import served_abi
 from items_oracle import drop_mask, items64, order64
 from util import ROOT, pkg
 
@@ -50,17 +51,16 @@ def test_oracle_order_by_value_then_id_with_unfilled_slots_last():
 
 
 # ------------------------------------------------------------------------------------------- C ABI
-NAMES = ['sr', 'ld_sr', 'comp_stride', 'E', 'ld_e', 'cs', 'off_ex', 'off_in', 'listed', 'L', 'listed_mode', 'items', 'ld_items',
-         'M', 'id_lo', 'B', 'V', 'd', 'C', 'out', 'stream']
+REST = ['items', 'ld_items', 'M', 'out', 'stream']               # what follows the descriptor
 
 
 def test_header_declares_score_items_and_the_library_exports_it():
     L = pkg('_lib')
-    assert [n for _, n in L.lib.protos['srec_score_items']] == NAMES
-    types = dict((n, t) for t, n in L.lib.protos['srec_score_items'])
-    assert types['items'] == 'const int*' and types['ld_items'] == 'long' and types['id_lo'] == 'long' and types['out'] == 'float*'
+    assert L.lib.protos['srec_score_items'] == [('const void*', 'served'), ('const int*', 'items'), ('long', 'ld_items'), ('int', 'M'),
+                                                ('float*', 'out'), ('void*', 'stream')]
+    assert L.STRUCTS['srec_served']._fields_ == served_abi.MEMBERS          # (id_lo among them, a long)
     dll = L.lib.load()                                  # binds every declared symbol: a missing export raises here
-    assert len(dll.srec_score_items.argtypes) == len(NAMES)
+    assert len(dll.srec_score_items.argtypes) == 1 + len(REST)
     assert callable(pkg('ops').score_items) and pkg('ops').score_items is pkg('score').score_items
 
 
@@ -74,8 +74,9 @@ def test_c_entry_refuses_bad_arguments_without_a_launch():
            dict(L=65, listed=0x5000), dict(M=0), dict(id_lo=-1), dict(ld_items=3), dict(listed_mode=2), dict(items=None),
            dict(out=None), dict(ld_e=30), dict(ld_sr=34)]
     for change in bad:
-        assert dll.srec_score_items(*[{**good, **change}[n] for n in NAMES]) == 1001, change
-    assert dll.srec_score_items(*[{**good, 'B': 0, 'd': 30}[n] for n in NAMES]) == 0          # no sessions: nothing to do
+        assert served_abi.call(dll.srec_score_items, REST, {**good, **change}) == 1001, change
+    assert served_abi.call(dll.srec_score_items, REST, {**good, 'B': 0, 'd': 30}) == 0        # no sessions: nothing to do
+    assert served_abi.call(dll.srec_score_items, REST, good, null=True) == 1001               # no descriptor
 
 
 # ------------------------------------------------------------------------------------------- ops.score_items, before the library

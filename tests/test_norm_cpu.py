@@ -1,6 +1,6 @@
 """CPU half of the renormalisation of the served scores: the float64 oracle (tests/norm_oracle.py) against a brute-force
 loop and its -inf rules, the argument checks of ops.score_norm on CPU tensors (pure torch ahead of any launch), the C ABI of
-srec_score_norm / srec_score_norm_ws (declared in the order of srec_score_select_biased, exported, bad arguments refused
+srec_score_norm / srec_score_norm_ws (declared with the descriptor of srec_score_select, exported, bad arguments refused
 without a launch), dist.lse_fold, and --renormalize of the two launchers."""
 import math
 import os
@@ -9,6 +9,7 @@ import sys
 import pytest
 import torch
 
+import served_abi
 from item_bias_oracle import NINF, exact_bias
 from norm_oracle import eligible, lse_pair64, norm64
 from select_oracle import drop_mask
@@ -101,21 +102,18 @@ def test_score_norm_refuses_bad_arguments_on_cpu_tensors():
 
 
 # ------------------------------------------------------------------------------------------- C ABI
-HEAD = ['sr', 'ld_sr', 'comp_stride', 'E', 'ld_e', 'cs', 'off_ex', 'off_in', 'listed', 'L', 'listed_mode', 'id_lo', 'B', 'V', 'd', 'C']
-BIAS = [('const float*', 'bias'), ('long', 'ld_bias'), ('const int*', 'group'), ('int', 'G')]
 TAIL = [('float*', 'out'), ('void*', 'ws'), ('void*', 'stream')]
 
 
 def test_header_declares_both_entry_points():
     L = pkg('_lib')
     protos = L.parse_header()
-    sel = protos['srec_score_select_biased']
-    assert [n for _, n in sel[:len(HEAD) + 1]] == HEAD + ['K']
-    # the order of srec_score_select_biased, minus K, val and idx, plus out
-    assert protos['srec_score_norm'] == sel[:len(HEAD)] + BIAS + TAIL
+    # the descriptor srec_score_select takes, then out where that call has K, floor, val and idx
+    assert protos['srec_score_norm'] == protos['srec_score_select'][:1] + TAIL == [('const void*', 'served')] + TAIL
+    assert L.STRUCTS['srec_served']._fields_ == served_abi.MEMBERS
     assert protos['srec_score_norm_ws'] == [('int', 'B'), ('int', 'V'), ('int', 'd'), ('int', 'C'), ('int', 'L'), ('long*', 'bytes')]
     dll = L.lib.load()                                  # binds every declared symbol: a missing export raises here
-    assert len(dll.srec_score_norm.argtypes) == len(HEAD) + 7
+    assert len(dll.srec_score_norm.argtypes) == 4
 
 
 def test_c_entries_refuse_bad_arguments_without_a_launch():
@@ -124,12 +122,13 @@ def test_c_entries_refuse_bad_arguments_without_a_launch():
     good = dict(sr=0x1000, ld_sr=32, comp_stride=0, E=0x2000, ld_e=32, cs=None, off_ex=None, off_in=None, listed=None, L=0,
                 listed_mode=0, id_lo=0, B=2, V=10, d=32, C=1, bias=0x6000, ld_bias=10, group=0x7000, G=3, out=0x4000, ws=0x8000,
                 stream=None)
-    names = HEAD + [n for _, n in BIAS + TAIL]
+    rest = [n for _, n in TAIL]
     for change in (dict(G=0), dict(group=None), dict(ld_bias=9), dict(bias=0x6002), dict(group=0x7001), dict(d=30), dict(d=1028),
                    dict(C=5), dict(C=0), dict(L=65), dict(listed_mode=2), dict(out=None), dict(ws=None), dict(id_lo=-1),
                    dict(id_lo=2 ** 31 - 5), dict(E=0x2004), dict(ld_e=30), dict(bias=None, group=None, G=2)):
-        assert dll.srec_score_norm(*[{**good, **change}[n] for n in names]) == 1001, change
-    assert dll.srec_score_norm(*[{**good, 'B': 0, 'G': 0}[n] for n in names]) == 0          # no sessions: nothing to do
+        assert served_abi.call(dll.srec_score_norm, rest, {**good, **change}) == 1001, change
+    assert served_abi.call(dll.srec_score_norm, rest, {**good, 'B': 0, 'G': 0}) == 0        # no sessions: nothing to do
+    assert served_abi.call(dll.srec_score_norm, rest, good, null=True) == 1001              # no descriptor
     n = ctypes.c_long(-1)
     assert dll.srec_score_norm_ws(512, 37484, 256, 3, 20, ctypes.addressof(n)) == 0 and n.value > 0 and n.value % 8 == 0
     small = ctypes.c_long(-1)

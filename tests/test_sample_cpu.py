@@ -1,6 +1,6 @@
 """CPU half of drawing from the served distribution: the oracle's noise (tests/sample_oracle.py) against the library's host
 restatement srec_sample_uniform and against ops.sample_noise, bit for bit; the C ABI of srec_score_sample (declared in the
-order of srec_score_select_biased, exported, bad arguments refused without a launch); the argument checks of
+order of srec_score_select, exported, bad arguments refused without a launch); the argument checks of
 ops.score_sample and model.sample on CPU tensors; the launcher's flags; and the yardstick itself - the oracle's own draws
 pass the statistical cases of tests/test_sample_gpu.py at their thresholds, and the seeds chosen there leave lists that
 round-off cannot reorder."""
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import sample_oracle as so
+import served_abi
 from select_oracle import window_count
 from util import ROOT, pkg
 
@@ -105,25 +106,25 @@ def test_ops_sample_noise_equals_the_oracle_exactly(seed):
 
 
 # ------------------------------------------------------------------------------------------- C ABI
-HEAD = ['sr', 'ld_sr', 'comp_stride', 'E', 'ld_e', 'cs', 'off_ex', 'off_in', 'listed', 'L', 'listed_mode', 'id_lo', 'B', 'V', 'd', 'C', 'K']
-BIAS = [('const float*', 'bias'), ('long', 'ld_bias'), ('const int*', 'group'), ('int', 'G')]
+HEAD = [('const void*', 'served'), ('int', 'K')]
 NOISE = [('float', 'inv_temperature'), ('unsigned long long', 'seed'), ('const int*', 'session_keys')]
-TAIL = [('float*', 'out_key'), ('int*', 'out_idx'), ('void*', 'ws'), ('void*', 'stream')]
+TAIL = [('const float*', 'floor'), ('float*', 'out_key'), ('int*', 'out_idx'), ('void*', 'ws'), ('void*', 'stream')]
 
 
 def test_header_declares_the_entry_points_in_the_order_of_select_biased():
+    """srec_score_select with the noise operands between K and floor"""
     L = pkg('_lib')
     protos = L.parse_header()
-    sel = protos['srec_score_select_biased']
-    n = len(HEAD) + len(BIAS)
-    assert [a for _, a in sel[:len(HEAD)]] == HEAD and sel[len(HEAD):n] == BIAS
-    assert protos['srec_score_sample'] == sel[:n] + NOISE + TAIL
+    sel = protos['srec_score_select']
+    n = len(HEAD)
+    assert sel[:n] == HEAD and L.STRUCTS['srec_served']._fields_ == served_abi.MEMBERS
+    assert protos['srec_score_sample'] == HEAD + NOISE + TAIL
     assert [t for t, _ in sel[n:]] == [t for t, _ in TAIL]
     assert protos['srec_score_sample_ws'] == protos['srec_score_select_ws']
     assert protos['srec_sample_uniform'] == [('unsigned long long', 'seed'), ('const int*', 'session_keys'), ('int', 'n_b'),
                                              ('const int*', 'ids'), ('int', 'n_v'), ('unsigned*', 'h_out'), ('float*', 'w_out')]
     dll = L.lib.load()                                  # binds every declared symbol: a missing export raises here
-    assert len(dll.srec_score_sample.argtypes) == n + 7
+    assert len(dll.srec_score_sample.argtypes) == n + len(NOISE) + len(TAIL)
     assert dll.srec_score_sample.argtypes[n:n + 2] == [ctypes.c_float, ctypes.c_ulonglong]
 
 
@@ -131,17 +132,20 @@ def test_c_entry_refuses_bad_arguments_without_a_launch():
     dll = pkg('_lib').lib.load()
     good = dict(sr=0x1000, ld_sr=32, comp_stride=0, E=0x2000, ld_e=32, cs=None, off_ex=None, off_in=None, listed=None, L=0,
                 listed_mode=0, id_lo=0, B=2, V=10, d=32, C=1, K=5, bias=0x6000, ld_bias=10, group=0x7000, G=3, inv_temperature=1.0,
-                seed=7, session_keys=0x9000, out_key=0x4000, out_idx=0x5000, ws=0x8000, stream=None)
-    names = HEAD + [a for _, a in BIAS + NOISE + TAIL]
+                seed=7, session_keys=0x9000, floor=None, out_key=0x4000, out_idx=0x5000, ws=0x8000, stream=None)
+    rest = [a for _, a in HEAD[1:] + NOISE + TAIL]
     inf = float('inf')
     for change in (dict(K=129), dict(K=0), dict(inv_temperature=0.0), dict(inv_temperature=-1.0), dict(inv_temperature=inf),
                    dict(inv_temperature=float('nan')), dict(session_keys=0x9002),
-                   # ... and everything srec_score_select_biased refuses
+                   dict(floor=0xa002),
+                   # ... and everything srec_score_select refuses
                    dict(G=0), dict(group=None), dict(ld_bias=9), dict(bias=0x6002), dict(group=0x7001), dict(d=30), dict(d=1028),
                    dict(C=5), dict(C=0), dict(L=65), dict(listed_mode=2), dict(out_key=None), dict(out_idx=None), dict(ws=None),
                    dict(id_lo=-1), dict(id_lo=2 ** 31 - 5), dict(E=0x2004), dict(ld_e=30), dict(bias=None, group=None, G=2)):
-        assert dll.srec_score_sample(*[{**good, **change}[n] for n in names]) == 1001, change
-    assert dll.srec_score_sample(*[{**good, 'B': 0}[n] for n in names]) == 0                # no sessions: nothing to do
+        assert served_abi.call(dll.srec_score_sample, rest, {**good, **change}) == 1001, change
+        assert served_abi.call(dll.srec_score_sample, rest, {**good, 'floor': 0xa000, **change}) == 1001, change   # (was _floor)
+    assert served_abi.call(dll.srec_score_sample, rest, {**good, 'B': 0}) == 0              # no sessions: nothing to do
+    assert served_abi.call(dll.srec_score_sample, rest, good, null=True) == 1001            # no descriptor
     n, m = ctypes.c_long(-1), ctypes.c_long(-2)
     assert dll.srec_score_sample_ws(512, 37484, 256, 3, 20, 100, ctypes.addressof(n)) == 0 and n.value > 0
     assert dll.srec_score_select_ws(512, 37484, 256, 3, 20, 100, ctypes.addressof(m)) == 0 and m.value == n.value

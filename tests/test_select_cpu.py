@@ -8,6 +8,7 @@ import sys
 import pytest
 import torch
 
+import served_abi
 from select_oracle import drop_mask, merge_lists, select64
 from util import GOLDEN, ROOT, pkg
 
@@ -59,12 +60,12 @@ def test_header_declares_both_functions_and_the_library_binds_them():
     L = pkg('_lib')
     protos = L.lib.protos
     assert [t for t, _ in protos['srec_score_select_ws']] == ['int'] * 6 + ['long*']
-    names = [n for _, n in protos['srec_score_select']]
-    assert names == ['sr', 'ld_sr', 'comp_stride', 'E', 'ld_e', 'cs', 'off_ex', 'off_in', 'listed', 'L', 'listed_mode', 'id_lo',
-                     'B', 'V', 'd', 'C', 'K', 'out_val', 'out_idx', 'ws', 'stream']
+    assert protos['srec_score_select'] == [('const void*', 'served'), ('int', 'K'), ('const float*', 'floor'), ('float*', 'out_val'),
+                                           ('int*', 'out_idx'), ('void*', 'ws'), ('void*', 'stream')]
+    assert L.STRUCTS['srec_served']._fields_ == served_abi.MEMBERS      # the operands ahead of K, in the order they always had
     assert L.CONST['SREC_SELECT_MAXK'] == 128 and L.CONST['SREC_LISTED_SCORE'] == 0 and L.CONST['SREC_LISTED_DROP'] == 1
     dll = L.lib.load()                                  # binds every declared symbol: a missing export raises here
-    assert len(dll.srec_score_select.argtypes) == 21 and len(dll.srec_score_select_ws.argtypes) == 7
+    assert len(dll.srec_score_select.argtypes) == 7 and len(dll.srec_score_select_ws.argtypes) == 7
 
 
 def test_score_select_refuses_bad_arguments_before_any_gpu_call():

@@ -29,12 +29,10 @@ def pieces(ops, sc, L, srs, E, cs, off_ex, listed, drop, bias, group):
     """{row name: callable} of the single launches of one score_cutoff(top_k, top_p) call, each on the state the call itself
     would hand it (the passes are run once, the state ahead of every pass is kept)"""
     k_, p_, gap, inv_t = ops.cutoff_scalars('timing', TOP_K, TOP_P, None, T)
-    a = sc._mixture_args('score_cutoff', srs, E, off_ex, None, listed)
-    bi = sc._bias_args('score_cutoff', bias, group, a.B, a.V)
+    a = sc._served_args('score_cutoff', srs, E, cs, off_ex, None, listed, drop, 0, bias, group)
     B, dev = a.B, a.srs.device
-    head = (L.ptr(a.srs), a.ld_sr, a.comp, L.ptr(a.table), a.table.stride(0), L.ptr(cs), L.ptr(a.off_ex), L.ptr(a.off_in),
-            L.ptr(a.listed), a.L, sc._listed_mode(drop), 0, B, a.V, a.d, a.C)
-    tail = (L.ptr(bi.bias), bi.ld_bias, L.ptr(bi.group), bi.G)
+    desc = a.struct()
+    served = ctypes.addressof(desc)
     lib, st = L.lib, L.stream
     n = ctypes.c_long()
     lib.srec_score_select_ws(B, a.V, a.d, a.C, a.L, 1, ctypes.addressof(n))
@@ -46,23 +44,23 @@ def pieces(ops, sc, L, srs, E, cs, off_ex, listed, drop, bias, group):
     lk = torch.empty(B, device=dev)
     hist = torch.zeros(B, 3, 256, device=dev, dtype=torch.int64)
     state = torch.zeros(B, 8, device=dev, dtype=torch.int64)
-    lib.srec_score_select_biased(*head, 1, *tail, L.ptr(top), L.ptr(ids), L.ptr(ws), st())
+    lib.srec_score_select(served, 1, None, L.ptr(top), L.ptr(ids), L.ptr(ws), st())
     before, hists = [], []
     for j in range(4):
         before.append(state.clone())
-        lib.srec_score_cutoff_hist(*head, *tail, inv_t, k_, p_, j, L.ptr(top), L.ptr(state), L.ptr(hist), st())
+        lib.srec_score_cutoff_hist(served, inv_t, k_, p_, j, L.ptr(top), L.ptr(state), L.ptr(hist), st())
         hists.append(hist.clone())
         lib.srec_score_cutoff_advance(B, j, k_, p_, gap, L.ptr(hist), L.ptr(state), L.ptr(top), L.ptr(floor), st())
     scratch = torch.zeros_like(state)
-    keep = (a, bi, cs, ws, before, hists)                  # the operands behind the pointers
+    keep = (a, desc, ws, before, hists)                    # the operands behind the pointers
 
     def hist_pass(j, k, p):
-        return lambda: lib.srec_score_cutoff_hist(*head, *tail, inv_t, k, p, j, L.ptr(top), L.ptr(before[j]), L.ptr(hist), st())
+        return lambda: lib.srec_score_cutoff_hist(served, inv_t, k, p, j, L.ptr(top), L.ptr(before[j]), L.ptr(hist), st())
 
     def advance():
         scratch.copy_(before[1])
         lib.srec_score_cutoff_advance(B, 1, k_, p_, gap, L.ptr(hists[1]), L.ptr(scratch), L.ptr(top), L.ptr(floor), st())
-    fns = {'maximum (K = 1 selection)': lambda: lib.srec_score_select_biased(*head, 1, *tail, L.ptr(top), L.ptr(ids), L.ptr(ws), st())}
+    fns = {'maximum (K = 1 selection)': lambda: lib.srec_score_select(served, 1, None, L.ptr(top), L.ptr(ids), L.ptr(ws), st())}
     for j in range(4):
         fns['histogram pass %d, top_k + top_p' % j] = hist_pass(j, k_, p_)
     for j in range(4):
@@ -70,7 +68,7 @@ def pieces(ops, sc, L, srs, E, cs, off_ex, listed, drop, bias, group):
     for j in range(4):
         fns['histogram pass %d, top_k alone' % j] = hist_pass(j, k_, 1.0)
     fns['advance step (with a 4 KB state copy)'] = advance
-    fns['tail pass'] = lambda: lib.srec_score_cutoff_tail(*head, *tail, inv_t, L.ptr(top), L.ptr(floor), L.ptr(hist), st())
+    fns['tail pass'] = lambda: lib.srec_score_cutoff_tail(served, inv_t, L.ptr(top), L.ptr(floor), L.ptr(hist), st())
     fns['finish step'] = lambda: lib.srec_score_cutoff_finish(B, L.ptr(hist), L.ptr(count), L.ptr(lk), st())
     return fns, keep
 
