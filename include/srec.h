@@ -703,6 +703,36 @@ int srec_score_cutoff_finish(int B, const long long* hist, int* count, float* lo
 int srec_score_cutoff(const void* served, float inv_temperature, int top_k, float top_p, float min_gap, float* floor,
                       int* count, float* log_kept, float* top, void* ws, void* stream);
 
+/* ---- serving: top-N lists BEYOND SREC_SELECT_MAXK - collect what the cutoff keeps, then order it (select_many.hip) ---------
+ * The K best eligible items per session under the biased served score for 1 <= K <= SREC_SELECT_MANY_MAXK, the contract of
+ * srec_score_select (descending values, ties towards the lower id, (-INFINITY, -1) once the eligible rows run out), without
+ * the (B, V) matrix and without a running list in LDS.  floor = the floor of srec_score_cutoff(top_k = K) at temperature 1
+ * over the same descriptor (over the WHOLE catalogue for a row shard), whose count[b] is exactly the number of pairs the
+ * collect pass finds for session b: both form s' through the same tile product.  count exceeds K only by rows that tie with
+ * the K-th.  An eligible row that merely scores -INFINITY is collected (and counted) only under floor = -INFINITY, i.e. when
+ * the session has fewer than K eligible rows; it then precedes the unfilled slots with value -INFINITY and its own id.
+ * srec_score_select_many_collect: one pass over the table.  Every eligible (session b, row v) pair with !(s'[b,v] < floor[b])
+ *   - the test of srec_score_select's floor - is appended as (s', id_lo + v) to row b of buf_val (fp32) / buf_idx (int32),
+ *   both [B, cap]; n int32 [B] is ZEROED here and counts the pairs with integer atomics, one returned atomic per (workgroup,
+ *   session, 128-item chunk) that has any.  A pair whose slot would be >= cap is counted and not written: n[b] > cap tells the
+ *   caller that the row is incomplete.  The ORDER inside a row is arrival order and means nothing; the SET is a pure function
+ *   of the inputs.  No float atomics.
+ * srec_score_select_many_order: no table access, one workgroup per session.  Sorts the first min(n[b], cap) pairs of row b by
+ *   (value descending, id ascending) - distinct keys, so the output is a pure function of the set - and writes the first K
+ *   to out_val / out_idx [B, K], (-INFINITY, -1) behind them.  Values come back as s' + 0.0f (-0.0 is canonicalised, as in
+ *   srec_score_cutoff).  cap <= SREC_SELECT_MANY_SORT pairs (64 KB of 64-bit keys in LDS); a caller with more pairs in a row
+ *   (more than SORT - K rows tie with the K-th) orders the buffer by other means.
+ * The lists of disjoint row shards - every shard with its id_lo, the floor of the whole catalogue - merge by (value, id) to the
+ * bits of the single-device call.  Both return SREC_BAD_ARG and do not launch for: (collect) the descriptor's reasons, cap < 1,
+ * a NULL or misaligned floor / buffer / n; (order) K outside 1 .. SREC_SELECT_MANY_MAXK, cap < 1, cap > SREC_SELECT_MANY_SORT,
+ * a NULL or misaligned n / buffer / output.  No workspace. */
+#define SREC_SELECT_MANY_MAXK 4096
+#define SREC_SELECT_MANY_SORT 8192
+int srec_score_select_many_collect(const void* served, const float* floor, int cap, float* buf_val, int* buf_idx, int* n,
+                                   void* stream);
+int srec_score_select_many_order(int B, int cap, const int* n, const float* buf_val, const int* buf_idx, int K, float* out_val,
+                                 int* out_idx, void* stream);
+
 /* ---- serving: diversified top-N - greedy MMR re-rank of a pool, and intra-list diversity (diversify.hip) ------------------
  * Per session a pool of M slots; slot i has a row index row[b * M + i] into the row source X (fp32, n_rows rows of d columns,
  * leading dimension ld_x) and a value s[b * M + i].  A slot whose row index is < 0 or >= n_rows is UNFILLED: X is never read

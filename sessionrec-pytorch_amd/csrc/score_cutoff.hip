@@ -25,6 +25,7 @@
 // would be 195.5 KB), else the tiles are
 // read through the cache.  The tail keeps 2 bins per session: 768 bytes.
 #include "common.h"
+#include "score_key.h"
 #include "score_pass.h"
 
 namespace {
@@ -51,14 +52,7 @@ struct CutArgs : PassArgs {
     u64* hist;                      // [B][3][NBIN]
 };
 
-// s + 0.0f (-0.0 -> +0.0) as a key whose unsigned order is the order of the floats (no NaN)
-__device__ __forceinline__ unsigned key_of(float s) {
-    const unsigned u = __float_as_uint(s + 0.f);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float score_of(unsigned key) {
-    return __uint_as_float((key >> 31) ? key ^ 0x80000000u : ~key);
-}
+// key_of / score_of: score_key.h (s + 0.0f as a key whose unsigned order is the order of the floats)
 // the fixed-point weight of a score under the session's maximum m (m == -inf: every weight is 0, never exp(nan))
 __device__ __forceinline__ u64 weight_of(float s, float m, float inv_t) {
     if (m == -INFINITY) return 0ull;

@@ -421,6 +421,13 @@ class HipLocal:
         ([B], the sessions' cutoff) only when there is one"""
         return self.ops.score_select(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
+    def select_many(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, floor, cap, **bias):
+        """this shard's k best rows (values, global ids) of ops.score_select_many, 128 < k <= 4096 included: rows
+        [id_lo, id_lo + n) of the catalog at or above floor ([B]: the k-th best score over the WHOLE catalogue, cutoff()'s),
+        cap = the largest of cutoff()'s counts.  bias: as in select()"""
+        return self.ops.score_select_many(srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, floor=floor, cap=cap,
+                                          **bias)
+
     def sample(self, srs, table, cs, k, off_ex, off_in, listed, drop_listed, id_lo, temperature, seed, session_keys, **bias):
         """this shard's k best sampled keys (keys, global ids) of ops.score_sample: rows [id_lo, id_lo + n) of the catalog.
         session_keys: one integer per session (the noise is a function of the key, never of the row).  bias: as in select()"""
@@ -909,6 +916,26 @@ class VocabParallel:
         of this rank's sessions, what cutoff() returned): ops.score_select's; under data_parallel it travels with the sessions."""
         return self._serve(lambda tab, mix, fl, **b: self.local.select(*tab, k, *mix, drop_listed, self.lo, **b, **self._floor_kw(fl)),
                            srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group, extra=floor,
+                           neutral=self._no_lists(k), combine=self._merge_lists)
+
+    def select_many(self, srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
+                    bias=None, group=None):
+        """select() beyond 128 items (ops.score_select_many's contract, 1 <= k <= 4096): cutoff(top_k=k) gives every rank the
+        same floor - the k-th best score over the whole catalogue - and the same counts, so the buffer size needs no
+        collective of its own; every rank then collects and orders the rows at or above the floor among its own LIVE rows
+        with its id_lo, and select()'s merge (ONE all-gather of the pairs) orders the ranks' lists: the single-device
+        call's result, bit for bit.  A rank without live rows joins the cutoff's collectives and contributes unfilled lists.
+        data_parallel: floor and count travel with the sessions (one all-gather of a [B, 2] tensor), as select()'s floor does;
+        the largest count is read on the host (the one device-to-host read of ops.score_select_many)."""
+        floor, count, _, _ = self.cutoff(srs, table, cs, off_ex, off_in, listed, drop_listed, data_parallel, bias, group, top_k=k)
+        cut = torch.stack([floor.contiguous().view(torch.int32), count.to(torch.int32)], 1)       # [B, 2]: one tensor to gather
+
+        def entry(tab, mix, fc, **b):
+            fl, cap = fc[:, 0].contiguous().view(torch.float32), int(fc[:, 1].max()) if fc.shape[0] else 0
+            if cap < 1:                                            # nothing eligible in any session
+                return self._no_lists(k)(fc.shape[0], fc.device)
+            return self.local.select_many(*tab, k, *mix, drop_listed, self.lo, fl, cap, **b)
+        return self._serve(entry, srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group, extra=cut,
                            neutral=self._no_lists(k), combine=self._merge_lists)
 
     @staticmethod

@@ -227,6 +227,7 @@ class _ScoringMixin:
 
     # served call of dist.VocabParallel over a row-sharded table <-> (launcher of ops on one device, its own keywords)
     _ROUTES = {'target_rank': ('score_rank', {}), 'select': ('score_select', {}), 'sample': ('score_sample', {}),
+               'select_many': ('score_select_many', {}),
                'norm': ('score_norm', {}), 'cutoff': ('score_cutoff', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
                'score_items': ('score_items', {'checked': True})}   # (model.score_items looked; sample() passes the kernel's ids)
 
@@ -312,6 +313,24 @@ class _ScoringMixin:
         with _Serving(self):
             srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
             return self._select_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, **bias)
+
+    def recommend_many(self, *inputs, k, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
+        """(log_probs fp32 [B,k] descending, item_ids int32 [B,k]): recommend() beyond 128 items, 1 <= k <= 4096 - the candidate
+        stage of a two-stage set-up (rerank() / score_items() of a second model take lists of any length) and the export of
+        long lists.  Values, order, ties, (-inf, -1) slots and every keyword (exclude_seen, item_bias / item_group,
+        renormalize, mixtures, row-sharded tables) mean what they mean in recommend(); k and item_bias / item_group are
+        checked before anything of the model runs.  No (B, V) score matrix: the k-th best score of every session is found
+        by the radix search of cutoff(top_k=k), one more pass collects the items at or above it and one workgroup per
+        session orders them (csrc/select_many.hip; ops.score_select_many) - about seven passes over the table and ONE
+        device-to-host read (the largest count sizes the buffer).  For k <= 128 the call IS recommend(): the selection
+        kernel takes one pass over the table instead of seven (ops.score_select_many itself always takes the long route).
+        Runs in eval mode under torch.no_grad()."""
+        k = ops.select_many_k('recommend_many', k)
+        bias = self._item_bias('recommend_many', item_bias, item_group)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+            fn, kw = self._route('select' if k <= 128 else 'select_many')
+            return fn(srs, self._table(), cs, k, off_ex, off_in, listed, exclude_seen, **kw, **bias)
 
     def recommend_diverse(self, *inputs, k=20, diversity=0.5, pool=None, exclude_seen=False, item_bias=None, item_group=None,
                           renormalize=False):
