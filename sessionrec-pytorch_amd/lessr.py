@@ -115,8 +115,19 @@ class LESSR(_ScoringMixin, nn.Module):
         self.fc_sr = nn.Linear(input_dim, embedding_dim, bias=False)
         self._max_norm = 1.0
 
+    def check_widths(self):
+        """layer i concatenates its output to its input, so the EOPA layer i reads (i + 1) x embedding_dim columns and its
+        GRU over the in-edges keeps that many per node in LDS: a model beyond the kernel's width is refused here, on the
+        host and ahead of the first launch, instead of failing with a bad-argument status in the middle of a forward"""
+        for i, layer in enumerate(self.layers):
+            if isinstance(layer, EOPA) and layer.gru.hidden_size > ops.GRU_SEQ_MAXD:
+                raise ValueError('EOPA layer %d of this LESSR reads %d columns (embedding_dim x %d); the GRU over a node\'s '
+                                 'in-edges holds at most %d (MAXD, csrc/gruseq.hip): lower embedding_dim or num_layers'
+                                 % (i, layer.gru.hidden_size, i + 1, ops.GRU_SEQ_MAXD))
+
     def session_repr(self, mg, sg=None, tgrad=None):
         from ._lib import lib, ptr, stream
+        self.check_widths()
         W = self.embedding.weight
         if not self._take_prepared(self.__dict__.get('_srec_state'))[0]:   # (FusedAdam's row pass left the rows renormalised)
             with torch.no_grad():                # Embedding(max_norm=1): in-place renorm before the lookup

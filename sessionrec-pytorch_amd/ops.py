@@ -1324,6 +1324,9 @@ def prelu(x, a, dyn=None):
     return PReLU.apply(x, a, dyn)
 
 
+GRU_SEQ_MAXD = 256      # MAXD of csrc/gruseq.hip: the hidden state and the three gate rows of one node live in LDS
+
+
 class GRUSeq(torch.autograd.Function):
     """EOPA: last hidden state of a GRU run over each node's in-neighbours in edge-id order.
     GI = ft W_ih^T + b_ih (per source node); graph = (in_ptr, in_idx, out_ptr, out_idx, esrc, edst)."""

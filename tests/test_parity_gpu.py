@@ -26,7 +26,7 @@ def _pair(kind, V, d, K=3, **kw):
         model = sp.MSGIFSR(V, 'x', d, 1, order=K, extra=False, fusion=False, **kw)
         fn, ofn = c.collate_fn_factory_ccs((c.seq_to_ccs_graph,), K), oc.collate_fn_factory_ccs((oc.seq_to_ccs_graph,), K)
     elif kind == 'lessr':
-        ref, model = om.LESSR(V, d, 2), sp.LESSR(V, d, 2)
+        ref, model = om.LESSR(V, d, kw.get('num_layers', 2)), sp.LESSR(V, d, kw.get('num_layers', 2))
         fn = c.collate_fn_factory(c.seq_to_eop_multigraph, c.seq_to_shortcut_graph)
         ofn = oc.collate_fn_factory(oc.seq_to_eop_multigraph, oc.seq_to_shortcut_graph)
     else:
@@ -133,6 +133,50 @@ def test_oversized_sessions_are_refused_not_truncated(dev):
     # the same sessions inside the budgets run (and match the oracle)
     model, ref, fn, ofn = _pair('msgifsr', V, d)
     _step_vs_oracle(dev, model, ref, fn, ofn, [(list(range(80)), 3), ([1, 2, 3], 4)], 'msgifsr 80 clicks')
+
+
+def test_lessr_exactly_at_the_kernel_budgets_matches_the_oracle(dev):
+    """a batch AT the static budgets (the refusal test above stands one beyond them): one session of 256 distinct items - 256
+    read-out nodes in one seg_attn session and, through the self-loops of the shortcut graph, an SGAT in-degree of 256 - and
+    [a, b] x 128, whose EOP multigraph gives b 128 in-edges (the degree budget) and EOPA's GRU a chain of 128 steps"""
+    L = pkg('ops').limits()
+    V, d = 400, 32
+    model, ref, fn, ofn = _pair('lessr', V, d)
+    samples = [(list(range(100, 100 + L['nodes'])), 7), ([3, 4] * L['deg'], 5), ([5], 9), ([7, 7, 8, 7], 1)]
+    (mg, sg), _ = fn(samples)
+    assert mg.meta['max_nodes'] == L['nodes'] and sg.meta['max_deg'] == L['sgat_deg'] and mg.meta['max_deg'] == L['deg'], \
+        (mg.meta, sg.meta)
+    _step_vs_oracle(dev, model, ref, fn, ofn, samples, 'lessr at the budgets')
+
+
+@pytest.mark.parametrize('d', [64, 100])
+@pytest.mark.parametrize('kind', ['lessr', 'srgnn', 'niser'])
+def test_lessr_srgnn_niser_widths_match_the_oracle(dev, kind, d):
+    """every other test of these three models runs at d = 32 (half a wavefront in the per-node loops) or at C2's 96: 64 fills
+    the wavefront exactly, 100 is no multiple of 16 / 32 / 64 (LESSR's read-out then runs at h = 100, D = 300, its SGAT at
+    256-column trips of 200)"""
+    V = 400
+    model, ref, fn, ofn = _pair(kind, V, d)
+    samples = _long_sessions(12, V, 2, 20, 17) + [([5], 9), ([7, 7, 7, 7], 1)]
+    _step_vs_oracle(dev, model, ref, fn, ofn, samples, '%s d=%d' % (kind, d))
+
+
+def test_lessr_refuses_a_model_wider_than_the_gru_kernel(dev):
+    """LESSR with 3 layers at d = 100: the third layer is an EOPA on 300 columns, beyond the 256 the GRU-over-in-edges
+    kernels hold per node (csrc/gruseq.hip): a ValueError on the host ahead of the first launch, not a bad-argument status
+    from the middle of the forward; the same model at d = 64 (192 columns) runs and matches the oracle"""
+    V = 400
+    samples = _long_sessions(6, V, 2, 12, 19) + [([5], 9)]
+    model, ref, fn, ofn = _pair('lessr', V, 100, num_layers=3)
+    model = model.to(dev).train()
+    inputs, labels = fn(samples)
+    inputs, labels = [x.to(dev) for x in inputs], labels.to(dev)
+    with pytest.raises(ValueError, match=r'EOPA layer 2 of this LESSR reads 300 columns .* at most 256'):
+        model.fused_loss(*inputs, labels)
+    with pytest.raises(ValueError, match='at most 256'):
+        model(*inputs)
+    model, ref, fn, ofn = _pair('lessr', V, 64, num_layers=3)
+    _step_vs_oracle(dev, model, ref, fn, ofn, samples, 'lessr 3 layers d=64')
 
 
 @pytest.mark.parametrize('lens', [(1, 1, 1), (2, 2, 1, 2), (2, 3, 1), (1, 4)])
