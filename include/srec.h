@@ -733,6 +733,30 @@ int srec_score_select_many_collect(const void* served, const float* floor, int c
 int srec_score_select_many_order(int B, int cap, const int* n, const float* buf_val, const int* buf_idx, int K, float* out_val,
                                  int* out_idx, void* stream);
 
+/* ---- evaluation of what is SERVED: the eligible rows ahead of a given label under the biased served score (rank_served.hip) --
+ * The rank of the label among what a user is shown - under a bias, allow / deny lists, exclude-seen and a truncation floor -
+ * which srec_score_rank refuses to compute; srec_score_rank is unchanged.  No (B, V) tensor.
+ * labels [B] int32 global ids; target [B] fp32 = the label's biased served score, exactly what srec_score_items returns for it
+ * (bias included, -INFINITY for a dropped or out-of-catalogue item, shard results summed): an INPUT, there is no target pass.
+ * ahead[b] (int32 [B]) = the number of local rows v for which ALL of these hold:
+ *   (b, v) is ELIGIBLE (above);  id_lo + v != labels[b] - the label is left out by id, never by its score;
+ *   !(s'[b,v] < floor[b]) when floor != NULL - the floor of srec_score_cutoff, as srec_score_select tests it;
+ *   s'[b,v] > target[b], or s'[b,v] == target[b] and id_lo + v < labels[b] - ties towards the lower id, as everywhere.
+ * labels[b] < 0 writes 0.  ahead is WRITTEN, not accumulated (zeroed on the stream by the call).  Counts of disjoint row shards
+ * add up; a label another shard owns keeps its order relative to every local id (no global id is formed as an int, so ids
+ * need not fit one: the exemption of srec_score_rank).  SREC_LISTED_SCORE and SREC_LISTED_DROP are both resolved INSIDE the
+ * pass - no fix-up pass, so the count is exact for the scores the pass forms: with labels[b] = out_idx[b,j] and target[b] =
+ * out_val[b,j] of srec_score_select over the same operands, ahead[b] == j.  Whether the label itself could be shown is the
+ * CALLER's test (target == -INFINITY, or target < floor[b]): the count does not look at it.
+ * bias == NULL is the unbiased case; floor == NULL runs the same kernel instances as a floor of -INFINITY; a descriptor without
+ * a list (L == 0) runs instances with the list machinery compiled out - the same scores, the same counts.  Integer atomics
+ * only: the output is a pure function of the inputs.  ws: srec_score_ahead_ws() bytes (a token: nothing is kept there).
+ * Nonzero and no launch, beyond the descriptor's reasons: labels, target or ahead NULL; labels, target, floor or ahead not
+ * aligned to 4 bytes. */
+int srec_score_ahead_ws(int B, int V, int d, int C, int L, long* bytes);
+int srec_score_ahead(const void* served, const int* labels, const float* target, const float* floor, int* ahead, void* ws,
+                     void* stream);
+
 /* ---- serving: diversified top-N - greedy MMR re-rank of a pool, and intra-list diversity (diversify.hip) ------------------
  * Per session a pool of M slots; slot i has a row index row[b * M + i] into the row source X (fp32, n_rows rows of d columns,
  * leading dimension ld_x) and a value s[b * M + i].  A slot whose row index is < 0 or >= n_rows is UNFILLED: X is never read

@@ -450,6 +450,10 @@ class HipLocal:
         """this shard's log-normaliser of ops.score_norm: rows [id_lo, id_lo + n) of the catalog.  bias: as in select()"""
         return self.ops.score_norm(srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
+    def ahead(self, srs, table, cs, labels, target, off_ex, off_in, listed, drop_listed, id_lo, **bias):
+        """this shard's count of ops.score_ahead: the eligible rows of [id_lo, id_lo + n) ahead of (labels, target).  bias: as in select()"""
+        return self.ops.score_ahead(srs, table, cs, labels, target, off_ex, off_in, listed, drop_listed, id_lo, **bias)
+
     def diversify(self, X, row, val, k, diversity):
         """ops.diversify over rows the caller has bounded (checked): (val [B,k], pick [B,k], mmr [B,k], ild [B])"""
         return self.ops.diversify(X, row, val, k, diversity, checked=True)
@@ -1026,6 +1030,21 @@ class VocabParallel:
                            neutral=lambda B, dev: torch.zeros(B, M, device=dev, dtype=torch.float32),
                            # (-inf + 0 and -inf + -inf stay -inf: no slot is ever +inf)
                            combine=lambda out: all_reduce_sum(out, self.group))
+
+    def ahead(self, srs, table, cs, labels, target, off_ex=None, off_in=None, listed=None, drop_listed=False, data_parallel=False,
+              bias=None, group=None, floor=None):
+        """int32 [B]: the eligible items ahead of every session's label over the sharded table (ops.score_ahead's contract; the
+        arguments of select(); labels [B] global ids, target fp32 [B] the labels' served scores - what score_items() over the
+        sharded table returned at labels[:, None], the same on every rank; floor [B] or None: cutoff()'s).  The count is a SUM
+        over disjoint row ranges: every rank counts among its own LIVE rows with its id_lo and its columns of the bias (a rank
+        without live rows counts nothing), and ONE sum-all-reduce of B integers finishes it - the single-device result, bit for
+        bit.  data_parallel as in select(): labels, target and floor travel with the sessions."""
+        return self._serve(lambda tab, mix, ltf, **b: self.local.ahead(*tab, ltf[0], ltf[1], *mix, drop_listed, self.lo, **b,
+                                                                       **self._floor_kw(ltf[2])),
+                           srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group,
+                           extra=(labels.reshape(-1).to(torch.int64), target.reshape(-1), floor),
+                           neutral=lambda B, dev: torch.zeros(B, device=dev, dtype=torch.int32),
+                           combine=lambda n: all_reduce_sum(n, self.group))
 
     def diversify(self, table, ids, val, k, diversity, data_parallel=False):
         """the greedy MMR re-rank of ops.diversify over the sharded table (val [B,k], pick [B,k], mmr [B,k], ild [B]): ids

@@ -282,6 +282,7 @@ _LISTED_TOO_MANY = {
     'score_sample': 'score_sample: %d listed items per session; csrc/recommend.hip takes at most 64',
     'score_cutoff': 'score_cutoff: %d listed items per session; csrc/score_cutoff.hip takes at most 64',
     'score_select_many': 'score_select_many: %d listed items per session; csrc/select_many.hip takes at most 64',
+    'score_ahead': 'score_ahead: %d listed items per session; csrc/rank_served.hip takes at most 64',
 }
 _LISTED_TOO_MANY['cutoff_passes'] = _LISTED_TOO_MANY['score_cutoff']      # (score_cutoff's generator speaks of lists in its words)
 
@@ -488,6 +489,44 @@ def score_select(srs, table, cs, k, off_ex=None, off_in=None, listed=None, drop_
     # (no bias: bias NULL, G 1; no floor: NULL - the plain call, the same kernel instances)
     lib.srec_score_select(_ct.addressof(desc), k, ptr(floor), ptr(val), ptr(idx), ptr(ws), stream())
     return val, idx
+
+
+def score_ahead(srs, table, cs, labels, target, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None,
+                group=None, floor=None):
+    """int32 [B]: the number of ELIGIBLE rows of `table` that stand ahead of each session's label under the biased score s' of
+    score_select - the rank of the label among what is SERVED (a bias, allow / deny lists, exclude-seen, a truncation floor),
+    which score_rank refuses to compute - no (B, V) tensor (csrc/rank_served.hip: one pass, listed items resolved inside it,
+    integer atomics; equal bits on every call).  labels: [B] global item ids (< 0: 0); target: fp32 [B], the label's own s' -
+    what score_items returns at labels[:, None] with the same operands (summed over row shards).  A row counts when it is
+    eligible (not listed under drop_listed, bias > -inf), is not the label (by id), is not below floor[b] (floor: fp32 [B] or
+    None, score_cutoff's) and scores above target[b], or equal to it with a lower id - the tie rule of score_select, so with
+    (labels, target) = (ids[:, j], values[:, j]) of score_select over the same operands the result is j.  Whether the label
+    itself could be shown (target > -inf, target >= floor) is the caller's test: model.served_rank makes it.  Other arguments
+    as score_select; id_lo: global id of table row 0 - counts of disjoint row shards add up, a shard without rows gives 0."""
+    a = _served_args('score_ahead', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
+    B, dev = a.B, a.srs.device
+    labels = torch.as_tensor(labels).detach()
+    if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool or labels.numel() != B:
+        raise ValueError('score_ahead: labels must hold %d integer item ids (one per session), got %s %s'
+                         % (B, labels.dtype, tuple(labels.shape)))
+    target = torch.as_tensor(target).detach()
+    if not target.is_floating_point() or target.numel() != B:
+        raise ValueError('score_ahead: target must hold %d floating numbers (the labels\' scores), got %s %s'
+                         % (B, target.dtype, tuple(target.shape)))
+    floor = _floor_arg('score_ahead', floor, B, dev)
+    if B == 0 or a.V == 0:
+        return torch.zeros(B, device=dev, dtype=torch.int32)
+    if labels.dtype != torch.int32:         # (an id beyond int32 stays beyond every local row: the kernel clamps around them)
+        labels = labels.to(torch.int64).clamp(min=-1, max=2 ** 31 - 1).to(torch.int32)
+    labels = labels.to(dev).reshape(B).contiguous()
+    target = target.to(device=dev, dtype=torch.float32).reshape(B).contiguous()
+    # no scratch: the counts meet in integer atomics (srec_score_ahead_ws is a token); the call validates the shape up front
+    n = _ct.c_long()
+    lib.srec_score_ahead_ws(B, a.V, a.d, a.C, a.L, _ct.addressof(n))
+    out = torch.empty(B, device=dev, dtype=torch.int32)
+    desc = a.struct()
+    lib.srec_score_ahead(_ct.addressof(desc), ptr(labels), ptr(target), ptr(floor), ptr(out), None, stream())
+    return out
 
 
 def _seed_words(who, seed):

@@ -229,7 +229,8 @@ class _ScoringMixin:
     _ROUTES = {'target_rank': ('score_rank', {}), 'select': ('score_select', {}), 'sample': ('score_sample', {}),
                'select_many': ('score_select_many', {}),
                'norm': ('score_norm', {}), 'cutoff': ('score_cutoff', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
-               'score_items': ('score_items', {'checked': True})}   # (model.score_items looked; sample() passes the kernel's ids)
+               'score_items': ('score_items', {'checked': True}),   # (model.score_items looked; sample() passes the kernel's ids)
+               'ahead': ('score_ahead', {})}
 
     def _route(self, name):
         """(callable, its route keywords) of served call `name`: shard.<name> fed as evaluate() feeds the shard
@@ -526,6 +527,50 @@ class _ScoringMixin:
             _, ids = self._sample_of(srs, cs, k, off_ex, off_in, listed, exclude_seen, temperature, seed, session_keys, **cut,
                                      **bias)
             return self._items_of(srs, cs, ids, off_ex, off_in, listed, exclude_seen, **bias), ids
+
+    def served_rank(self, *inputs, labels, exclude_seen=False, item_bias=None, item_group=None, top_k=None, top_p=None, min_p=None,
+                    temperature=1.0):
+        """int32 [B]: the rank of every session's label among what is SERVED - the number of items recommend() / sample() could
+        return with the same keywords (not the session's own under exclude_seen, item_bias > -inf, inside the kept set of
+        top_k / top_p / min_p at `temperature`) that stand ahead of the label under recommend()'s order (log-probability plus
+        bias, ties towards the lower item id).  target_rank() is this number for the unfiltered model; every HR / MRR / NDCG @k
+        of what users are shown follows from it (train.metrics_from_served_ranks, train.evaluate_served).
+          -1: the session has no label (labels[b] < 0).
+          -2: the label could NOT have been shown: its served value is -inf - it is the session's own item under exclude_seen,
+              its item_bias is -inf, or it merely scores -inf, which counts as not shown by definition - or it lies below the
+              truncation floor.  A miss at every cutoff.
+          otherwise the count r >= 0: when r < k <= 128 the label sits at position r of recommend(k=k, same keywords).
+        The label's own value is what score_items() returns for it; one more fused pass over the table counts the eligible
+        items ahead of it (csrc/rank_served.hip; ops.score_ahead), listed items and the bias resolved inside the pass: no (B, V)
+        score matrix, sharded table included (one integer all-reduce).  Renormalising shifts a session's values by a constant
+        and cannot change a rank, so there is no renormalize keyword.  Runs in eval mode under torch.no_grad(); item_bias /
+        item_group, the labels (integers below num_items) and the truncation keywords are checked before anything of the
+        model runs (ValueError)."""
+        bias = self._item_bias('served_rank', item_bias, item_group)
+        n = self.shard.V if self.shard is not None else self._table().shape[0]
+        lab = torch.as_tensor(labels).detach()
+        if lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError('served_rank: labels must be an integer tensor (one item id per session), got %s' % lab.dtype)
+        lab = lab.reshape(-1).to(torch.int64)
+        if lab.numel() > 0 and int(lab.max()) >= n:
+            raise ValueError('served_rank: label %d; item ids are in [0, %d), or negative for a session without a label'
+                             % (int(lab.max()), n))
+        ops.cutoff_scalars('served_rank', top_k, top_p, min_p, temperature)
+        crit = self._cutoff_args('served_rank', top_k, top_p, min_p, temperature)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=False, **bias)
+            lab = lab.to(srs[0].device).clamp(min=-1)
+            if lab.numel() != srs[0].shape[0]:
+                raise ValueError('served_rank: %d labels for %d sessions' % (lab.numel(), srs[0].shape[0]))
+            target = self._items_of(srs, cs, lab[:, None], off_ex, off_in, listed, exclude_seen, **bias)[:, 0]
+            cut = {} if crit is None else dict(floor=self._cutoff_of(srs, cs, off_ex, off_in, listed, exclude_seen, crit, **bias)[0])
+            fn, kw = self._route('ahead')
+            ahead = fn(srs, self._table(), cs, lab.to(torch.int32), target, off_ex, off_in, listed, exclude_seen, **kw, **cut, **bias)
+            shown = target > float('-inf')
+            if cut:
+                shown = shown & ~(target < cut['floor'])           # (the kernels' own test of a floor)
+            out = torch.where(shown, ahead, torch.full_like(ahead, -2))
+            return torch.where(lab < 0, torch.full_like(ahead, -1), out)
 
     def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """fp32 [B, M]: the log-probability forward() returns at the given items of every session - full-catalog soft-max

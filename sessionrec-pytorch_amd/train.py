@@ -58,6 +58,104 @@ def ranks_from_scores(scores, labels):
     return th.where(lab >= 0, ahead.sum(1), th.full_like(lab, -1))
 
 
+def metrics_from_served_ranks(ranks, cutoffs):
+    """metrics_from_ranks for the ranks of model.served_rank: the same keys plus 'shown', the share of the labelled sessions
+    whose label COULD be shown (rank >= 0).  A rank of -2 (the label is filtered out: seen, denied, below the truncation
+    floor) is a miss at every cutoff and stays in the denominator; -1 (no label) is left out of both."""
+    r = th.as_tensor(ranks).detach().reshape(-1).to('cpu', th.float64)
+    r = r[r != -1]
+    n = max(int(r.numel()), 1)
+    shown = r >= 0
+    out = {}
+    for k in cutoffs:
+        k = int(k)
+        inside = shown & (r < k)
+        out['hit@%d' % k] = float(inside.sum()) / n
+        out['mrr@%d' % k] = float((1.0 / (r[inside] + 1.0)).sum()) / n
+        out['ndcg@%d' % k] = float((1.0 / th.log2(r[inside] + 2.0)).sum()) / n
+    out['shown'] = float(shown.sum()) / n
+    return out
+
+
+def served_ranks_from_scores(scores, labels, item_bias=None, item_group=None, seen=None, top_k=None, top_p=None, min_p=None,
+                             temperature=1.0):
+    """model.served_rank from a materialised (B, V) score matrix (a CPU model's forward()): int64 [B] with its -1 / -2
+    convention.  item_bias [V] or [G, V] (item_group [B]) is added to the scores, -inf = not in the catalogue; seen [B, L] item
+    ids (-1 = empty) are not eligible; top_k / top_p / min_p at `temperature` as model.cutoff() defines them, on the eligible
+    rows.  Ties go towards the lower id (ranks_from_scores)."""
+    ninf = float('-inf')
+    s = scores.double()
+    B, V = s.shape
+    elig = th.ones(B, V, dtype=th.bool, device=s.device)
+    if item_bias is not None:
+        b = item_bias.to(s.device).double()
+        b = b[item_group.to(s.device).long()] if (b.dim() == 2 and item_group is not None) else b.reshape(-1, V)
+        s = s + b
+        elig &= b != ninf
+    if seen is not None:
+        sl = seen.to(s.device).long()
+        drop = th.zeros(B, V + 1, dtype=th.bool, device=s.device)
+        drop.scatter_(1, th.where(sl < 0, th.full_like(sl, V), sl), True)
+        elig &= ~drop[:, :V]
+    lab = labels.to(s.device).long()
+    safe = lab.clamp(min=0)
+    t = s.gather(1, safe.unsqueeze(1))
+    shown = elig.gather(1, safe.unsqueeze(1)).squeeze(1) & (t.squeeze(1) > ninf)
+    if top_k is not None or top_p is not None or min_p is not None:
+        se = th.where(elig, s, th.full_like(s, ninf))
+        top = se.max(1, keepdim=True).values
+        floor = th.full((B, 1), ninf, dtype=th.float64, device=s.device)
+        srt = se.sort(1, descending=True).values
+        if top_k is not None:
+            kth = srt[:, int(top_k) - 1:int(top_k)] if int(top_k) <= V else floor
+            few = elig.sum(1, keepdim=True) < int(top_k)
+            floor = th.maximum(floor, th.where(few, th.full_like(kth, ninf), kth))
+        if top_p is not None and float(top_p) < 1.0:
+            w = th.where(srt > ninf, th.exp((srt - top) / float(temperature)), th.zeros_like(srt))
+            cum = w.cumsum(1)
+            first = (cum >= float(top_p) * cum[:, -1:]).double().argmax(1, keepdim=True)
+            floor = th.maximum(floor, srt.gather(1, first))
+        if min_p is not None:
+            import math
+            floor = th.maximum(floor, top + float(temperature) * math.log(float(min_p)))
+        elig &= ~(s < floor)
+        shown &= ~(t.squeeze(1) < floor.squeeze(1))
+    ids = th.arange(V, device=s.device).unsqueeze(0)
+    ahead = elig & (ids != safe.unsqueeze(1)) & ((s > t) | ((s == t) & (ids < safe.unsqueeze(1))))
+    r = th.where(shown, ahead.sum(1), th.full_like(lab, -2))
+    return th.where(lab >= 0, r, th.full_like(lab, -1))
+
+
+def evaluate_served(model, data_loader, device, cutoffs=(20,), **served):
+    """metrics_from_served_ranks over a data loader: HR / MRR / NDCG @cutoffs and 'shown' of what users are SHOWN - under
+    served = the keywords of model.served_rank (exclude_seen, item_bias, item_group, top_k, top_p, min_p, temperature).  On the
+    GPU every batch is model.served_rank (fused passes, no (B, V) tensor, sharded table included); a CPU model takes the
+    materialised route: forward() plus bias and masks, served_ranks_from_scores (exclude_seen then needs the model's
+    _session_items).  item_group, being per session, may be a callable (inputs, labels) -> [B] row ids.  With no keywords the
+    metrics are those of evaluate(method='rank', cutoffs=cutoffs).  evaluate() is unchanged."""
+    model.eval()
+    group_of = served.get('item_group')
+    ranks = []
+    with th.no_grad():
+        for batch in data_loader:
+            inputs, labels = prepare_batch(batch, device)
+            kw = dict(served)
+            if callable(group_of):
+                kw['item_group'] = group_of(inputs, labels)
+            if hasattr(model, 'served_rank') and labels.is_cuda:
+                r = model.served_rank(*inputs, labels=labels, **kw)
+            else:
+                seen = None
+                if kw.pop('exclude_seen', False):
+                    if not hasattr(model, '_session_items'):
+                        raise ValueError('evaluate_served: exclude_seen on the materialised route needs model._session_items')
+                    seen = model._session_items(inputs[0])
+                r = served_ranks_from_scores(model(*inputs), labels, seen=seen, **kw)
+            ranks.append(r.long().cpu())
+    ranks = th.cat(ranks) if ranks else th.zeros(0, dtype=th.long)
+    return metrics_from_served_ranks(ranks, [int(k) for k in cutoffs])
+
+
 def evaluate(model, data_loader, device, cutoff=20, method='topk', cutoffs=None):
     """(MRR@cutoff, HR@cutoff) as the reference (train.py:36-55).  method='rank': from the label's rank among ALL items
     (model.target_rank on the GPU: one fused pass, no (B, V) tensor, mixtures of soft-maxes included; a CPU model's
