@@ -757,6 +757,31 @@ int srec_score_ahead_ws(int B, int V, int d, int C, int L, long* bytes);
 int srec_score_ahead(const void* served, const int* labels, const float* target, const float* floor, int* ahead, void* ws,
                      void* stream);
 
+/* ---- ... for M given items per session in ONE pass: where several targets stand among what is served (rank_served_many.hip) --
+ * Rest-of-session evaluation (every remaining item of a session is relevant) and "where would these items land?".
+ * items [B, M] int32 global ids, row stride ld_items; an entry < 0 is an EMPTY slot; every id appears at most once per row.
+ * target [B, M] fp32, row stride ld_items: the items' own served values s' - what srec_score_items returns for them, summed over
+ * row shards.  floor [B] or NULL.  1 <= M <= SREC_AHEAD_MAXT.  For a live slot (b, j) with u = items[b,j], t = target[b,j]:
+ *   ahead[b,j] = N[b,j] + A[b,j]                                                              (int32 [B, M], contiguous)
+ *   N[b,j] = #{ local rows v : (b, v) ELIGIBLE (above), id_lo + v is NOT one of items[b,:], !(s'[b,v] < floor[b]),
+ *               s'[b,v] > t  or (s'[b,v] == t and id_lo + v < u) }                                           - the pass
+ *   A[b,j] = #{ i != j live : items[b,i] != u, target[b,i] > -INFINITY, !(target[b,i] < floor[b]),
+ *               target[b,i] > t or (target[b,i] == t and items[b,i] < u) }            - the targets among themselves
+ * An empty slot gives 0.  A is added only with among_targets != 0 (a row shard passes 0: A needs no table and is added once).
+ * The session's own targets are left out of the pass BY ID and ordered among themselves by their GIVEN values - the rule of
+ * srec_score_ahead for its one label: round-off between the gather kernel's and the pass's summation orders cannot make a
+ * target count against itself, two targets never both count as ahead of each other, and the shown targets of a session get
+ * pairwise distinct ranks in (value descending, id ascending) order.  N is a sum over disjoint row ranges (row shards add up).
+ * With M == 1 the result is srec_score_ahead's, bit for bit.  Duplicate ids in a row are the caller's error: they do not fault,
+ * the result for those columns is unspecified; so is a NaN among the target values, for its session (no fault either).  ahead is WRITTEN (zeroed on the stream by the call); integer atomics only: a
+ * pure function of the inputs.  A bias, a grouped bias, SREC_LISTED_DROP, a floor and ids beyond int32 are accepted.
+ * ws: srec_score_ahead_many_ws() bytes (a token).  Nonzero and no launch, beyond the descriptor's reasons: M outside
+ * 1 .. SREC_AHEAD_MAXT; ld_items < M; items, target or ahead NULL; items, target, floor or ahead not aligned to 4 bytes. */
+#define SREC_AHEAD_MAXT 64
+int srec_score_ahead_many_ws(int B, int V, int d, int C, int L, int M, long* bytes);
+int srec_score_ahead_many(const void* served, const int* items, const float* target, long ld_items, int M, const float* floor,
+                          int among_targets, int* ahead, void* ws, void* stream);
+
 /* ---- serving: diversified top-N - greedy MMR re-rank of a pool, and intra-list diversity (diversify.hip) ------------------
  * Per session a pool of M slots; slot i has a row index row[b * M + i] into the row source X (fp32, n_rows rows of d columns,
  * leading dimension ld_x) and a value s[b * M + i].  A slot whose row index is < 0 or >= n_rows is UNFILLED: X is never read

@@ -138,6 +138,25 @@ class AugmentedDataset:
     def __len__(self):
         return len(self.index)
 
+    def rest_items(self, indices, max_targets=64):
+        """(int32 [n, M] array, truncated): the targets of rest-of-session evaluation for the samples `indices` - for sample
+        i = (session, label position p) the DISTINCT items of session[p:] in order of first occurrence, -1-padded; M is the
+        longest row of the call.  Column 0 is always the sample's next-item label.  truncated: the number of samples with more
+        than max_targets distinct remaining items; they keep the first max_targets."""
+        rows, truncated = [], 0
+        for i in indices:
+            sid, lidx = self.index[i]
+            rest = list(dict.fromkeys(int(x) for x in self.sessions[sid][lidx:]))
+            if len(rest) > max_targets:
+                truncated += 1
+                rest = rest[:max_targets]
+            rows.append(rest)
+        M = max([len(r) for r in rows] + [1])
+        out = np.full((len(rows), M), -1, dtype=np.int32)
+        for k, r in enumerate(rows):
+            out[k, :len(r)] = r
+        return out, truncated
+
 
 class RankSliceBatchSampler:
     """Multi-rank training on the reference's batches (strong scaling): batches are formed from `sampler` exactly as the

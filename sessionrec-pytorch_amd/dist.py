@@ -454,6 +454,12 @@ class HipLocal:
         """this shard's count of ops.score_ahead: the eligible rows of [id_lo, id_lo + n) ahead of (labels, target).  bias: as in select()"""
         return self.ops.score_ahead(srs, table, cs, labels, target, off_ex, off_in, listed, drop_listed, id_lo, **bias)
 
+    def ahead_many(self, srs, table, cs, items, target, off_ex, off_in, listed, drop_listed, id_lo, **bias):
+        """this shard's N of ops.score_ahead_many: per target, the eligible rows of [id_lo, id_lo + n) ahead of it that are not
+        targets of the session themselves (among_targets=False: the caller adds A once).  bias: as in select()"""
+        return self.ops.score_ahead_many(srs, table, cs, items, target, off_ex, off_in, listed, drop_listed, id_lo,
+                                         among_targets=False, **bias)
+
     def diversify(self, X, row, val, k, diversity):
         """ops.diversify over rows the caller has bounded (checked): (val [B,k], pick [B,k], mmr [B,k], ild [B])"""
         return self.ops.diversify(X, row, val, k, diversity, checked=True)
@@ -1045,6 +1051,27 @@ class VocabParallel:
                            extra=(labels.reshape(-1).to(torch.int64), target.reshape(-1), floor),
                            neutral=lambda B, dev: torch.zeros(B, device=dev, dtype=torch.int32),
                            combine=lambda n: all_reduce_sum(n, self.group))
+
+    def ahead_many(self, srs, table, cs, items, target, off_ex=None, off_in=None, listed=None, drop_listed=False,
+                   data_parallel=False, bias=None, group=None, floor=None):
+        """int32 [B, M]: where each of M given items per session stands over the sharded table (ops.score_ahead_many's contract;
+        the arguments of select(); items [B, M] global ids, -1 = empty; target fp32 [B, M] their served scores - what
+        score_items() over the sharded table returned at `items`, the same on every rank; floor [B] or None: cutoff()'s).  N is
+        a SUM over disjoint row ranges: every rank counts among its own LIVE rows with its id_lo and its columns of the bias,
+        leaving the targets' own rows out (a rank without live rows counts nothing), and ONE sum-all-reduce of [B, M] integers
+        follows; A - the targets among themselves - needs no table and is added once, from the values every rank holds alike
+        (ops.ahead_among_targets): the single-device result, bit for bit.  data_parallel as in select(): items, target and
+        floor travel with the sessions."""
+        from .score import ahead_among_targets
+        M = items.shape[-1]
+        items, target = items.reshape(-1, M).to(torch.int64), target.reshape(-1, M)
+        n = self._serve(lambda tab, mix, itf, **b: self.local.ahead_many(*tab, itf[0], itf[1], *mix, drop_listed, self.lo, **b,
+                                                                         **self._floor_kw(itf[2])),
+                        srs, table, cs, off_ex, off_in, listed, data_parallel, bias, group, extra=(items, target, floor),
+                        neutral=lambda B, dev: torch.zeros(B, M, device=dev, dtype=torch.int32),
+                        combine=lambda c: all_reduce_sum(c, self.group))
+        # (under data_parallel n is this rank's own sessions again, as items, target and floor are)
+        return n + ahead_among_targets(items, target, floor).to(device=n.device, dtype=n.dtype)
 
     def diversify(self, table, ids, val, k, diversity, data_parallel=False):
         """the greedy MMR re-rank of ops.diversify over the sharded table (val [B,k], pick [B,k], mmr [B,k], ild [B]): ids

@@ -283,6 +283,7 @@ _LISTED_TOO_MANY = {
     'score_cutoff': 'score_cutoff: %d listed items per session; csrc/score_cutoff.hip takes at most 64',
     'score_select_many': 'score_select_many: %d listed items per session; csrc/select_many.hip takes at most 64',
     'score_ahead': 'score_ahead: %d listed items per session; csrc/rank_served.hip takes at most 64',
+    'score_ahead_many': 'score_ahead_many: %d listed items per session; csrc/rank_served_many.hip takes at most 64',
 }
 _LISTED_TOO_MANY['cutoff_passes'] = _LISTED_TOO_MANY['score_cutoff']      # (score_cutoff's generator speaks of lists in its words)
 
@@ -526,6 +527,70 @@ def score_ahead(srs, table, cs, labels, target, off_ex=None, off_in=None, listed
     out = torch.empty(B, device=dev, dtype=torch.int32)
     desc = a.struct()
     lib.srec_score_ahead(_ct.addressof(desc), ptr(labels), ptr(target), ptr(floor), ptr(out), None, stream())
+    return out
+
+
+def ahead_among_targets(items, target, floor=None):
+    """int32 [B, M]: the A part of score_ahead_many - how many of a session's OTHER targets stand ahead of each of them by
+    their given values: A[b,j] = #{ i != j live : items[b,i] != items[b,j], target[b,i] > -inf, !(target[b,i] < floor[b]),
+    target[b,i] > target[b,j] or (equal and items[b,i] < items[b,j]) }; a slot with items < 0 is empty, counts for nobody and
+    gets 0.  It needs no table: the sharded route adds it once after the all-reduce, the materialised evaluation uses it too.
+    Plain torch on any device."""
+    items = torch.as_tensor(items).detach()
+    target = torch.as_tensor(target).detach().to(device=items.device, dtype=torch.float32)
+    B, M = items.shape
+    u = items.to(torch.int64)
+    live = u >= 0
+    f = torch.full((B,), float('-inf'), device=items.device) if floor is None else \
+        torch.as_tensor(floor).detach().to(device=items.device, dtype=torch.float32).reshape(B)
+    counts = live & (target > float('-inf')) & ~(target < f[:, None])                  # [B, i]: i can stand ahead of somebody
+    ti, tj, ui, uj = target[:, :, None], target[:, None, :], u[:, :, None], u[:, None, :]
+    ahead = counts[:, :, None] & live[:, None, :] & (ui != uj) & ((ti > tj) | ((ti == tj) & (ui < uj)))
+    return ahead.sum(1).to(torch.int32)
+
+
+def score_ahead_many(srs, table, cs, items, target, off_ex=None, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None,
+                     group=None, floor=None, among_targets=True):
+    """int32 [B, M]: score_ahead for M given items per session in ONE pass over the table (csrc/rank_served_many.hip) - where
+    each of them stands among what is SERVED.  items: [B, M] global item ids, 1 <= M <= 64, an entry < 0 is an empty slot
+    (result 0), every id at most once per row (not checked here: the model-level entry points refuse duplicates); target:
+    fp32 [B, M], the items' own s' - what score_items returns at `items` with the same operands (summed over row shards).
+    ahead[b,j] = N + A.  N: the eligible rows that are NOT one of items[b,:] (left out by id), are not below floor[b] and score
+    above target[b,j], or equal to it with a lower id.  A (among_targets=True): the session's other targets that could be
+    shown (target > -inf, not below the floor) and stand ahead of j by their GIVEN values, ties towards the lower id
+    (ahead_among_targets) - so a session's shown targets get pairwise distinct ranks, and round-off between the gather kernel
+    and the pass cannot make two targets count against each other.  With M = 1 the result is score_ahead's, bit for bit; N of
+    disjoint row shards adds up (among_targets=False on the shards, A added once).  Whether a target itself could be shown is
+    the caller's test: model.rank_items makes it.  Integer atomics: equal bits on every call.  Other arguments as score_ahead."""
+    a = _served_args('score_ahead_many', srs, table, cs, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
+    B, dev = a.B, a.srs.device
+    items = torch.as_tensor(items).detach()
+    if items.is_floating_point() or items.is_complex() or items.dtype == torch.bool or items.dim() != 2 or items.shape[0] != B:
+        raise ValueError('score_ahead_many: items must hold [%d, M] integer item ids, got %s %s' % (B, items.dtype, tuple(items.shape)))
+    M = items.shape[1]
+    if not 1 <= M <= CONST['SREC_AHEAD_MAXT']:
+        raise ValueError('score_ahead_many: %d items per session; csrc/rank_served_many.hip takes between 1 and %d'
+                         % (M, CONST['SREC_AHEAD_MAXT']))
+    target = torch.as_tensor(target).detach()
+    if not target.is_floating_point() or tuple(target.shape) != (B, M):
+        raise ValueError('score_ahead_many: target must hold [%d, %d] floating numbers (the items\' scores), got %s %s'
+                         % (B, M, target.dtype, tuple(target.shape)))
+    floor = _floor_arg('score_ahead_many', floor, B, dev)
+    if B == 0:
+        return torch.zeros(0, M, device=dev, dtype=torch.int32)
+    if items.dtype != torch.int32:          # (an id beyond int32 stays beyond every local row: the kernel clamps around them)
+        items = items.to(torch.int64).clamp(min=-1, max=2 ** 31 - 1).to(torch.int32)
+    items = items.to(dev).contiguous()
+    target = target.to(device=dev, dtype=torch.float32).contiguous()
+    if a.V == 0:                            # a shard without rows: the targets among themselves, or nothing
+        return ahead_among_targets(items, target, floor) if among_targets else torch.zeros(B, M, device=dev, dtype=torch.int32)
+    # no scratch: the counts meet in integer atomics (srec_score_ahead_many_ws is a token); the call validates the shape up front
+    n = _ct.c_long()
+    lib.srec_score_ahead_many_ws(B, a.V, a.d, a.C, a.L, M, _ct.addressof(n))
+    out = torch.empty(B, M, device=dev, dtype=torch.int32)
+    desc = a.struct()
+    lib.srec_score_ahead_many(_ct.addressof(desc), ptr(items), ptr(target), M, M, ptr(floor), int(bool(among_targets)), ptr(out),
+                              None, stream())
     return out
 
 

@@ -230,7 +230,7 @@ class _ScoringMixin:
                'select_many': ('score_select_many', {}),
                'norm': ('score_norm', {}), 'cutoff': ('score_cutoff', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
                'score_items': ('score_items', {'checked': True}),   # (model.score_items looked; sample() passes the kernel's ids)
-               'ahead': ('score_ahead', {})}
+               'ahead': ('score_ahead', {}), 'ahead_many': ('score_ahead_many', {})}
 
     def _route(self, name):
         """(callable, its route keywords) of served call `name`: shard.<name> fed as evaluate() feeds the shard
@@ -571,6 +571,67 @@ class _ScoringMixin:
                 shown = shown & ~(target < cut['floor'])           # (the kernels' own test of a floor)
             out = torch.where(shown, ahead, torch.full_like(ahead, -2))
             return torch.where(lab < 0, torch.full_like(ahead, -1), out)
+
+    def rank_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None, top_k=None, top_p=None, min_p=None,
+                   temperature=1.0):
+        """int32 [B, M]: the rank of each of M given items per session among what is SERVED - served_rank() for several items
+        at once, the counterpart of score_items(): rest-of-session evaluation (every remaining item of a session is relevant;
+        train.evaluate_rest, train.metrics_from_item_ranks) and "where would these items land?" (a campaign, a re-ranker's
+        candidates).  items: [B, M] item ids per session or [M] shared by all sessions, any integer dtype, M <= 64, -1 =
+        padding; an id may not appear twice in a row.
+          -1: an empty slot.
+          -2: the item could NOT be shown: its served value is -inf (the session's own item under exclude_seen, item_bias -inf,
+              or a score of -inf) or it lies below the truncation floor.
+          otherwise the rank r >= 0: when r < k <= 128 the item sits at position r of recommend(k=k, same keywords).
+        The rank counts the eligible items ahead - the catalogue's by the counting pass, the session's other given items by the
+        values score_items() returns for them - so the shown items of a session always get pairwise distinct ranks, in
+        recommend()'s order.  The values come from the gather kernel; ONE more fused pass over the table compares every score
+        with the session's M thresholds (csrc/rank_served_many.hip; ops.score_ahead_many), instead of M passes of served_rank():
+        no (B, V) score matrix, sharded table included (one integer all-reduce).  M = 1 takes served_rank()'s route.  There is
+        no renormalize keyword: a per-session constant shifts no rank.  Runs in eval mode under torch.no_grad(); item_bias /
+        item_group, the items and the truncation keywords are checked before anything of the model runs (ValueError), at the
+        price of the one device-to-host read score_items() pays."""
+        bias = self._item_bias('rank_items', item_bias, item_group)
+        n = self.shard.V if self.shard is not None else self._table().shape[0]
+        ids = torch.as_tensor(items).detach()
+        if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() not in (1, 2):
+            raise ValueError('rank_items: items must be an integer tensor [B, M] or [M], got %s %s' % (ids.dtype, tuple(ids.shape)))
+        M = ids.shape[-1]
+        if not 1 <= M <= ops.CONST['SREC_AHEAD_MAXT']:
+            raise ValueError('rank_items: %d items per session; between 1 and %d are ranked in one call'
+                             % (M, ops.CONST['SREC_AHEAD_MAXT']))
+        ids = ids.to(torch.int64)
+        if ids.numel() > 0:
+            rows = ids.reshape(-1, M).sort(dim=1).values
+            dup = ((rows[:, 1:] == rows[:, :-1]) & (rows[:, 1:] >= 0)).any()
+            lo, hi, dup = torch.stack([ids.min(), ids.max(), dup.to(torch.int64)]).tolist()      # the one device-to-host read
+            if lo < -1 or hi >= n:
+                raise ValueError('rank_items: item id %d; ids are in [0, %d), or -1 for a padding slot' % (lo if lo < -1 else hi, n))
+            if dup:
+                raise ValueError('rank_items: an item id appears twice in a row of items; every id at most once per session')
+        ops.cutoff_scalars('rank_items', top_k, top_p, min_p, temperature)
+        crit = self._cutoff_args('rank_items', top_k, top_p, min_p, temperature)
+        with _Serving(self):
+            srs, cs, off_ex, off_in, listed = self._served(*inputs, exclude_seen=exclude_seen, renormalize=False, **bias)
+            B = srs[0].shape[0]
+            if ids.dim() == 2 and ids.shape[0] != B:
+                raise ValueError('rank_items: items for %d sessions, the batch has %d' % (ids.shape[0], B))
+            ids = ids.to(srs[0].device).expand(B, M).contiguous()
+            target = self._items_of(srs, cs, ids, off_ex, off_in, listed, exclude_seen, **bias)
+            cut = {} if crit is None else dict(floor=self._cutoff_of(srs, cs, off_ex, off_in, listed, exclude_seen, crit, **bias)[0])
+            if M == 1:
+                fn, kw = self._route('ahead')
+                ahead = fn(srs, self._table(), cs, ids[:, 0].to(torch.int32), target[:, 0], off_ex, off_in, listed, exclude_seen,
+                           **kw, **cut, **bias)[:, None]
+            else:
+                fn, kw = self._route('ahead_many')
+                ahead = fn(srs, self._table(), cs, ids.to(torch.int32), target, off_ex, off_in, listed, exclude_seen, **kw, **cut,
+                           **bias)
+            shown = target > float('-inf')
+            if cut:
+                shown = shown & ~(target < cut['floor'][:, None])           # (the kernels' own test of a floor)
+            out = torch.where(shown, ahead, torch.full_like(ahead, -2))
+            return torch.where(ids < 0, torch.full_like(ahead, -1), out)
 
     def score_items(self, *inputs, items, exclude_seen=False, item_bias=None, item_group=None, renormalize=False):
         """fp32 [B, M]: the log-probability forward() returns at the given items of every session - full-catalog soft-max

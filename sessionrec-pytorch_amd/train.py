@@ -156,6 +156,147 @@ def evaluate_served(model, data_loader, device, cutoffs=(20,), **served):
     return metrics_from_served_ranks(ranks, [int(k) for k in cutoffs])
 
 
+def _served_scores(scores, item_bias, item_group, seen, top_k, top_p, min_p, temperature):
+    """(s float64 [B, V], eligible bool [B, V], floor float64 [B, 1]) under served_ranks_from_scores' conventions (restated here: that function stays as it is): the biased
+    score, the rows that can be shown (bias > -inf, not seen, not below the truncation floor) and that floor (-inf without one)"""
+    ninf = float('-inf')
+    s = scores.double()
+    B, V = s.shape
+    elig = th.ones(B, V, dtype=th.bool, device=s.device)
+    if item_bias is not None:
+        b = item_bias.to(s.device).double()
+        b = b[item_group.to(s.device).long()] if (b.dim() == 2 and item_group is not None) else b.reshape(-1, V)
+        s = s + b
+        elig &= b != ninf
+    if seen is not None:
+        sl = seen.to(s.device).long()
+        drop = th.zeros(B, V + 1, dtype=th.bool, device=s.device)
+        drop.scatter_(1, th.where(sl < 0, th.full_like(sl, V), sl), True)
+        elig &= ~drop[:, :V]
+    floor = th.full((B, 1), ninf, dtype=th.float64, device=s.device)
+    if top_k is not None or top_p is not None or min_p is not None:
+        se = th.where(elig, s, th.full_like(s, ninf))
+        top = se.max(1, keepdim=True).values
+        srt = se.sort(1, descending=True).values
+        if top_k is not None:
+            kth = srt[:, int(top_k) - 1:int(top_k)] if int(top_k) <= V else floor
+            few = elig.sum(1, keepdim=True) < int(top_k)
+            floor = th.maximum(floor, th.where(few, th.full_like(kth, ninf), kth))
+        if top_p is not None and float(top_p) < 1.0:
+            w = th.where(srt > ninf, th.exp((srt - top) / float(temperature)), th.zeros_like(srt))
+            cum = w.cumsum(1)
+            first = (cum >= float(top_p) * cum[:, -1:]).double().argmax(1, keepdim=True)
+            floor = th.maximum(floor, srt.gather(1, first))
+        if min_p is not None:
+            import math
+            floor = th.maximum(floor, top + float(temperature) * math.log(float(min_p)))
+        elig = elig & ~(s < floor)
+    return s, elig, floor
+
+
+def item_ranks_from_scores(scores, items, item_bias=None, item_group=None, seen=None, top_k=None, top_p=None, min_p=None,
+                           temperature=1.0):
+    """model.rank_items from a materialised (B, V) score matrix (a CPU model's forward()): int64 [B, M] with its -1 / -2
+    convention, beside served_ranks_from_scores and with its keywords.  items: [B, M] or [M] item ids, -1 = empty slot, every id
+    at most once per row.  An item that can be shown is ranked among ALL items that can (its session's other targets
+    included), by (value descending, id ascending): the contract of ops.score_ahead_many on exact scores."""
+    ninf = float('-inf')
+    s, elig, _ = _served_scores(scores, item_bias, item_group, seen, top_k, top_p, min_p, temperature)
+    B, V = s.shape
+    it = th.as_tensor(items).to(s.device).long()
+    it = it.expand(B, it.shape[-1]) if it.dim() == 1 else it
+    safe = it.clamp(min=0)
+    t = s.gather(1, safe)                                                     # [B, M]
+    shown = elig.gather(1, safe) & (t > ninf)
+    se = th.where(elig, s, th.full_like(s, float('nan')))                     # (a NaN is ahead of nothing)
+    ids = th.arange(V, device=s.device).view(1, 1, V)
+    ahead = (se[:, None, :] > t[:, :, None]) | ((se[:, None, :] == t[:, :, None]) & (ids < safe[:, :, None]))
+    r = th.where(shown, ahead.sum(2), th.full_like(it, -2))
+    return th.where(it >= 0, r, th.full_like(it, -1))
+
+
+def metrics_from_item_ranks(ranks, cutoffs):
+    """Rest-of-session metrics from the ranks of model.rank_items ([n, M]; -1 = empty slot, -2 = a target that could not be
+    shown): a CASE is a row with at least one slot != -1, n its number of such slots (a -2 stays in n), hits = #{0 <= r < k}.
+    Per cutoff k, means over the cases of  hit@k = [hits > 0];  recall@k = hits / n;  precision@k = hits / k;
+    mrr@k = 1 / (1 + min r) if that minimum is < k, else 0;  map@k = (1 / min(n, k)) * sum over the hits j of
+    #{i : 0 <= r_i <= r_j} / (r_j + 1);  ndcg@k = sum over the hits of 1 / log2(r_j + 2), divided by the ideal
+    sum_{i < min(n, k)} 1 / log2(i + 2).  'shown': the share of the live slots with r >= 0.  No cases: all zeros.  With one
+    target per case hit = recall, and hit / mrr / ndcg / shown are metrics_from_served_ranks'."""
+    r = th.as_tensor(ranks).detach().to('cpu', th.int64)
+    r = r.reshape(-1, r.shape[-1]) if r.dim() >= 2 else r.reshape(-1, 1)
+    live = r != -1
+    r, live = r[live.any(1)], live[live.any(1)]
+    cases = int(r.shape[0])
+    out = {}
+    ok = r >= 0
+    if cases == 0:
+        for k in cutoffs:
+            out.update({'%s@%d' % (m, int(k)): 0.0 for m in ('hit', 'recall', 'precision', 'mrr', 'map', 'ndcg')})
+        out['shown'] = 0.0
+        return out
+    n = live.sum(1).double()
+    rd = r.double()
+    # for MAP: the number of the case's shown targets ranked at or before each target
+    upto = (ok[:, None, :] & ok[:, :, None] & (r[:, None, :] <= r[:, :, None])).sum(2).double()      # [case, j]
+    big = th.where(ok, r, th.full_like(r, 2 ** 62)).min(1).values
+    for k in cutoffs:
+        k = int(k)
+        hit = ok & (r < k)
+        hits = hit.sum(1).double()
+        lim = th.minimum(n, th.full_like(n, float(k)))
+        ideal = th.cumsum(1.0 / th.log2(th.arange(int(lim.max())).double() + 2.0), 0)[(lim - 1).long()]
+        zero = th.zeros_like(rd)
+        out['hit@%d' % k] = float((hits > 0).double().mean())
+        out['recall@%d' % k] = float((hits / n).mean())
+        out['precision@%d' % k] = float((hits / k).mean())
+        out['mrr@%d' % k] = float(th.where(big < k, 1.0 / (big.double() + 1.0), th.zeros_like(n)).mean())
+        out['map@%d' % k] = float((th.where(hit, upto / (rd + 1.0), zero).sum(1) / lim).mean())
+        out['ndcg@%d' % k] = float((th.where(hit, 1.0 / th.log2(rd.clamp(min=0) + 2.0), zero).sum(1) / ideal).mean())
+    out['shown'] = float(ok.sum()) / float(live.sum())
+    return out
+
+
+def evaluate_rest(model, dataset, collate_fn, device, batch_size, cutoffs=(20,), max_targets=64, **served):
+    """Rest-of-session evaluation, the second standard protocol of the session-based literature: every prefix is judged
+    against ALL distinct items its session still contains (dataset.rest_items; the next-item label is one of them) -
+    metrics_from_item_ranks (hit / recall / precision / mrr / map / ndcg @cutoffs, 'shown') plus 'truncated', the number of
+    prefixes with more than max_targets remaining items (they keep the first max_targets).  dataset: an AugmentedDataset,
+    walked sequentially in batches of batch_size through collate_fn.  served: the keywords of model.rank_items (exclude_seen,
+    item_bias, item_group - also a callable (inputs, labels) -> [B] - top_k, top_p, min_p, temperature).  On the GPU every
+    batch is ONE model.rank_items call (one counting pass for all targets, no (B, V) tensor, sharded table included); a CPU
+    model takes the materialised route, item_ranks_from_scores.  evaluate() and evaluate_served() are unchanged."""
+    model.eval()
+    group_of = served.get('item_group')
+    ranks, truncated, width = [], 0, 1
+    with th.no_grad():
+        for lo in range(0, len(dataset), batch_size):
+            idx = list(range(lo, min(lo + batch_size, len(dataset))))
+            inputs, labels = prepare_batch(collate_fn([dataset[i] for i in idx]), device)
+            items, cut = dataset.rest_items(idx, max_targets)
+            truncated += cut
+            items = th.from_numpy(items).to(device)
+            kw = dict(served)
+            if callable(group_of):
+                kw['item_group'] = group_of(inputs, labels)
+            if hasattr(model, 'rank_items') and labels.is_cuda:
+                r = model.rank_items(*inputs, items=items, **kw)
+            else:
+                seen = None
+                if kw.pop('exclude_seen', False):
+                    if not hasattr(model, '_session_items'):
+                        raise ValueError('evaluate_rest: exclude_seen on the materialised route needs model._session_items')
+                    seen = model._session_items(inputs[0])
+                r = item_ranks_from_scores(model(*inputs), items, seen=seen, **kw)
+            ranks.append(r.long().cpu())
+            width = max(width, r.shape[1])
+    pad = [th.cat([r, r.new_full((r.shape[0], width - r.shape[1]), -1)], 1) for r in ranks]
+    ranks = th.cat(pad) if pad else th.zeros(0, 1, dtype=th.long)
+    out = metrics_from_item_ranks(ranks, [int(k) for k in cutoffs])
+    out['truncated'] = int(truncated)
+    return out
+
+
 def evaluate(model, data_loader, device, cutoff=20, method='topk', cutoffs=None):
     """(MRR@cutoff, HR@cutoff) as the reference (train.py:36-55).  method='rank': from the label's rank among ALL items
     (model.target_rank on the GPU: one fused pass, no (B, V) tensor, mixtures of soft-maxes included; a CPU model's

@@ -13,7 +13,12 @@ counting pass over the item table - csrc/rank_served.hip - no (B, V) score matri
 --sample-min-p Q at --temperature additionally keep only the items a truncated draw (recommend.py --sample) could return.
 A label that cannot be shown - the session's own item under --exclude-seen, a denied item, an item outside the truncated
 set - is a miss at every cutoff; `shown` is the share of the test cases whose label could be shown at all.
-Output: ONE JSON line - {"metrics": {"hit@k", "mrr@k", "ndcg@k" per cutoff, "shown"}, "sessions": n, "flags": {...}}."""
+Output: ONE JSON line - {"metrics": {"hit@k", "mrr@k", "ndcg@k" per cutoff, "shown"}, "sessions": n, "flags": {...}}.
+--protocol rest is the second standard protocol of the session-based literature: every prefix is judged against ALL distinct
+items its session still contains (at most --max-targets of them, in order of first occurrence), under the same serving
+controls - hit / recall / precision / mrr / map / ndcg per cutoff and "shown" (train.evaluate_rest: model.rank_items ranks all
+targets of a batch in one counting pass, csrc/rank_served_many.hip).  Its line carries "truncated", the number of prefixes
+with more than --max-targets remaining items, and the flags "protocol" and "max_targets"."""
 import argparse
 import json
 import sys
@@ -38,6 +43,10 @@ def parser(model):
                    help='only items at least Q times as probable as the best one (0 < Q <= 1)')
     p.add_argument('--temperature', type=float, default=1.0, help='the temperature --sample-top-p / --sample-min-p are taken at')
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
+    p.add_argument('--protocol', default='next', choices=['next', 'rest'],
+                   help='next: the next item is the one relevant item; rest: every item the session still contains is relevant')
+    p.add_argument('--max-targets', type=int, default=64, metavar='M',
+                   help='--protocol rest: at most M distinct remaining items per prefix (1 .. 64), the first M are kept')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
     return p
 
@@ -58,6 +67,8 @@ def parse(argv=None):
         p.error('--sample-top-p must be a probability mass in (0, 1)')
     if args.sample_min_p is not None and not 0.0 < args.sample_min_p <= 1.0:
         p.error('--sample-min-p must be in (0, 1]')
+    if not 1 <= args.max_targets <= 64:
+        p.error('--max-targets must be in 1 .. 64')
     args.catalog = read_catalog(p, args)
     return args
 
@@ -69,11 +80,15 @@ def served_keywords(args, item_bias):
 
 
 def report(metrics, sessions, args):
-    """the one JSON line"""
+    """the one JSON line (--protocol next: exactly the keys it always had)"""
     flags = {k: getattr(args, k) for k in ('model', 'checkpoint', 'dataset_dir', 'exclude_seen', 'allow', 'deny', 'item_bias',
                                            'sample_top_k', 'sample_top_p', 'sample_min_p', 'temperature', 'batch_size', 'precision')}
     flags['cutoffs'] = list(args.cutoffs)
-    return json.dumps({'metrics': metrics, 'sessions': sessions, 'flags': flags})
+    if getattr(args, 'protocol', 'next') != 'rest':
+        return json.dumps({'metrics': metrics, 'sessions': sessions, 'flags': flags})
+    metrics = dict(metrics)
+    flags.update(protocol='rest', max_targets=args.max_targets)
+    return json.dumps({'metrics': metrics, 'sessions': sessions, 'truncated': metrics.pop('truncated', 0), 'flags': flags})
 
 
 def main(argv=None):
@@ -99,8 +114,12 @@ def main(argv=None):
     model.table_written()
     item_bias = None if args.catalog is None else ops.catalog_bias(num_items, device=device, **args.catalog)
     test_set = ds.AugmentedDataset(ds.read_sessions(str(Path(args.dataset_dir) / 'test.txt')))
-    loader = DataLoader(test_set, batch_size=args.batch_size, shuffle=False, collate_fn=collate_fn)
-    metrics = train.evaluate_served(model, loader, device, args.cutoffs, **served_keywords(args, item_bias))
+    if args.protocol == 'rest':
+        metrics = train.evaluate_rest(model, test_set, collate_fn, device, args.batch_size, args.cutoffs, args.max_targets,
+                                      **served_keywords(args, item_bias))
+    else:
+        loader = DataLoader(test_set, batch_size=args.batch_size, shuffle=False, collate_fn=collate_fn)
+        metrics = train.evaluate_served(model, loader, device, args.cutoffs, **served_keywords(args, item_bias))
     print(report(metrics, len(test_set), args))
 
 
