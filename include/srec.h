@@ -446,6 +446,11 @@ int srec_gemm16_nt(const void* desc, void* stream);
  * with SREC_G16_KEEP_DEAD only (the forward projections over the live-source rows of srec_hg_live_rows). */
 int srec_gemm16_nt_rows(const void* desc, const void* rows, void* stream);
 int srec_gemm16_tn(const void* desc, void* stream);
+/* two srec_gemm16_tn launches as ONE: the problems of desc_a (family A) and of desc_b (family B), np_a + np_b <= SREC_G16_MAXP, equal
+ * beta; every output tile gets the bytes the launch of its own desc gives it.  Each family's tiles are dealt to the XCDs in runs of
+ * their own, the tile order within a family is that of srec_gemm16_tn; family A takes the low workgroup indices (it starts first)
+ * unless b_first != 0. */
+int srec_gemm16_tn2(const void* desc_a, const void* desc_b, int b_first, void* stream);
 int srec_rows_bf16(const float* src, int ld, int n, const int* dyn, int d, void* dst16, void* stream);
 /* out [C, n] = sum_r part [C, R, n] in fixed order (the row-split weight-gradient products of one module), n % 4 == 0 */
 int srec_sum_slabs(const float* part, int C, int R, long n, float* out, void* stream);

@@ -375,16 +375,15 @@ __device__ __forceinline__ uint2 lds_tr16(const unsigned short* base, unsigned b
     return __builtin_bit_cast(uint2, v);
 }
 
+// tile bid (< g.start[g.np]) of the launch's tile list: the whole life of a workgroup, whichever kernel below dealt it the tile
 template <int BR, int NS>
-__global__ __launch_bounds__(256) void gemm16_tn_kernel(G16Args g) {
+__device__ __forceinline__ void gemm16_tn_tile(const G16Args& g, const int bid) {
     constexpr int T = 128;                               // output tile; BR = reduction rows per stage
     constexpr int PD = NS - 1;
     constexpr int STG = 2 * BR * T;                      // bf16 elements per stage (A tile + B tile)
     constexpr int NIO = BR / 4;                          // DMA instructions (4 rows each) per operand and stage
     constexpr int IPS = 2 * NIO / 4;                     // ... per stage and wave
     extern __shared__ __attribute__((aligned(16))) unsigned short smem[];
-    const int bid = xcd_tile(g);
-    if (bid >= g.start[g.np]) return;
     int p = 0;
 #pragma unroll
     for (int i = 1; i < G16_MAXP; ++i)
@@ -529,6 +528,34 @@ __global__ __launch_bounds__(256) void gemm16_tn_kernel(G16Args g) {
                 }
             }
         }
+}
+
+template <int BR, int NS>
+__global__ __launch_bounds__(256) void gemm16_tn_kernel(G16Args g) {
+    const int bid = xcd_tile(g);
+    if (bid >= g.start[g.np]) return;
+    gemm16_tn_tile<BR, NS>(g, bid);
+}
+
+// Two problem families in one launch (srec_gemm16_tn2): the tile list of g is family A's tiles followed by family B's.  Consecutive
+// runs over the concatenation (xcd_tile) would put all of one family behind half of the L2s; here every family is dealt in runs of
+// its own - XCD x takes the x-th run of `per` tiles of the first family and the x-th run of the second - so each family keeps the
+// tile -> XCD map, the order within an XCD and the sibling tiles behind one L2 it has in a launch of its own.  The first family
+// takes the low workgroup indices of every XCD (it starts first); a family takes 8 x per workgroups, the surplus ones exit.
+struct G16Fam { int n, per, base; };                    // tiles, tiles per XCD = ceil(n / 8), first tile in g's list
+struct G16Args2 {
+    G16Args g;
+    G16Fam first, second;
+};
+
+template <int BR, int NS>
+__global__ __launch_bounds__(256) void gemm16_tn2_kernel(G16Args2 a) {
+    const int x = (int)blockIdx.x & 7, l = (int)blockIdx.x >> 3;
+    const bool lead = l < a.first.per;
+    const G16Fam f = lead ? a.first : a.second;
+    const int t = x * f.per + (lead ? l : l - a.first.per);
+    if (t >= f.n) return;
+    gemm16_tn_tile<BR, NS>(a.g, f.base + t);
 }
 
 // -------------------------------------------------------------------------------------------------- operand copies
@@ -718,6 +745,38 @@ extern "C" int srec_gemm16_tn(const void* desc_, void* stream) {
     const size_t lds = (size_t)2 * 2 * 64 * 128 * 2;
     if (int rc = optin(gemm16_tn_kernel<64, 2>, (int)lds, om)) return rc;
     hipLaunchKernelGGL((gemm16_tn_kernel<64, 2>), dim3(blocks), dim3(256), lds, st, g);
+    SREC_LAUNCH_CHECK();
+    return 0;
+}
+
+// the problems of desc_a (family A) and desc_b (family B) in ONE launch, every tile computed as srec_gemm16_tn computes it; each
+// family is dealt to the XCDs on its own (gemm16_tn2_kernel).  b_first: family B takes the low workgroup indices.
+extern "C" int srec_gemm16_tn2(const void* desc_a, const void* desc_b, int b_first, void* stream) {
+    G16Args2 a{};
+    G16Args b{};
+    G16Args& g = a.g;
+    int na = 0, nb = 0;
+    if (int rc = fill(g, desc_a, 128, 128, true, na)) return rc;
+    if (int rc = fill(b, desc_b, 128, 128, true, nb)) return rc;
+    if (g.np + b.np > G16_MAXP || g.beta != b.beta) return SREC_BAD_ARG;
+    for (int p = 0; p < b.np; ++p) {
+        const int q = g.np + p;
+        for (int s = 0; s < G16_MAXS; ++s) { g.A[q][s] = b.A[p][s]; g.B[q][s] = b.B[p][s]; }
+        g.C[q] = b.C[p]; g.dyn[q] = b.dyn[p];
+        g.M[q] = b.M[p]; g.N[q] = b.N[p]; g.K[q] = b.K[p]; g.nseg[q] = b.nseg[p]; g.koff[q] = b.koff[p]; g.nsplit[q] = b.nsplit[p];
+        g.ldap[q] = b.ldap[p]; g.ldbp[q] = b.ldbp[p]; g.ldcp[q] = b.ldcp[p];
+        g.start[q] = na + b.start[p];
+    }
+    g.np += b.np;
+    g.start[g.np] = na + nb;
+    const G16Fam fa = {na, cdiv(na, 8), 0}, fb = {nb, cdiv(nb, 8), na};
+    a.first = b_first ? fb : fa; a.second = b_first ? fa : fb;
+    const int blocks = 8 * (fa.per + fb.per);
+    hipStream_t st = (hipStream_t)stream;
+    static std::atomic<unsigned long long> om;
+    const size_t lds = (size_t)2 * 2 * 64 * 128 * 2;      // (the ring of srec_gemm16_tn)
+    if (int rc = optin(gemm16_tn2_kernel<64, 2>, (int)lds, om)) return rc;
+    hipLaunchKernelGGL((gemm16_tn2_kernel<64, 2>), dim3(blocks), dim3(256), lds, st, a);
     SREC_LAUNCH_CHECK();
     return 0;
 }

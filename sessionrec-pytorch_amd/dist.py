@@ -1245,7 +1245,7 @@ class VocabParallel:
         if not _active(self.group) or parts is None or self._no_sync or not (0 <= k < len(parts) - 1) \
                 or k in self._bucket_early or not parts[k]:
             return
-        self.ops_flush()                               # deferred slab sums of the layers behind us: their gradients are written
+        self.ops_flush()                               # waiting weight-gradient products, then the deferred slab sums of the layers behind us: their gradients are written
         self._bucket_early[k] = self._bucket_reduce(k, parts[k], self.side_stream)
         self.early_launches += 1
 

@@ -410,11 +410,15 @@ class GRUExpandAll(torch.autograd.Function):
             for gW, nrow, segs, dyn in ((gWih[p], o.n * o.k, [(dGI16[p], x16[p])], o.dyn_rows), (gWhh[p], o.n, hh, o.dyn_n)):
                 nsp = max(1, (nrow + 511) // 512)
                 sl = torch.empty(nsp, d3, d, device=dev, dtype=torch.float32) if nsp > 1 else gW.unsqueeze(0)
-                probs.append(GemmProb(d3, d, nrow, segs, sl, dyn, nsplit=nsp))
+                probs.append(GemmProb(d3, d, nrow, segs, sl, dyn, nsplit=nsp, ld=(d3, d, d)))
                 if nsp > 1:
                     slabs.append((sl, gW))
-        for i in range(0, len(probs), G16_MAXP):
-            gemm16('tn', probs[i:i + G16_MAXP], d3, d, d)
+        if ops.WGRAD_ONE_LAUNCH and len(probs) <= G16_MAXP:
+            # ... and the MSHGNN layers' weight-gradient products that wait (ops.STEP) leave in this launch as its other family
+            ops.STEP.leave_with(probs, G16_MAXP)
+        else:
+            for i in range(0, len(probs), G16_MAXP):
+                gemm16('tn', probs[i:i + G16_MAXP], d3, d, d)
         gb = [grad_buf_pair(o.bih, o.bhh) for o in orders]
         # the weight-gradient slab sums join the ONE end-of-backward launch (defer_slab_sum); the bias partials keep their own
         # kernel: hundreds of partial rows of only 6 d columns - as a task of the generic slab sum (one thread per 4 columns

@@ -290,10 +290,19 @@ def _weight_grads(ctx, x, dP, gWs):
         xin16 = ctx.g16[0]
         pcs = [plan.pieces(m) for m in range(nm)]
         slabs = {m: torch.empty(len(pcs[m]), HD, D, device=x.device, dtype=torch.float32) for m in range(nm) if len(pcs[m]) > 1}
-        probs = [GemmProb(HD, D, nc, [(dP[m][o:o + nc], xin16[m][t0:t0 + nc])], slabs[m][pi:pi + 1] if m in slabs else gWs[m], dyn_t)
+        # the launch may wait for the k-gram GRU's weight-gradient launch and leave inside it (ops.STEP, "Waiting tn products"):
+        # autograd is then handed EVERY gWs[m] unwritten, so the permission is asked for all module weights, and the waiting
+        # problems hold aliases (a second reference to a returned gradient would make AccumulateGrad clone it, unwritten)
+        wait = ops.WGRAD_ONE_LAUNCH and 0 < sum(map(len, pcs)) <= ops.G16_MAXP and ops.can_defer(ctx.defer, ctx.wparams)
+        gC = [g.detach() for g in gWs] if wait else gWs
+        probs = [GemmProb(HD, D, nc, [(dP[m][o:o + nc], xin16[m][t0:t0 + nc])], slabs[m][pi:pi + 1] if m in slabs else gC[m], dyn_t,
+                          ld=(HD, D, D))
                  for m in range(nm) for pi, (o, t0, nc, dyn_t) in enumerate(pcs[m])]
-        for i in range(0, len(probs), ops.G16_MAXP):
-            ops.gemm16('tn', probs[i:i + ops.G16_MAXP], HD, D, D)
+        if wait:
+            ops.STEP.defer_product(probs, (dP, xin16, slabs))
+        else:
+            for i in range(0, len(probs), ops.G16_MAXP):
+                ops.gemm16('tn', probs[i:i + ops.G16_MAXP], HD, D, D)
         if slabs and ops.can_defer(ctx.defer, [ctx.wparams[m] for m in slabs]):
             for m, sl in slabs.items():
                 ops.defer_slab_sum(sl, gWs[m])

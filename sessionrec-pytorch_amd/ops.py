@@ -769,7 +769,28 @@ def _launch_intake(box, M, counter, dst, cap, err):
     lib.srec_copy_words_mailbox(box, M, counter, dst, cap, err, stream())
 
 
-STEP = StepQueue(_launch_slab_sums, _launch_intake)
+# The MSHGNN layer's weight-gradient products wait for the k-gram GRU's and leave in its launch (StepQueue, "Waiting tn products");
+# 0 = every node launches its own (tests / A-B runs).  Family order: which family takes the low workgroup indices of the one
+# launch, 'a' = the waiting (long) problems, 'b' = the GRU's short ones.  Measured: profiles/r09_notes.md (72.9 us for the two
+# launches, 64.3 us merged with 'a', 60.2 us with 'b')
+WGRAD_ONE_LAUNCH = os.environ.get('SREC_WGRAD_ONE_LAUNCH', '1') != '0'
+WGRAD_FAMILY_ORDER = os.environ.get('SREC_WGRAD_FAMILY_ORDER', 'b')
+
+
+def _launch_tn_products(fam_a, fam_b=None):
+    """fam_a / fam_b: [GemmProb with ld set] or None.  Both: one two-family launch (srec_gemm16_tn2, together at most one problem
+    table); one: its own srec_gemm16_tn launches"""
+    if fam_a and fam_b:
+        assert WGRAD_FAMILY_ORDER in ('a', 'b'), WGRAD_FAMILY_ORDER
+        ga, gb = gemm16_desc(fam_a, *fam_a[0].ld), gemm16_desc(fam_b, *fam_b[0].ld)
+        lib.srec_gemm16_tn2(_ct.addressof(ga), _ct.addressof(gb), int(WGRAD_FAMILY_ORDER == 'b'), stream())
+        return
+    probs = fam_a or fam_b
+    for i in range(0, len(probs), G16_MAXP):
+        gemm16('tn', probs[i:i + G16_MAXP], *probs[0].ld)
+
+
+STEP = StepQueue(_launch_slab_sums, _launch_intake, _launch_tn_products)
 defer_slab_sum = STEP.defer_slab_sum
 flush_deferred = STEP.flush                  # (from inside a backward pass; its end: STEP.finish)
 drop_stale_deferred = STEP.drop_stale
