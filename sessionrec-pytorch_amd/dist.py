@@ -855,7 +855,7 @@ class VocabParallel:
             if _active(self.group):
                 # sessions without a label carry -1 on every rank: summed as 0, restored afterwards
                 rank = all_reduce_sum(torch.where(labels < 0, torch.zeros_like(rank), rank), self.group)
-            # (a fix-up correction within round-off of the target may overshoot by one: see _ScoringMixin._rank_of)
+            # (a fix-up correction within round-off of the target may overshoot by one: see serving.ServingMixin._label_rank)
             return torch.where(labels < 0, torch.full_like(rank, -1), rank.clamp(min=0))
         # (no neutral value: the two passes meet in a collective, so a rank without live rows runs the body as well)
         return self._serve(two_passes, srs, table, cs, off_ex, off_in, listed, data_parallel, extra=labels.to(torch.int64))

@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .serving import Query
 from .srgnn import _ScoringMixin
 
 
@@ -562,17 +563,17 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         in-session mask): the mixture of msgifsr.py:281-321 is logsumexp_c(z_c[b,v] + off_c[b]) with per-session offsets
         built from what fused_loss computes anyway - off_ex = log softmax(alpha)_c + log phi_c[b, explore] - lse_ex_c[b],
         off_in = ... + log phi_c[b, repeat] - lse_in_c[b] for the session's own items (`listed`); without `extra`
-        off_ex = log softmax(alpha)_c - lse_c[b]; without fusion one component.  See _ScoringMixin.target_rank."""
+        off_ex = log softmax(alpha)_c - lse_c[b]; without fusion one component.  See ServingMixin.target_rank (serving.py)."""
         if not (self.extra or (self.fusion and self.order > 1)):
             return super().target_rank(*inputs, labels=labels)
         (mg,) = inputs
         with torch.no_grad():
-            srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg, labels)
-            return self._rank_of(srs, cs, labels, off_ex, off_in, listed)
+            return self._label_rank(self._mixture_offsets(mg, labels), labels)
 
     def _mixture_offsets(self, mg, labels=None):
-        """(session vectors per order, column scale, off_ex [C, B], off_in [C, B] or None, listed [B, L] or None): the
-        per-session offsets under which logsumexp_c(z_c[b,v] + off_c[b]) is the score forward() returns (target_rank)"""
+        """serving.Query(session vectors per order, column scale, off_ex [C, B], off_in [C, B] or None, listed [B, L] or
+        None; nothing dropped, no bias): the per-session offsets under which logsumexp_c(z_c[b,v] + off_c[b]) is the score
+        forward() returns (target_rank)"""
         srs = self.session_repr(mg)
         if not isinstance(srs, (list, tuple)):
             srs = [srs]
@@ -595,7 +596,7 @@ class MSGIFSR(_ScoringMixin, nn.Module):
                 off_ex.append(la[c] + lphi[:, 1] - lse_ex)
             else:
                 off_ex.append(la[c] - lse)
-        return srs, cs, torch.stack(off_ex, 0), torch.stack(off_in, 0) if self.extra else None, listed
+        return Query(srs, cs, torch.stack(off_ex, 0), torch.stack(off_in, 0) if self.extra else None, listed)
 
     def _scoring_args(self, *inputs, exclude_seen, raw=False):
         """the mixture of target_rank: forward()'s log scores WITHOUT its (B, V) matrices (one per order, plus the
@@ -606,13 +607,11 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         if not (self.extra or (self.fusion and self.order > 1)):
             return super()._scoring_args(*inputs, exclude_seen=exclude_seen, raw=raw)
         (mg,) = inputs
-        srs, cs, off_ex, off_in, listed = self._mixture_offsets(mg)
+        q = self._mixture_offsets(mg)._replace(drop=exclude_seen)
         if self.extra or exclude_seen:
             # (the tight [B, L] view: _in_session's is as wide as the longest read-out over all orders)
-            listed = self._session_items(mg)
-        if exclude_seen:
-            off_in = None
-        return srs, cs, off_ex, off_in, listed
+            q = q._replace(listed=self._session_items(mg))
+        return q._replace(off_in=None) if exclude_seen else q
 
     def forward(self, mg):
         sr = self.session_repr(mg)

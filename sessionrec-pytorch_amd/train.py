@@ -83,47 +83,17 @@ def served_ranks_from_scores(scores, labels, item_bias=None, item_group=None, se
     convention.  item_bias [V] or [G, V] (item_group [B]) is added to the scores, -inf = not in the catalogue; seen [B, L] item
     ids (-1 = empty) are not eligible; top_k / top_p / min_p at `temperature` as model.cutoff() defines them, on the eligible
     rows.  Ties go towards the lower id (ranks_from_scores)."""
-    ninf = float('-inf')
-    s = scores.double()
-    B, V = s.shape
-    elig = th.ones(B, V, dtype=th.bool, device=s.device)
-    if item_bias is not None:
-        b = item_bias.to(s.device).double()
-        b = b[item_group.to(s.device).long()] if (b.dim() == 2 and item_group is not None) else b.reshape(-1, V)
-        s = s + b
-        elig &= b != ninf
-    if seen is not None:
-        sl = seen.to(s.device).long()
-        drop = th.zeros(B, V + 1, dtype=th.bool, device=s.device)
-        drop.scatter_(1, th.where(sl < 0, th.full_like(sl, V), sl), True)
-        elig &= ~drop[:, :V]
-    lab = labels.to(s.device).long()
-    safe = lab.clamp(min=0)
-    t = s.gather(1, safe.unsqueeze(1))
-    shown = elig.gather(1, safe.unsqueeze(1)).squeeze(1) & (t.squeeze(1) > ninf)
-    if top_k is not None or top_p is not None or min_p is not None:
-        se = th.where(elig, s, th.full_like(s, ninf))
-        top = se.max(1, keepdim=True).values
-        floor = th.full((B, 1), ninf, dtype=th.float64, device=s.device)
-        srt = se.sort(1, descending=True).values
-        if top_k is not None:
-            kth = srt[:, int(top_k) - 1:int(top_k)] if int(top_k) <= V else floor
-            few = elig.sum(1, keepdim=True) < int(top_k)
-            floor = th.maximum(floor, th.where(few, th.full_like(kth, ninf), kth))
-        if top_p is not None and float(top_p) < 1.0:
-            w = th.where(srt > ninf, th.exp((srt - top) / float(temperature)), th.zeros_like(srt))
-            cum = w.cumsum(1)
-            first = (cum >= float(top_p) * cum[:, -1:]).double().argmax(1, keepdim=True)
-            floor = th.maximum(floor, srt.gather(1, first))
-        if min_p is not None:
-            import math
-            floor = th.maximum(floor, top + float(temperature) * math.log(float(min_p)))
-        elig &= ~(s < floor)
-        shown &= ~(t.squeeze(1) < floor.squeeze(1))
-    ids = th.arange(V, device=s.device).unsqueeze(0)
-    ahead = elig & (ids != safe.unsqueeze(1)) & ((s > t) | ((s == t) & (ids < safe.unsqueeze(1))))
-    r = th.where(shown, ahead.sum(1), th.full_like(lab, -2))
-    return th.where(lab >= 0, r, th.full_like(lab, -1))
+    return item_ranks_from_scores(scores, labels.reshape(-1, 1), item_bias, item_group, seen, top_k, top_p, min_p, temperature)[:, 0]
+
+
+def _seen_items(who, model, inputs, kw):
+    """the materialised routes' `seen`: exclude_seen taken OUT of the keywords kw; when set, the model's own view of every
+    session's items (model._session_items), None otherwise"""
+    if not kw.pop('exclude_seen', False):
+        return None
+    if not hasattr(model, '_session_items'):
+        raise ValueError('%s: exclude_seen on the materialised route needs model._session_items' % who)
+    return model._session_items(inputs[0])
 
 
 def evaluate_served(model, data_loader, device, cutoffs=(20,), **served):
@@ -145,11 +115,7 @@ def evaluate_served(model, data_loader, device, cutoffs=(20,), **served):
             if hasattr(model, 'served_rank') and labels.is_cuda:
                 r = model.served_rank(*inputs, labels=labels, **kw)
             else:
-                seen = None
-                if kw.pop('exclude_seen', False):
-                    if not hasattr(model, '_session_items'):
-                        raise ValueError('evaluate_served: exclude_seen on the materialised route needs model._session_items')
-                    seen = model._session_items(inputs[0])
+                seen = _seen_items('evaluate_served', model, inputs, kw)
                 r = served_ranks_from_scores(model(*inputs), labels, seen=seen, **kw)
             ranks.append(r.long().cpu())
     ranks = th.cat(ranks) if ranks else th.zeros(0, dtype=th.long)
@@ -157,8 +123,8 @@ def evaluate_served(model, data_loader, device, cutoffs=(20,), **served):
 
 
 def _served_scores(scores, item_bias, item_group, seen, top_k, top_p, min_p, temperature):
-    """(s float64 [B, V], eligible bool [B, V], floor float64 [B, 1]) under served_ranks_from_scores' conventions (restated here: that function stays as it is): the biased
-    score, the rows that can be shown (bias > -inf, not seen, not below the truncation floor) and that floor (-inf without one)"""
+    """(s float64 [B, V], eligible bool [B, V], floor float64 [B, 1]) of the materialised routes: the biased score, the rows
+    that can be shown (bias > -inf, not seen, not below the truncation floor) and that floor (-inf without one)"""
     ninf = float('-inf')
     s = scores.double()
     B, V = s.shape
@@ -282,11 +248,7 @@ def evaluate_rest(model, dataset, collate_fn, device, batch_size, cutoffs=(20,),
             if hasattr(model, 'rank_items') and labels.is_cuda:
                 r = model.rank_items(*inputs, items=items, **kw)
             else:
-                seen = None
-                if kw.pop('exclude_seen', False):
-                    if not hasattr(model, '_session_items'):
-                        raise ValueError('evaluate_rest: exclude_seen on the materialised route needs model._session_items')
-                    seen = model._session_items(inputs[0])
+                seen = _seen_items('evaluate_rest', model, inputs, kw)
                 r = item_ranks_from_scores(model(*inputs), items, seen=seen, **kw)
             ranks.append(r.long().cpu())
             width = max(width, r.shape[1])

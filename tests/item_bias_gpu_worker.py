@@ -49,13 +49,15 @@ def run_rank(rank, world, port, outdir):
         with torch.no_grad():
             out['select'] = cpu(vp.select([sr], table, cs_loc, K, bias=bias, group=group))
             out['select_shared'] = cpu(vp.select([sr], table, cs_loc, K, bias=bias[1]))
-            out['select_routed'] = cpu(model._select_of([sr], cs_loc, K, None, None, None, False, bias=bias, group=group))
+            out['select_routed'] = cpu(model._run(pkg('serving').Query([sr], cs_loc, None, None, None, False, dict(bias=bias, group=group)),
+                                                  'select', K))
             out['select_drop'] = cpu(vp.select([sr], table, cs_loc, K, listed=listed, drop_listed=True, bias=bias, group=group))
             out['select_dp_drop'] = cpu(vp.select([sr[mine]], table, cs_loc, K, listed=listed[mine, :4 + rank], drop_listed=True,
                                                   data_parallel=True, bias=bias, group=group[mine]))
             out['items'] = cpu(vp.score_items([sr], table, cs_loc, items, bias=bias, group=group))
             out['items_shared'] = cpu(vp.score_items([sr], table, cs_loc, items[0], bias=bias[1]))
-            out['items_routed'] = cpu(model._items_of([sr], cs_loc, items, None, None, None, False, bias=bias, group=group))
+            out['items_routed'] = cpu(model._run(pkg('serving').Query([sr], cs_loc, None, None, None, False, dict(bias=bias, group=group)),
+                                                 'score_items', items))
             out['items_drop'] = cpu(vp.score_items([sr], table, cs_loc, items, listed=listed, drop_listed=True, bias=bias, group=group))
             out['items_dp_drop'] = cpu(vp.score_items([sr[mine]], table, cs_loc, items[mine], listed=listed[mine, :4 + rank],
                                                       drop_listed=True, data_parallel=True, bias=bias, group=group[mine]))

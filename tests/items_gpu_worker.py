@@ -48,7 +48,7 @@ def run_rank(rank, world, port, outdir):
         out = dict(rank=rank, lo=vp.lo, hi=vp.hi, n_live=vp.n_live, rows=table.shape[0])
         with torch.no_grad():
             out['replicated'] = vp.score_items([sr], table, cs_loc, items).cpu()
-            out['routed'] = model._items_of([sr], cs_loc, items, None, None, None, False).cpu()       # the model's own route
+            out['routed'] = model._run(pkg('serving').Query([sr], cs_loc, None, None, None), 'score_items', items).cpu()    # the model's own route
             out['replicated_shared'] = vp.score_items([sr], table, cs_loc, items[0]).cpu()
             out['replicated_drop'] = vp.score_items([sr], table, cs_loc, items, listed=listed, drop_listed=True).cpu()
             out['data_parallel_drop'] = vp.score_items([sr[mine]], table, cs_loc, items[mine], listed=listed[mine, :4 + rank],

@@ -43,7 +43,8 @@ def run_rank(rank, world, port, outdir):
         with torch.no_grad():
             out['norm'] = vp.norm([sr], table, cs_loc, bias=bias, group=group).cpu()
             out['norm_plain'] = vp.norm([sr], table, cs_loc).cpu()
-            out['norm_routed'] = model._norm_of([sr], cs_loc, None, None, None, False, bias=bias, group=group).cpu()
+            out['norm_routed'] = model._run(pkg('serving').Query([sr], cs_loc, None, None, None, False, dict(bias=bias, group=group)),
+                                            'norm').cpu()
             out['norm_drop'] = vp.norm([sr], table, cs_loc, listed=listed, drop_listed=True, bias=bias, group=group).cpu()
             out['norm_dp'] = vp.norm([sr[mine]], table, cs_loc, data_parallel=True, bias=bias, group=group[mine]).cpu()
             out['norm_dp_drop'] = vp.norm([sr[mine]], table, cs_loc, listed=listed[mine, :4 + rank], drop_listed=True,

@@ -57,8 +57,8 @@ def run_rank(rank, world, port, outdir):
             out['target'], out['floor'] = target.cpu(), floor.cpu()
             out['ahead'] = vp.ahead_many([sr], table, cs_loc, items, target, **kw).cpu()
             out['ahead_floor'] = vp.ahead_many([sr], table, cs_loc, items, target, floor=floor, **kw).cpu()
-            out['ahead_routed'] = model._route('ahead_many')[0]([sr], table, cs_loc, items, target, None, None, listed, True,
-                                                                bias=bias, group=group).cpu()
+            out['ahead_routed'] = model._run(pkg('serving').Query([sr], cs_loc, None, None, listed, True, dict(bias=bias, group=group)),
+                                            'ahead_many', items, target).cpu()
             out['ahead_dp'] = vp.ahead_many([sr[mine]], table, cs_loc, items[mine], target[mine], listed=listed[mine, :4 + rank],
                                             drop_listed=True, data_parallel=True, bias=bias, group=group[mine],
                                             floor=floor[mine]).cpu()

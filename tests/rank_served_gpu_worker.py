@@ -65,8 +65,8 @@ def run_rank(rank, world, port, outdir):
             out['target'], out['floor'] = target.cpu(), floor.cpu()
             out['ahead'] = vp.ahead([sr], table, cs_loc, labels, target, **kw).cpu()
             out['ahead_floor'] = vp.ahead([sr], table, cs_loc, labels, target, floor=floor, **kw).cpu()
-            out['ahead_routed'] = model._route('ahead')[0]([sr], table, cs_loc, labels, target, None, None, listed, True,
-                                                           bias=bias, group=group).cpu()
+            out['ahead_routed'] = model._run(pkg('serving').Query([sr], cs_loc, None, None, listed, True, dict(bias=bias, group=group)),
+                                            'ahead', labels, target).cpu()
             out['ahead_dp'] = vp.ahead([sr[mine]], table, cs_loc, labels[mine], target[mine], listed=listed[mine, :4 + rank],
                                        drop_listed=True, data_parallel=True, bias=bias, group=group[mine], floor=floor[mine]).cpu()
         out['served'] = model.served_rank(sr, labels=labels, exclude_seen=True, item_bias=bias, item_group=group).cpu()

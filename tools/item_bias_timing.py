@@ -5,7 +5,7 @@ call, p10 / p90 as the spread.
   select C = 1 K = 20 and C = 3 K = 100, each: no bias | zero bias [V] | half the catalogue -inf | [4, V] with random groups
   score_items M = 100 and M = 1000, C = 1: no bias | bias [V] with half the catalogue -inf | [4, V] with random groups
   before: score_logp(...) + bias, topk(20) for C = 1; the three-matrix mixture + bias, topk(100) for C = 3
-  the model-level check of item_bias / item_group (_ScoringMixin._item_bias: one pass over the bias, one device-to-host read)
+  the model-level check of item_bias / item_group (serving.ServingMixin._item_bias: one pass over the bias, one device-to-host read)
 Prints a markdown table (and writes it with --out).
 usage (GPU box, under its own time limit):  timeout -k 10 300 python tools/item_bias_timing.py --out profiles/item_bias_timing.md"""
 import argparse

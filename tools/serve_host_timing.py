@@ -5,8 +5,9 @@ d 256): median of N device-event timed calls after warm-up, rows alternating cal
   1-rank shard: the same MSGIFSR with a dist.VocabParallel of one rank attached (no collective is issued): the same five calls,
                 and `route`: VocabParallel.target_rank / select / sample / norm / score_items alone on scoring arguments
                 computed once - the sharded routes without the model in front of them
-Writes the raw per-call times as JSON ({part: {row: [us]}}) and prints the medians.  To compare two commits, copy this file into
-a checkout of the other one beside the same libsrec_hip.so and run the two alternately, each run a process of its own.
+Writes the raw per-call times as JSON ({part: {row: [us]}}) and prints the medians.  To compare two commits, run each checkout's
+own copy of this file beside the same libsrec_hip.so, the two alternately, each run a process of its own (_scoring_args
+returns a record since serving.py; before, the bare five operands).
 usage (GPU box, under its own time limit):  timeout -k 10 300 python tools/serve_host_timing.py --out serve_host.json"""
 import argparse
 import importlib
@@ -73,7 +74,7 @@ def main():
         a, b = (a, b) if isinstance(a, tuple) else ((a,), (b,))
         same = same and all(torch.equal(x, y) for x, y in zip(a, b))
     with torch.no_grad():
-        srs, cs, oe, oi, li = ms._scoring_args(mg3, exclude_seen=False)
+        srs, cs, oe, oi, li = ms._scoring_args(mg3, exclude_seen=False)[:5]        # (a serving.Query: its five operands)
         E = ms._table()
         out['route'] = timed({
             'route target_rank': lambda: vp.target_rank(srs, E, cs, labels, oe, oi, li),
