@@ -807,6 +807,25 @@ int srec_score_ahead_many(const void* served, const int* items, const float* tar
 int srec_diversify(const float* X, int ld_x, long n_rows, const int* row, const float* s, int B, int M, int K, int d,
                    float theta, int* pick, float* val, float* mmr, float* ild, void* stream);
 
+/* ---- serving: per-category caps on an ordered pool - "at most caps[c] items of category c in the list" (cap_select.hip) ----
+ * Per session an ORDERED pool of P slots: ids[b * P + i] a global item id, s[b * P + i] its value (what srec_score_select /
+ * srec_score_select_many_order wrote).  A slot is FILLED iff 0 <= ids < n_items; anything else is an unfilled slot, never
+ * dereferenced and never picked.  c_i = category[ids[b * P + i]] (category: int32 [n_items]); c_i < 0 or c_i >= G: the item
+ * has no category and is always accepted - caps (int32 [G]) and the counters are never indexed with it.  Otherwise the slot
+ * is accepted iff the number of EARLIER filled slots of the session with the same category is < caps[c_i] (which equals
+ * "earlier accepted ones < cap": the greedy over a partition matroid, the optimum); caps[c] <= 0: category c is never shown.
+ * Duplicate ids in a pool each count.
+ * pick [B, K] int32: the slot numbers of the first K accepted slots in slot order, -1 once they run out.  val [B, K]: s[pick]
+ * copied bit for bit, -INFINITY in the tail.  kept [B] = min(K, number accepted).  scanned [B]: the pool slots consumed - the
+ * index after the K-th accepted slot, or P when fewer than K were accepted; slots at or past it are not part of the result.
+ * One workgroup per session, integer logic only, no atomics, no workspace: a session's result is the same bits in any batch.
+ * SREC_BAD_ARG and no launch unless 1 <= K <= P <= SREC_CAP_MAXP, 1 <= G <= SREC_CAP_MAXG (64 KB of int32 counters in LDS
+ * beside the chunk state), n_items >= 0, every pointer non-null and aligned to 4 bytes.  B <= 0 returns 0. */
+#define SREC_CAP_MAXP 4096
+#define SREC_CAP_MAXG 16384
+int srec_cap_select(const int* ids, const float* s, int B, int P, int K, const int* category, long n_items, const int* caps,
+                    int G, int* pick, float* val, int* kept, int* scanned, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

@@ -464,6 +464,10 @@ class HipLocal:
         """ops.diversify over rows the caller has bounded (checked): (val [B,k], pick [B,k], mmr [B,k], ild [B])"""
         return self.ops.diversify(X, row, val, k, diversity, checked=True)
 
+    def cap_select(self, ids, val, rule, k):
+        """ops.cap_select over a pool whose ids the select kernels wrote (checked): (val [B,k], pick [B,k], kept [B], scanned [B])"""
+        return self.ops.cap_select(ids, val, rule, k, checked=True)
+
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
 
@@ -1100,6 +1104,28 @@ class VocabParallel:
         row = torch.arange(B * M, device=ids.device, dtype=torch.int32).view(B, M)
         row = torch.where(ids < 0, torch.full_like(row, -1), row)
         return self.local.diversify(buf.reshape(B * M, d), row, val, k, diversity)
+
+    def cap_select(self, ids, val, rule, k, data_parallel=False):
+        """the per-category caps of ops.cap_select over the sharded table (val [B,k], pick [B,k], kept [B], scanned [B]): ids
+        [B, P] GLOBAL item ids of every session's ordered pool (-1 = unfilled), val [B, P] their values - what select() /
+        select_many() returned, the same on every rank (data_parallel: this rank's own sessions, as they returned them).  The
+        rule is over global ids and replicated, and the caps look at nothing but the pool: no row of the table is read, so
+        there is NO collective - every rank runs the kernel on the pool it holds and gets the single-device call's result,
+        bit for bit."""
+        return self.local.cap_select(ids, val, rule, k)
+
+    cap = cap_select        # (the name of the served call: ServingMixin._ROUTES)
+
+    def any_session(self, flag, data_parallel=False):
+        """host bool, the SAME on every rank: is `flag` (bool [B], one entry per session) set for any session of the call?
+        A caller that branches on it between two sharded calls (recommend_capped: whether the batch goes to the larger pool,
+        whose selection is a chain of collectives) must branch alike on every rank.  Replicated sessions: every rank holds
+        the same flags, no collective.  data_parallel: the flags are the rank's own sessions', so ONE max-all-reduce of one
+        integer makes the ranks agree before the device-to-host read."""
+        any_ = flag.any().to(torch.int32).reshape(1)
+        if data_parallel and _active(self.group):
+            all_reduce_(any_, dist.ReduceOp.MAX, self.group)
+        return bool(any_.item())
 
     # ---- replicated-parameter gradients: bucketed all-reduce, launched in backward order ----------------------------------
     N_BUCKETS = 3

@@ -2,6 +2,7 @@
 nodes, top-K, target rank, top-N select (and beyond 128 items), the scores of given items and the (B, V) log-probabilities, with the workspaces and argument conventions they share.
 ops.py keeps the GEMM wrappers and the tests' switches (reached through the module object at call time) and re-exports this."""
 import ctypes as _ct
+import numbers
 from collections import namedtuple
 
 import torch
@@ -1086,6 +1087,139 @@ def diversify(X, row, val, k, diversity, checked=False):
     lib.srec_diversify(ptr(X), _ld(X), n, ptr(row), ptr(val), B, M, k, d, diversity, ptr(pick), ptr(out_val), ptr(mmr),
                        ptr(ild), stream())
     return out_val, pick, mmr, ild
+
+
+# per-category caps on a served list: category int32 [num_items] (-1: the item has none), caps int32 [G], G (cap_rule builds it)
+CapRule = namedtuple('CapRule', 'category caps G')
+
+
+def _int_vector(who, what, x, device):
+    """x (an integer tensor or sequence) as a 1-D integer tensor on `device` (None: where it is), ValueError otherwise"""
+    try:
+        x = torch.as_tensor(x, device=device).detach()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError('%s: %s must be an integer tensor or sequence' % (who, what)) from None
+    if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool or x.dim() != 1:
+        raise ValueError('%s: %s must be a 1-D integer tensor or sequence, got %s %s' % (who, what, x.dtype, tuple(x.shape)))
+    return x
+
+
+def cap_rule(num_items, item_category, max_per_category, device=None):
+    """CapRule(category int32 [num_items], caps int32 [G], G): the rule "at most caps[c] items of category c in a served list"
+    as cap_select and the models' recommend_capped take it.  item_category: an integer tensor or sequence [num_items] over
+    GLOBAL item ids with values in [-1, G), -1 = the item has no category and is never capped.  max_per_category: an int >= 0
+    for every category (G = the largest category + 1, at least 1), or an integer tensor or sequence [G]; a cap of 0 means
+    the category is never shown.  ValueError for a wrong length, a non-integer dtype, a category < -1 or >= G, a negative
+    cap, and G > SREC_CAP_MAXG (the counters of csrc/cap_select.hip live in LDS).  Pure torch, at the price of ONE
+    device-to-host read: a server builds the rule once and passes the record from then on."""
+    who, gmax = 'cap_rule', CONST['SREC_CAP_MAXG']
+    num_items = int(num_items)
+    cat = _int_vector(who, 'item_category', item_category, device)
+    if cat.numel() != num_items:
+        raise ValueError('%s: item_category has %d entries for %d items' % (who, cat.numel(), num_items))
+    cat = cat.to(torch.int64)
+    one = isinstance(max_per_category, numbers.Integral) and not isinstance(max_per_category, bool)
+    if one:
+        caps = None
+        if max_per_category < 0:
+            raise ValueError('%s: max_per_category = %d; a cap is >= 0' % (who, max_per_category))
+    elif isinstance(max_per_category, (bool, numbers.Number)):
+        raise ValueError('%s: max_per_category must be an int or an integer tensor or sequence, got %r' % (who, max_per_category))
+    else:
+        caps = _int_vector(who, 'max_per_category', max_per_category, cat.device).to(torch.int64)
+        if not 1 <= caps.numel() <= gmax:
+            raise ValueError('%s: %d categories; csrc/cap_select.hip counts between 1 and %d' % (who, caps.numel(), gmax))
+    seen = [cat.min(), cat.max()] if num_items > 0 else [cat.new_tensor(-1)] * 2
+    lo, hi, cap_lo = torch.stack(seen + [cat.new_tensor(0) if one else caps.min()]).tolist()     # the one device-to-host read
+    if lo < -1:
+        raise ValueError('%s: category %d; categories are in [0, G), or -1 for an item without one' % (who, lo))
+    if cap_lo < 0:
+        raise ValueError('%s: max_per_category holds the cap %d; a cap is >= 0' % (who, cap_lo))
+    if one:
+        G = max(hi + 1, 1)
+        if G > gmax:
+            raise ValueError('%s: %d categories; csrc/cap_select.hip counts at most %d' % (who, G, gmax))
+        caps = torch.full((G,), min(int(max_per_category), 2 ** 31 - 1), dtype=torch.int64, device=cat.device)
+    G = caps.numel()
+    if hi >= G:
+        raise ValueError('%s: category %d; max_per_category names %d categories' % (who, hi, G))
+    return CapRule(cat.to(torch.int32).contiguous(), caps.clamp(max=2 ** 31 - 1).to(torch.int32).contiguous(), G)
+
+
+def cap_rule_check(who, rule):
+    """rule as a CapRule whose tensors agree with each other, or ValueError in the words of `who`.  No device read: the
+    VALUES are cap_rule's business (and the kernel never indexes out of range whatever they are)"""
+    if not isinstance(rule, CapRule):
+        raise ValueError('%s: rule must be the record ops.cap_rule returns, got %s' % (who, type(rule).__name__))
+    cat, caps, G = rule
+    if not (torch.is_tensor(cat) and cat.dtype == torch.int32 and cat.dim() == 1 and torch.is_tensor(caps)
+            and caps.dtype == torch.int32 and caps.dim() == 1 and isinstance(G, int) and caps.numel() == G
+            and 1 <= G <= CONST['SREC_CAP_MAXG']):
+        raise ValueError('%s: rule must hold category int32 [num_items], caps int32 [G] and 1 <= G <= %d (ops.cap_rule builds it)'
+                         % (who, CONST['SREC_CAP_MAXG']))
+    return rule
+
+
+def cap_k(who, k, P=None):
+    """k of a capped list as the library takes it, or ValueError in the words of `who`: 1 .. SREC_CAP_MAXP (and <= P, the
+    pool, when given: P itself in 1 .. SREC_CAP_MAXP)"""
+    pmax = CONST['SREC_CAP_MAXP']
+    k = int(k)
+    if P is not None and not 1 <= int(P) <= pmax:
+        raise ValueError('%s: a pool of %d slots per session; csrc/cap_select.hip takes between 1 and %d' % (who, P, pmax))
+    if k < 1 or k > (pmax if P is None else int(P)):
+        raise ValueError('%s: k = %d; csrc/cap_select.hip keeps between 1 and %s items per session'
+                         % (who, k, '%d' % pmax if P is None else 'the pool\'s %d' % P))
+    return k
+
+
+def cap_select(ids, val, rule, k, checked=False):
+    """(val fp32 [B,k], pick int32 [B,k], kept int32 [B], scanned int32 [B]): the first k slots of an ORDERED pool per session
+    that respect the per-category caps of `rule` (cap_rule's record) - csrc/cap_select.hip, one workgroup per session, integer
+    logic only: no [B, P] host read, no loop per session.  Slot i of session b holds the item ids[b, i] and the value
+    val[b, i] - what score_select / score_select_many return; ids < 0 is an unfilled slot.
+      c_i = rule.category[ids[b, i]]; -1: the item has no category and is always accepted;
+      otherwise the slot is accepted iff fewer than rule.caps[c_i] EARLIER filled slots of the session have category c_i
+      (= fewer than that many earlier accepted ones: the greedy over a partition matroid, which is the optimum).
+    Duplicate ids each count.  pick: the slot numbers of the first k accepted slots in slot order, -1 once they run out; the
+    returned val: val[pick] copied bit for bit, -inf in the tail; kept = min(k, accepted); scanned: the pool slots consumed -
+    the index after the k-th accepted slot, or P with fewer than k (slots past it play no part in the result).
+    ids: [B, P] of any integer dtype; val: fp32 [B, P] (views are taken as they are: made contiguous here);
+    1 <= k <= P <= 4096; ids, val and the rule's tensors on ONE device (nothing is moved).  Wrong shapes, dtypes, devices, k
+    and rule raise ValueError before any launch, and - unless checked=True, the caller vouches - so does an id >= num_items
+    (one max, one device-to-host read).  Under checked=True an id outside
+    [0, num_items) is an unfilled slot; the kernel never dereferences it."""
+    who = 'cap_select'
+    rule = cap_rule_check(who, rule)
+    ids, val = ids.detach(), val.detach()
+    if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() != 2:
+        raise ValueError('%s: ids must be an integer tensor [B, P], got %s %s' % (who, ids.dtype, tuple(ids.shape)))
+    if val.dtype != torch.float32 or val.shape != ids.shape:
+        raise ValueError('%s: val must be fp32 %s like ids, got %s %s' % (who, tuple(ids.shape), val.dtype, tuple(val.shape)))
+    B, P = ids.shape
+    k = cap_k(who, k, P)
+    n = rule.category.numel()
+    dev = rule.category.device
+    if not (ids.device == val.device == dev == rule.caps.device):
+        raise ValueError('%s: ids (%s), val (%s) and the rule (%s, %s) must be on one device (ops.cap_rule(..., device=) places '
+                         'the rule)' % (who, ids.device, val.device, dev, rule.caps.device))
+    if not checked and B > 0:
+        hi = int(ids.max())                                         # the one device-to-host read
+        if hi >= n:
+            raise ValueError('%s: item id %d; the rule covers %d items (a negative id is an unfilled slot)' % (who, hi, n))
+    if ids.dtype != torch.int32:                                    # (an id beyond int32 must not wrap into the catalogue)
+        ids = torch.where((ids < 0) | (ids >= n), torch.full_like(ids, -1), ids)
+    ids = ids.to(torch.int32).contiguous()
+    val = val.contiguous()
+    out_val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    pick = torch.empty(B, k, device=dev, dtype=torch.int32)
+    kept = torch.empty(B, device=dev, dtype=torch.int32)
+    scanned = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return out_val, pick, kept, scanned
+    lib.srec_cap_select(ptr(ids), ptr(val), B, P, k, ptr(rule.category), n, ptr(rule.caps), rule.G, ptr(pick), ptr(out_val),
+                        ptr(kept), ptr(scanned), stream())
+    return out_val, pick, kept, scanned
 
 
 def _logp_cols(sr, ld_sr, table, cs, lse):

@@ -1,4 +1,4 @@
-"""The serving surface every model shares: recommend / recommend_many / recommend_diverse, sample, cutoff, log_mass,
+"""The serving surface every model shares: recommend / recommend_many / recommend_diverse / recommend_capped, sample, cutoff, log_mass,
 score_items / rerank, served_rank / rank_items, and the evaluation calls topk / target_rank.
 
 ServingMixin is the base of srgnn._ScoringMixin, which supplies what it needs of a model: _table, _state, _col_scale, _lse,
@@ -66,6 +66,7 @@ class ServingMixin:
     _ROUTES = {'target_rank': ('score_rank', {}), 'select': ('score_select', {}), 'sample': ('score_sample', {}),
                'select_many': ('score_select_many', {}),
                'norm': ('score_norm', {}), 'cutoff': ('score_cutoff', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
+               'cap': ('cap_select', {'checked': True}),            # (the pool's ids are the select kernels')
                'score_items': ('score_items', {'checked': True}),   # (model.score_items looked; sample() passes the kernel's ids)
                'ahead': ('score_ahead', {}), 'ahead_many': ('score_ahead_many', {})}
 
@@ -79,7 +80,7 @@ class ServingMixin:
         return getattr(ops, fn), kw
 
     def _run(self, q, name, *lead, **kw):
-        """served call `name` (a key of _ROUTES but 'diversify', which scores nothing) over the Query q.  The one place that
+        """served call `name` (a key of _ROUTES but 'diversify' and 'cap', which score nothing) over the Query q.  The one place that
         knows the routes' positional order: (srs, table, cs, *lead, off_ex, off_in, listed, drop_listed - not for
         'target_rank', which drops nothing - then keywords only).  lead: k | items | (labels, target) | (items, target), as
         the route takes them; kw: keywords of the call beyond the route's own and the bias (the criteria of cutoff, floor=,
@@ -231,6 +232,76 @@ class ServingMixin:
         """(val, pick, mmr, ild) of ops.diversify over the rows of the item table at the global ids [B, M] (-1: unfilled)"""
         fn, kw = self._route('diversify')
         return fn(self._table(), ids, val, k, diversity, **kw)
+
+    def recommend_capped(self, *inputs, k=20, item_category=None, max_per_category=None, rule=None, pool=None, exclude_seen=False,
+                         item_bias=None, item_group=None, renormalize=False, return_complete=False):
+        """(log_probs fp32 [B,k], item_ids int32 [B,k]) in served order: the first k items of recommend()'s order, with the same
+        keywords, that respect "at most m items of one category (brand, seller) in the list", 1 <= k <= 4096.  Walking the
+        served order and skipping an item once its category is full is the optimum under such caps (a partition matroid), so
+        the catalogue pass stays what it is and ONE more launch walks the ordered pool (csrc/cap_select.hip; ops.cap_select,
+        one workgroup per session, integer logic only): no [B, 4096] host read, no Python loop per session.  The values are
+        the pool's own numbers at the kept items, bit for bit; a list that runs short ends in (-inf, -1) slots.
+        The rule: either item_category ([num_items] integers over GLOBAL item ids, -1 = no category, never capped) with
+        max_per_category (an int >= 0 for every category, or one cap per category; 0 = never shown) - ops.cap_rule builds the
+        record at the price of one device-to-host read - or rule=, the record itself, which a server builds once.  Not both.
+        The pool: pool=P (k <= P <= 4096) takes that pool alone - recommend(k=P) for P <= 128, recommend_many(k=P) beyond.
+        pool=None with k <= 128: the one-pass pool of 128 items first; a session is COMPLETE when it kept k items or the pool's
+        last slot is unfilled (the pool was the whole eligible catalogue); ONE device-to-host read of "any session incomplete"
+        follows, and if so the WHOLE batch is re-run on a 4096-item pool and that result is returned - one pool per call, so
+        the values never mix two kernels' round-off.  pool=None with k > 128: the 4096-item pool directly.
+        return_complete=True adds a bool [B]: False where even the last pool used was full and gave fewer than k items (the
+        catalogue may hold more that fit).  exclude_seen, item_bias / item_group, renormalize, mixtures (MSGIFSR fusion /
+        extra) and row-sharded tables mean what they mean in recommend(): the caps themselves need no collective
+        (dist.VocabParallel.cap_select), and where every rank feeds its own sessions the "any session incomplete" flag is
+        max-all-reduced first, so that all ranks enter the 4096-item pool's collectives together or not at all.  Runs
+        in eval mode under torch.no_grad(); k, pool, the rule and item_bias / item_group are checked before anything of the
+        model runs (ValueError).
+        Out of scope: caps together with sample() or recommend_diverse(), more than one attribute per item, minimum quotas,
+        and served_rank() / rank_items() under caps."""
+        who = 'recommend_capped'
+        k = ops.cap_k(who, k)
+        if pool is not None:
+            pool = int(pool)
+            if not k <= pool <= ops.CONST['SREC_CAP_MAXP']:
+                raise ValueError('%s: pool = %d; it holds at least the k = %d items asked for and at most %d (recommend_many()\'s '
+                                 'limit)' % (who, pool, k, ops.CONST['SREC_CAP_MAXP']))
+        rule = self._cap_rule(who, item_category, max_per_category, rule)
+        bias = self._item_bias(who, item_bias, item_group)
+        stages = [pool] if pool is not None else [128, ops.CONST['SREC_CAP_MAXP']] if k <= 128 else [ops.CONST['SREC_CAP_MAXP']]
+        fn, kw = self._route('cap')
+        with _Serving(self):
+            q = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+            for P in stages:
+                val, ids = self._run(q, 'select' if P <= 128 else 'select_many', P)
+                pval, pick, kept, _ = fn(ids, val, rule, k, **kw)
+                complete = (kept == k) | (ids[:, -1] < 0)
+                if P == stages[-1] or not self._any_session(~complete):      # (the one device-to-host read, only with a stage to go)
+                    break
+            picked = ids.gather(1, pick.clamp(min=0).long())
+            out = pval, torch.where(pick < 0, torch.full_like(picked, -1), picked)
+            return out + (complete,) if return_complete else out
+
+    def _any_session(self, flag):
+        """host bool: is flag [B] set for any session of the call - of ANY rank's sessions over a sharded table fed
+        data-parallel (dist.VocabParallel.any_session: one small all-reduce), so that every rank takes the same branch
+        between two sharded calls, which are chains of collectives.  One device-to-host read"""
+        if self.shard is not None:
+            return self.shard.any_session(flag, data_parallel=self.shard.eval_data_parallel)
+        return bool(flag.any())
+
+    def _cap_rule(self, who, item_category, max_per_category, rule):
+        """the ops.CapRule of recommend_capped on the table's device: `rule` as given (its category covers the catalogue) or
+        built from item_category / max_per_category - one of the two, ValueError otherwise"""
+        pair = item_category is not None or max_per_category is not None
+        if (rule is not None) == pair or (pair and (item_category is None or max_per_category is None)):
+            raise ValueError('%s: give either rule= (the record of ops.cap_rule) or item_category= with max_per_category=' % who)
+        n, dev = self._num_items(), self._table().device
+        if rule is None:
+            return ops.cap_rule(n, item_category, max_per_category, device=dev)
+        rule = ops.cap_rule_check(who, rule)
+        if rule.category.numel() != n:
+            raise ValueError('%s: the rule covers %d items, the catalogue has %d' % (who, rule.category.numel(), n))
+        return ops.CapRule(rule.category.to(dev), rule.caps.to(dev), rule.G)
 
     def list_diversity(self, item_ids):
         """fp32 [B]: the intra-list diversity of given lists, 1 - the mean cosine between the item-table rows of every pair of

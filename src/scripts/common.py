@@ -124,6 +124,81 @@ def read_catalog(p, args):
     return kw
 
 
+def cap_flags(p):
+    """the per-category caps of scripts/recommend.py (ops.cap_rule builds the rule, model.recommend_capped applies it)"""
+    p.add_argument('--categories', default=None, metavar='FILE',
+                   help='the category (brand, seller) of the items: one `id:category` per line, categories are integers >= 0; '
+                        'an unlisted item has none and is never capped')
+    p.add_argument('--max-per-category', type=int, default=None, metavar='N',
+                   help='--categories: at most N items of one category in every printed list (0: none at all)')
+    p.add_argument('--category-caps', default=None, metavar='FILE',
+                   help='--categories: one `category:cap` per line, instead of N for the categories it names')
+
+
+def read_pair_file(path, what):
+    """([first, ...], [second, ...]): one `first:second` pair of integers per non-empty line (`what` names the format);
+    ValueError names the line that is none"""
+    a, b = [], []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            line = line.strip()
+            if not line:
+                continue
+            parts = line.split(':')
+            try:
+                if len(parts) != 2:
+                    raise ValueError
+                a.append(int(parts[0]))
+                b.append(int(parts[1]))
+            except ValueError:
+                raise ValueError('%s line %d: `%s` is not `%s`' % (path, n, line, what)) from None
+    return a, b
+
+
+MAX_CATEGORIES = 16384      # SREC_CAP_MAXG (include/srec.h)
+
+
+def read_caps(p, args):
+    """the keywords item_category / max_per_category of model.recommend_capped from --categories / --max-per-category /
+    --category-caps, or None when none is given.  Read and checked against <dataset-dir>/num_items.txt before any model is
+    built; p.error() for a cap flag without --categories, --categories without a cap, a file that cannot be read, an item
+    outside the catalogue, an item named twice, a category outside [0, MAX_CATEGORIES) and a negative cap.  A category without
+    a cap of its own (--category-caps alone) is not capped."""
+    if args.categories is None:
+        if args.max_per_category is not None or args.category_caps is not None:
+            p.error('--max-per-category / --category-caps cap the categories of --categories: give the file')
+        return None
+    if args.max_per_category is None and args.category_caps is None:
+        p.error('--categories goes with --max-per-category N or --category-caps FILE')
+    if args.max_per_category is not None and args.max_per_category < 0:
+        p.error('--max-per-category must be >= 0')
+    try:
+        with open(Path(args.dataset_dir) / 'num_items.txt') as f:
+            num_items = int(f.readline())
+        ids, cats = read_pair_file(args.categories, 'id:category')
+        named = read_pair_file(args.category_caps, 'category:cap') if args.category_caps is not None else ([], [])
+    except (OSError, ValueError) as e:
+        p.error(str(e))
+    item_category = [-1] * num_items
+    for i, c in zip(ids, cats):
+        if not 0 <= i < num_items:
+            p.error('--categories: item id %d; ids are in [0, %d)' % (i, num_items))
+        if not 0 <= c < MAX_CATEGORIES:
+            p.error('--categories: category %d of item %d; categories are in [0, %d)' % (c, i, MAX_CATEGORIES))
+        if item_category[i] >= 0:
+            p.error('--categories: item %d is named twice' % i)
+        item_category[i] = c
+    for c, m in zip(*named):
+        if not 0 <= c < MAX_CATEGORIES:
+            p.error('--category-caps: category %d; categories are in [0, %d)' % (c, MAX_CATEGORIES))
+        if m < 0:
+            p.error('--category-caps: the cap %d of category %d; a cap is >= 0' % (m, c))
+    caps = [2 ** 31 - 1 if args.max_per_category is None else min(args.max_per_category, 2 ** 31 - 1)] * (max(cats + named[0] + [0]) + 1)
+    for c, m in zip(*named):
+        caps[c] = min(m, 2 ** 31 - 1)
+    return dict(item_category=item_category, max_per_category=caps)
+
+
 def build_model(model_name, args, num_items, device, caps=None):
     """(model on the CPU, evaluation collate_fn, training collate_fn) of a launcher's flags (run, scripts/recommend.py)"""
     from src.models import LESSR, MSGIFSR, NISER, SRGNN

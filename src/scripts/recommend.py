@@ -22,13 +22,20 @@ matrix).  A session that keeps fewer than --top items prints fewer pairs.  Only 
 --diversity THETA re-ranks the --pool M most probable items of every session (default min(128, max(4 top, top))) into a slate
 of --top items that trades probability for coverage (model.recommend_diverse: greedy MMR on the cosine of the item rows, one
 more kernel, csrc/diversify.hip); the output has the same format, in PICK order, with the items' own values.  Not together
-with --sample."""
+with --sample.
+--categories FILE (`id:category` per line; an unlisted item has no category) with --max-per-category N prints the first --top
+items of the served order that hold at most N items of one category (model.recommend_capped: one more kernel over the ordered
+pool, csrc/cap_select.hip); --category-caps FILE (`category:cap` per line) sets the cap of the categories it names instead of
+N.  --pool M (--top <= M <= 4096) fixes the pool the list is taken from; by default the 128 most probable items, and the 4096
+most probable ones for a batch in which some session's list runs short.  Same output format, served order.  Not together with
+--sample or --diversity."""
 import argparse
 import sys
 
-from common import DEFAULTS, build_model, catalog_flags, model_flags, read_catalog, variant_flags
+from common import DEFAULTS, build_model, cap_flags, catalog_flags, model_flags, read_caps, read_catalog, variant_flags
 
 MAX_TOP = 128           # SREC_SELECT_MAXK (include/srec.h)
+MAX_CAP_POOL = 4096     # SREC_CAP_MAXP
 
 
 def read_session_file(path):
@@ -95,8 +102,10 @@ def parser(model):
                    help='re-rank the --pool most probable items into a diversified slate: each pick maximises value - THETA * '
                         '(largest cosine to the items picked so far); finite, >= 0; printed in pick order')
     p.add_argument('--pool', type=int, default=None, metavar='M',
-                   help='--diversity: items per session the slate is picked from, --top <= M <= %d (default: min(%d, 4 * top))'
-                        % (MAX_TOP, MAX_TOP))
+                   help='--diversity: items per session the slate is picked from, --top <= M <= %d (default: min(%d, 4 * top)); '
+                        '--categories: the pool the capped list is taken from, --top <= M <= %d (default: %d, then %d)'
+                        % (MAX_TOP, MAX_TOP, MAX_CAP_POOL, MAX_TOP, MAX_CAP_POOL))
+    cap_flags(p)
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -133,8 +142,14 @@ def parse(argv=None):
             p.error('--diversity must be finite and >= 0')
         if args.pool is not None and not args.top <= args.pool <= MAX_TOP:
             p.error('--pool must be between --top and %d' % MAX_TOP)
-    elif args.pool is not None:
-        p.error('--pool goes with --diversity')
+    elif args.pool is not None and args.categories is None:
+        p.error('--pool goes with --diversity or --categories')
+    if args.categories is not None:
+        if args.sample or args.diversity is not None:
+            p.error('--categories caps the most probable items in served order: not together with --sample or --diversity')
+        if args.pool is not None and not args.top <= args.pool <= MAX_CAP_POOL:
+            p.error('--pool must be between --top and %d' % MAX_CAP_POOL)
+    args.caps = read_caps(p, args)
     args.catalog = read_catalog(p, args)
     return args
 
@@ -158,6 +173,7 @@ def main(argv=None):
     ops.weights_changed()
     model.table_written()
     item_bias = None if args.catalog is None else ops.catalog_bias(num_items, device=device, **args.catalog)
+    rule = None if args.caps is None else ops.cap_rule(num_items, device=device, **args.caps)
 
     sessions = read_session_file(args.sessions)
     cap = session_capacity(ops.limits(), getattr(args, 'order', 1), args.exclude_seen or getattr(args, 'extra', False))
@@ -180,6 +196,10 @@ def main(argv=None):
                 val, idx = model.recommend_diverse(*[x.to(device) for x in inputs], k=args.top, diversity=args.diversity,
                                                    pool=args.pool, exclude_seen=args.exclude_seen, item_bias=item_bias,
                                                    renormalize=args.renormalize)
+            elif rule is not None:
+                val, idx = model.recommend_capped(*[x.to(device) for x in inputs], k=args.top, rule=rule, pool=args.pool,
+                                                  exclude_seen=args.exclude_seen, item_bias=item_bias,
+                                                  renormalize=args.renormalize)
             else:
                 val, idx = model.recommend(*[x.to(device) for x in inputs], k=args.top, exclude_seen=args.exclude_seen,
                                            item_bias=item_bias, renormalize=args.renormalize)
