@@ -826,6 +826,38 @@ int srec_diversify(const float* X, int ld_x, long n_rows, const int* row, const 
 int srec_cap_select(const int* ids, const float* s, int B, int P, int K, const int* category, long n_items, const int* caps,
                     int G, int* pick, float* val, int* kept, int* scanned, void* stream);
 
+/* ---- serving: calibrated slates - the greedy re-rank of a pool towards a target category distribution (calibrate.hip; Steck,
+ * "Calibrated Recommendations", RecSys 2018).  The soft counterpart of the caps above; plain arguments, no workspace.
+ * Per session a pool of M <= SREC_SELECT_MAXK slots: ids[b * M + i] a global item id and s[b * M + i] its value, as
+ * srec_score_select wrote them.  A slot is FILLED iff 0 <= ids < n_items; anything else is never dereferenced and never
+ * picked.  c_i = category[ids[b * M + i]] (category: int32 [n_items]); c_i < 0: the item has no category.
+ * The target: T <= SREC_CALIB_MAXT pairs (tcat[b * T + j], tw[b * T + j]) of a CATEGORY id (not an item id) and a weight;
+ * tcat < 0 or tw <= 0 is an empty pair, duplicates add up; T == 0 (tcat, tw may be NULL): no target.  Category ids are only
+ * compared, never used as an index: there is no upper bound on them.
+ * P_c = the sum of the weights of category c, S = {c : P_c > 0}, W = sum_{c in S} P_c.  W > 0: p_c = P_c / W; otherwise the
+ * session has NO TARGET and its calibration term is 0.
+ * After some picks n_c is the number of picks of category c and N the number of picks with ANY category >= 0, in S or not
+ * (uncategorised picks count nowhere);
+ *   KL(n, N) = sum_{c in S} p_c log(p_c / ((1 - a) n_c / max(N, 1) + a p_c)),   a = smooth in (0, 1) (Steck: 0.01).
+ * Greedy, t = 0 .. K-1: for every filled slot i not yet picked let (n', N') be the state with the slot added (unchanged when
+ * c_i < 0) and m_t(i) = (1 - w) s_i - w KL(n', N'), w = weight in [0, 1]; the pick is the largest m_t, ties to the LOWER slot.
+ * w == 0: m = s_i exactly, the target is not looked at.  s_i == -INFINITY: m = -INFINITY, never NaN (also at w == 1).  No
+ * target: KL = 0.  m depends on a slot only through s_i and its category: the calibration term is formed once per distinct
+ * category, so two slots with the same s that share a category, or are both outside S, or both uncategorised, get the same
+ * bits (and the lower slot wins).
+ * pick [B, K] int32: the slot numbers in pick order, -1 once the filled slots run out.  val [B, K]: s[pick] copied bit for
+ * bit, -INFINITY in the tail.  obj [B, K] (may be NULL): the winning m_t rounded to fp32, -INFINITY in the tail.  kl [B] (may
+ * be NULL): KL of the final picks rounded to fp32, 0 without a target.
+ * The sums of the weights, the calibration term and m_t are formed and compared in DOUBLE (weight and smooth are widened): a
+ * float64 loop on the host gives the same picks wherever its best two candidates differ by more than double round-off.
+ * One workgroup per session, no atomics, no workspace: a session's result is the same bits in any batch.
+ * SREC_BAD_ARG and no launch unless 1 <= K <= M <= SREC_SELECT_MAXK, 0 <= T <= SREC_CALIB_MAXT, n_items >= 0, 0 <= weight <= 1,
+ * 0 < smooth < 1 (NaN fails both), ids / s / category / pick / val non-null, tcat / tw non-null when T > 0, every pointer
+ * aligned to 4 bytes.  B <= 0 returns 0. */
+#define SREC_CALIB_MAXT 128
+int srec_calibrate(const int* ids, const float* s, int B, int M, int K, const int* category, long n_items, const int* tcat,
+                   const float* tw, int T, float weight, float smooth, int* pick, float* val, float* obj, float* kl, void* stream);
+
 /* ---- fused read-out head (headf.hip): msgifsr.py:124-155 (AttnReadout.forward) + :269-273 (fc_sr, F.normalize) for all live
  * orders in ONE launch, a group of SREC_HEAD_SESSIONS sessions per workgroup; replaces the {U, Vq} GEMM / srec_seg_attn_fwd /
  * {s} GEMM / split-K sum / srec_normalize_fwd chain of the grouped head in bf16 mode (d = 128 / 256).  desc: HOST

@@ -468,6 +468,11 @@ class HipLocal:
         """ops.cap_select over a pool whose ids the select kernels wrote (checked): (val [B,k], pick [B,k], kept [B], scanned [B])"""
         return self.ops.cap_select(ids, val, rule, k, checked=True)
 
+    def calibrate(self, ids, val, category, k, weight, tcat, tw, alpha):
+        """ops.calibrate over a pool whose ids the select kernel wrote and a target the caller has looked at (checked):
+        (val [B,k], pick [B,k], obj [B,k], kl [B])"""
+        return self.ops.calibrate(ids, val, category, k, weight, tcat, tw, alpha, checked=True)
+
     def workspace(self, B, V, d, device):
         return self.ops.CEWorkspace(B, V, d, device)
 
@@ -1115,6 +1120,15 @@ class VocabParallel:
         return self.local.cap_select(ids, val, rule, k)
 
     cap = cap_select        # (the name of the served call: ServingMixin._ROUTES)
+
+    def calibrate(self, ids, val, category, k, weight, tcat, tw, alpha, data_parallel=False):
+        """the calibrated re-rank of ops.calibrate over the sharded table (val [B,k], pick [B,k], obj [B,k], kl [B]): ids [B, M]
+        GLOBAL item ids of every session's pool (-1 = unfilled), val [B, M] their values - what select() returned, the same on
+        every rank (data_parallel: this rank's own sessions, as they returned them) - and tcat / tw [B, T] the sessions' target
+        pairs (None: no target).  The category vector is over global ids and replicated, as the cap rule is, and the re-rank
+        looks at nothing but the pool and the target: no row of the table is read, so there is NO collective - every rank
+        runs the kernel on the pool it holds and gets the single-device call's result, bit for bit."""
+        return self.local.calibrate(ids, val, category, k, weight, tcat, tw, alpha)
 
     def any_session(self, flag, data_parallel=False):
         """host bool, the SAME on every rank: is `flag` (bool [B], one entry per session) set for any session of the call?

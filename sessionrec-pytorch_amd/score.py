@@ -1222,6 +1222,108 @@ def cap_select(ids, val, rule, k, checked=False):
     return out_val, pick, kept, scanned
 
 
+def calibrate_scalars(who, k, weight, alpha, M=None):
+    """(k, weight, alpha) as the library takes them, or ValueError in the words of `who`: k in 1 .. 128 (and <= M, the pool,
+    when given: M itself in 1 .. 128), weight a number in [0, 1], alpha (the smoothing of the calibration term) in (0, 1).
+    weight and alpha come back ROUNDED TO fp32, as the kernel receives them.  No launch, no library call"""
+    kmax = CONST['SREC_SELECT_MAXK']
+    k = int(k)
+    if M is not None and not 1 <= int(M) <= kmax:
+        raise ValueError('%s: a pool of %d slots per session; csrc/calibrate.hip takes between 1 and %d' % (who, M, kmax))
+    if k < 1 or k > (kmax if M is None else int(M)):
+        raise ValueError('%s: k = %d; csrc/calibrate.hip picks between 1 and %s items per session'
+                         % (who, k, '%d' % kmax if M is None else 'the pool\'s %d' % M))
+    try:
+        weight, alpha = float(weight), float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError('%s: weight and alpha must be numbers, got %r and %r' % (who, weight, alpha)) from None
+    if not 0.0 <= weight <= 1.0:
+        raise ValueError('%s: weight = %r; it must be in [0, 1]' % (who, weight))
+    weight, alpha = _ct.c_float(weight).value, _ct.c_float(alpha).value
+    if not 0.0 < alpha < 1.0:
+        raise ValueError('%s: alpha = %r; it must be in (0, 1) (as fp32)' % (who, alpha))
+    return k, weight, alpha
+
+
+def calibrate(ids, val, category, k, weight, target_cat=None, target_w=None, alpha=0.01, checked=False):
+    """(val fp32 [B,k], pick int32 [B,k], obj fp32 [B,k], kl fp32 [B]): the greedy CALIBRATED re-rank of a pool of M <= 128
+    slots per session (Steck, "Calibrated Recommendations", RecSys 2018; csrc/calibrate.hip, one workgroup per session: no
+    loop of launches, no [B, M, categories] temporaries).  Slot i of session b holds the item ids[b, i] and the value
+    val[b, i] - what score_select returns; ids < 0 is an unfilled slot.  c_i = category[ids[b, i]], < 0: the item has none.
+      target: the pairs (target_cat[b, j], target_w[b, j]) of a CATEGORY id and a weight, T <= 128 per session; a category
+      < 0 or a weight <= 0 is an empty pair, duplicates add up.  P_c = the weights of category c summed, S = {c: P_c > 0},
+      p_c = P_c / sum_S P_c.  No pair at all (or target_cat = target_w = None): no target, the calibration term is 0.
+      state: n_c picks of category c, N picks with any category >= 0 (in S or not);
+      KL(n, N) = sum_{c in S} p_c log(p_c / ((1 - alpha) n_c / max(N, 1) + alpha p_c))
+      for t = 0 .. k-1: m_t(i) = (1 - weight) val[i] - weight KL(state with slot i added) over the filled slots not yet
+      picked; the pick is the largest m_t, ties to the lower slot.  weight 0: m_t = val[i]; val[i] = -inf: m_t = -inf.
+    pick: the slot numbers in pick order, -1 once the filled slots run out; the returned val: val[pick] copied bit for bit,
+    -inf in the tail; obj: the winning m_t; kl: KL of the final picks, 0 without a target.  The term, the sums and m_t are
+    double inside the kernel, weight and alpha fp32 (calibrate_scalars returns the rounded values).
+    ids: [B, M] of any integer dtype; val: fp32 [B, M] (views are made contiguous here); category: int32 [num_items];
+    target_cat: [B, T] of any integer dtype with target_w floating [B, T], or both None; 1 <= k <= M <= 128; everything on
+    ONE device (nothing is moved).  Wrong shapes, dtypes, devices and scalars raise ValueError before any launch, and -
+    unless checked=True, the caller vouches - so do an id >= num_items and a weight that is NaN, infinite or negative (ONE
+    device-to-host read for both).  Under checked=True an id outside [0, num_items) is an unfilled slot; the kernel never
+    dereferences it.  A category id beyond int32 is mapped to an empty pair."""
+    who = 'calibrate'
+    if not (torch.is_tensor(category) and category.dtype == torch.int32 and category.dim() == 1):
+        raise ValueError('%s: category must be an int32 tensor [num_items]' % who)
+    ids, val = ids.detach(), val.detach()
+    if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() != 2:
+        raise ValueError('%s: ids must be an integer tensor [B, M], got %s %s' % (who, ids.dtype, tuple(ids.shape)))
+    if val.dtype != torch.float32 or val.shape != ids.shape:
+        raise ValueError('%s: val must be fp32 %s like ids, got %s %s' % (who, tuple(ids.shape), val.dtype, tuple(val.shape)))
+    B, M = ids.shape
+    k, weight, alpha = calibrate_scalars(who, k, weight, alpha, M)
+    n, dev = category.numel(), category.device
+    if (target_cat is None) != (target_w is None):
+        raise ValueError('%s: target_cat and target_w go together' % who)
+    T = 0
+    if target_cat is not None:
+        tc, tw = target_cat.detach(), target_w.detach()
+        if tc.is_floating_point() or tc.is_complex() or tc.dtype == torch.bool or tc.dim() != 2 or tc.shape[0] != B:
+            raise ValueError('%s: target_cat must be an integer tensor [%d, T], got %s %s' % (who, B, tc.dtype, tuple(tc.shape)))
+        if not tw.is_floating_point() or tw.shape != tc.shape:
+            raise ValueError('%s: target_w must be a floating tensor %s like target_cat, got %s %s'
+                             % (who, tuple(tc.shape), tw.dtype, tuple(tw.shape)))
+        T = tc.shape[1]
+        if T > CONST['SREC_CALIB_MAXT']:
+            raise ValueError('%s: %d target pairs per session; csrc/calibrate.hip takes at most %d' % (who, T, CONST['SREC_CALIB_MAXT']))
+        if not (tc.device == tw.device == dev):
+            raise ValueError('%s: the target (%s, %s) must be on the device of category (%s)' % (who, tc.device, tw.device, dev))
+        tw = tw.to(torch.float32)                                   # (the weights the kernel sees are the ones checked)
+    if not (ids.device == val.device == dev):
+        raise ValueError('%s: ids (%s), val (%s) and category (%s) must be on one device' % (who, ids.device, val.device, dev))
+    if not checked and B > 0:
+        flags = [ids.max() >= n]
+        if T > 0:
+            flags.append(~(torch.isfinite(tw) & (tw >= 0)).all())
+        bad = torch.stack(flags).tolist()                           # the one device-to-host read
+        if bad[0]:
+            raise ValueError('%s: an item id >= %d, the items category covers (a negative id is an unfilled slot)' % (who, n))
+        if len(bad) > 1 and bad[1]:
+            raise ValueError('%s: target_w holds a NaN, infinite or negative weight' % who)
+    if ids.dtype != torch.int32:                                    # (an id beyond int32 must not wrap into the catalogue)
+        ids = torch.where((ids < 0) | (ids >= n), torch.full_like(ids, -1), ids)
+    ids = ids.to(torch.int32).contiguous()
+    val = val.contiguous()
+    if T > 0:
+        if tc.dtype != torch.int32:
+            tc = torch.where((tc < 0) | (tc > 2 ** 31 - 1), torch.full_like(tc, -1), tc)
+        tc = tc.to(torch.int32).contiguous()
+        tw = tw.contiguous()
+    out_val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    pick = torch.empty(B, k, device=dev, dtype=torch.int32)
+    obj = torch.empty(B, k, device=dev, dtype=torch.float32)
+    kl = torch.empty(B, device=dev, dtype=torch.float32)
+    if B == 0:
+        return out_val, pick, obj, kl
+    lib.srec_calibrate(ptr(ids), ptr(val), B, M, k, ptr(category), n, ptr(tc) if T > 0 else None, ptr(tw) if T > 0 else None, T,
+                       weight, alpha, ptr(pick), ptr(out_val), ptr(obj), ptr(kl), stream())
+    return out_val, pick, obj, kl
+
+
 def _logp_cols(sr, ld_sr, table, cs, lse):
     """[B, V] log-probabilities z[b, v] - lse[b] of the rows of `table` (fp32): a view of a buffer whose rows are padded to
     a multiple of 4 columns"""

@@ -1,5 +1,6 @@
-"""The serving surface every model shares: recommend / recommend_many / recommend_diverse / recommend_capped, sample, cutoff, log_mass,
-score_items / rerank, served_rank / rank_items, and the evaluation calls topk / target_rank.
+"""The serving surface every model shares: recommend / recommend_many / recommend_diverse / recommend_capped /
+recommend_calibrated, sample, cutoff, log_mass, score_items / rerank, served_rank / rank_items, the list measures
+list_diversity / list_calibration, and the evaluation calls topk / target_rank.
 
 ServingMixin is the base of srgnn._ScoringMixin, which supplies what it needs of a model: _table, _state, _col_scale, _lse,
 session_repr, shard.  Every served call scores with one Query - the operands of the score, the exclude_seen flag and the
@@ -67,6 +68,7 @@ class ServingMixin:
                'select_many': ('score_select_many', {}),
                'norm': ('score_norm', {}), 'cutoff': ('score_cutoff', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
                'cap': ('cap_select', {'checked': True}),            # (the pool's ids are the select kernels')
+               'calibrate': ('calibrate', {'checked': True}),       # (... and the target is _calibration_target's)
                'score_items': ('score_items', {'checked': True}),   # (model.score_items looked; sample() passes the kernel's ids)
                'ahead': ('score_ahead', {}), 'ahead_many': ('score_ahead_many', {})}
 
@@ -80,7 +82,7 @@ class ServingMixin:
         return getattr(ops, fn), kw
 
     def _run(self, q, name, *lead, **kw):
-        """served call `name` (a key of _ROUTES but 'diversify' and 'cap', which score nothing) over the Query q.  The one place that
+        """served call `name` (a key of _ROUTES but 'diversify', 'cap' and 'calibrate', which score nothing) over the Query q.  The one place that
         knows the routes' positional order: (srs, table, cs, *lead, off_ex, off_in, listed, drop_listed - not for
         'target_rank', which drops nothing - then keywords only).  lead: k | items | (labels, target) | (items, target), as
         the route takes them; kw: keywords of the call beyond the route's own and the bias (the criteria of cutoff, floor=,
@@ -256,8 +258,8 @@ class ServingMixin:
         max-all-reduced first, so that all ranks enter the 4096-item pool's collectives together or not at all.  Runs
         in eval mode under torch.no_grad(); k, pool, the rule and item_bias / item_group are checked before anything of the
         model runs (ValueError).
-        Out of scope: caps together with sample() or recommend_diverse(), more than one attribute per item, minimum quotas,
-        and served_rank() / rank_items() under caps."""
+        Out of scope: caps together with sample() or recommend_diverse(), more than one attribute per item, minimum quotas
+        (recommend_calibrated is the soft answer to those), and served_rank() / rank_items() under caps."""
         who = 'recommend_capped'
         k = ops.cap_k(who, k)
         if pool is not None:
@@ -302,6 +304,125 @@ class ServingMixin:
         if rule.category.numel() != n:
             raise ValueError('%s: the rule covers %d items, the catalogue has %d' % (who, rule.category.numel(), n))
         return ops.CapRule(rule.category.to(dev), rule.caps.to(dev), rule.G)
+
+    def recommend_calibrated(self, *inputs, k=20, weight=0.5, item_category=None, target=None, alpha=0.01, pool=None,
+                             exclude_seen=False, item_bias=None, item_group=None, renormalize=False, return_kl=False):
+        """(log_probs fp32 [B,k], item_ids int32 [B,k]) in PICK order: a slate of k items whose category mix follows the
+        session's own - CALIBRATION (Steck, "Calibrated Recommendations", RecSys 2018), the soft counterpart of
+        recommend_capped's hard caps and the answer to "minimum quotas": a session that was 70 % shoes and 30 % socks gets a
+        list of roughly that mix, and no per-category number is asked of the operator.  The greedy re-rank (csrc/calibrate.hip,
+        ops.calibrate: ONE more launch, one workgroup per session, no loop of launches) of the `pool` most probable items.
+        The pool is exactly what recommend(k=pool, same keywords) returns (pool: default min(128, max(4 k, k)); k <= pool
+        <= 128), so exclude_seen, item_bias / item_group, renormalize, mixtures and row-sharded tables mean what they mean
+        there (the re-rank itself needs no collective: dist.VocabParallel.calibrate).
+        item_category: [num_items] integers over GLOBAL item ids, < 0 = the item has no category; moved to the table's device
+        once - an int32 tensor already there is taken as it is, with no device read (category ids are only compared: any
+        int32 is fine).  target=None: the session's own DISTINCT items (_session_items), weight 1 each, through
+        item_category - how often an item was clicked is not seen.  target=(cats [B,T], weights [B,T]): an explicit sparse
+        target of category ids (not item ids) and weights >= 0, finite; a category < 0 or a weight 0 is an empty pair,
+        duplicates add up; at most 128 pairs per session (ValueError otherwise, also for a batch with a session of more
+        than 128 distinct items under target=None).  A session without any pair has no target: it gets the plain order.
+        With p the target distribution over its categories S, n_c the picks of category c and N the picks with any category,
+          KL = sum_{c in S} p_c log(p_c / ((1 - alpha) n_c / max(N, 1) + alpha p_c))
+        and step t picks the pool slot with the largest (1 - weight) value - weight KL(picks so far + the slot), ties to the
+        better-ranked slot; weight in [0, 1], alpha in (0, 1).  weight=0 returns the first k columns of recommend(k=pool).
+        The values are the pool's own numbers at the picks, bit for bit; unfilled slots (fewer than k eligible items) are
+        (-inf, -1).  return_kl=True adds kl fp32 [B], the KL of the returned list (list_calibration of it).  Runs in eval
+        mode under torch.no_grad(); k, weight, alpha, pool, item_category, the target and item_bias / item_group are
+        checked before anything of the model runs.
+        Out of scope: calibration together with caps, MMR (recommend_diverse) or sampling, pools beyond 128, several
+        categories per item, recency-weighted default targets, and served_rank() / rank_items() under calibration."""
+        who = 'recommend_calibrated'
+        k, weight, alpha = ops.calibrate_scalars(who, k, weight, alpha)
+        pool = min(128, max(4 * k, k)) if pool is None else int(pool)
+        if not k <= pool <= 128:
+            raise ValueError('%s: pool = %d; it holds at least the k = %d items asked for and at most 128 (recommend()\'s limit)'
+                             % (who, pool, k))
+        category = self._item_category(who, item_category)
+        tcat, tw = self._calibration_target(who, category, target, inputs)
+        bias = self._item_bias(who, item_bias, item_group)
+        fn, kw = self._route('calibrate')
+        with _Serving(self):
+            q = self._served(*inputs, exclude_seen=exclude_seen, renormalize=renormalize, **bias)
+            val, ids = self._run(q, 'select', pool)
+            pval, pick, _, kl = fn(ids, val, category, k, weight, tcat, tw, alpha, **kw)
+            picked = ids.gather(1, pick.clamp(min=0).long())
+            out = pval, torch.where(pick < 0, torch.full_like(picked, -1), picked)
+            return out + (kl,) if return_kl else out
+
+    def list_calibration(self, *inputs, item_ids, item_category=None, target=None, alpha=0.01):
+        """fp32 [B]: how far the category mix of given lists is from the target's - the KL of recommend_calibrated (0 for a
+        session without a target) - the number that compares a plain, a diversified, a capped and a calibrated list.
+        item_ids: [B, M] integer ids, -1 = padding, M <= 128; an id < -1 or >= num_items raises ValueError before anything
+        is launched.  item_category, target (None: the distinct items of the sessions in `inputs`) and alpha as in
+        recommend_calibrated.  The kernel of recommend_calibrated at weight 0 over zero values with k = M; the model itself
+        does not run.  Under torch.no_grad()."""
+        who = 'list_calibration'
+        ids = item_ids.detach()
+        if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() != 2:
+            raise ValueError('%s: item_ids must be an integer tensor [B, M], got %s %s' % (who, ids.dtype, tuple(ids.shape)))
+        M = ids.shape[1]
+        _, _, alpha = ops.calibrate_scalars(who, M, 0.0, alpha, M)
+        category = self._item_category(who, item_category)
+        tcat, tw = self._calibration_target(who, category, target, inputs)
+        self._check_ids(who, ids)
+        fn, kw = self._route('calibrate')
+        with torch.no_grad():
+            ids = ids.to(category.device)
+            return fn(ids, torch.zeros(ids.shape, device=ids.device, dtype=torch.float32), category, M, 0.0, tcat, tw, alpha, **kw)[3]
+
+    def _item_category(self, who, item_category):
+        """item_category as int32 [num_items] on the table's device.  An int32 tensor there is taken as it is (no device read:
+        the kernel only compares category ids); anything else is converted at the price of one read of its extremes"""
+        if item_category is None:
+            raise ValueError('%s: item_category= (the category of every item, [num_items] integers) is needed' % who)
+        n, dev = self._num_items(), self._table().device
+        cat = ops._int_vector(who, 'item_category', item_category, None)
+        if cat.numel() != n:
+            raise ValueError('%s: item_category has %d entries for %d items' % (who, cat.numel(), n))
+        if cat.dtype == torch.int32:
+            return cat.to(dev).contiguous()
+        if n > 0 and int(cat.max()) > 2 ** 31 - 1:
+            raise ValueError('%s: item_category holds a category id beyond int32' % who)
+        return cat.clamp(min=-1).to(device=dev, dtype=torch.int32).contiguous()
+
+    def _calibration_target(self, who, category, target, inputs):
+        """(tcat int32 [B,T], tw fp32 [B,T]) on the device of category, or (None, None) for T = 0.  target=None: the sessions'
+        own distinct items through category, weight 1 each.  target=(cats, weights): checked - shapes, dtypes, at most
+        SREC_CALIB_MAXT pairs, weights finite and >= 0 (one device-to-host read)"""
+        tmax, dev = ops.CONST['SREC_CALIB_MAXT'], category.device
+        if target is None:
+            if not inputs:
+                raise ValueError('%s: target=None takes the sessions\' own items: give the model\'s inputs, or target=' % who)
+            listed = self._session_items(inputs[0]).to(dev).long()
+            if listed.shape[1] > tmax:
+                raise ValueError('%s: a session of %d distinct items; the target holds at most %d pairs per session'
+                                 % (who, listed.shape[1], tmax))
+            if listed.shape[1] == 0 or category.numel() == 0:
+                return None, None
+            cats = category[listed.clamp(0, category.numel() - 1)]
+            return torch.where(listed < 0, torch.full_like(cats, -1), cats).contiguous(), torch.ones(listed.shape, device=dev)
+        try:
+            cats, weights = target
+            cats, weights = torch.as_tensor(cats).detach(), torch.as_tensor(weights).detach()
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError('%s: target must be a pair (categories [B, T], weights [B, T])' % who) from None
+        if cats.is_floating_point() or cats.is_complex() or cats.dtype == torch.bool or cats.dim() != 2:
+            raise ValueError('%s: the target\'s categories must be an integer tensor [B, T], got %s %s' % (who, cats.dtype, tuple(cats.shape)))
+        if not weights.is_floating_point() or weights.shape != cats.shape:
+            raise ValueError('%s: the target\'s weights must be a floating tensor %s like its categories, got %s %s'
+                             % (who, tuple(cats.shape), weights.dtype, tuple(weights.shape)))
+        if cats.shape[1] > tmax:
+            raise ValueError('%s: %d target pairs per session; at most %d' % (who, cats.shape[1], tmax))
+        if cats.shape[1] == 0:
+            return None, None
+        weights = weights.to(device=dev, dtype=torch.float32)
+        if not bool((torch.isfinite(weights) & (weights >= 0)).all()):          # the one device-to-host read
+            raise ValueError('%s: the target holds a NaN, infinite or negative weight' % who)
+        cats = cats.to(dev)
+        if cats.dtype != torch.int32:
+            cats = torch.where((cats < 0) | (cats > 2 ** 31 - 1), torch.full_like(cats, -1), cats).to(torch.int32)
+        return cats.contiguous(), weights.contiguous()
 
     def list_diversity(self, item_ids):
         """fp32 [B]: the intra-list diversity of given lists, 1 - the mean cosine between the item-table rows of every pair of

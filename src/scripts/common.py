@@ -199,6 +199,53 @@ def read_caps(p, args):
     return dict(item_category=item_category, max_per_category=caps)
 
 
+def calibrate_flags(p):
+    """the calibrated slates of scripts/recommend.py (model.recommend_calibrated)"""
+    p.add_argument('--calibrate', type=float, default=None, metavar='W',
+                   help='--categories: re-rank the --pool most probable items into a slate whose category mix follows the '
+                        'session\'s own: each pick maximises (1 - W) * value - W * KL(target, list so far); W in [0, 1]; printed '
+                        'in pick order')
+    p.add_argument('--calibrate-smooth', type=float, default=None, metavar='A',
+                   help='--calibrate: the smoothing of the KL term, 0 < A < 1 (default: 0.01)')
+
+
+def read_calibration(p, args):
+    """the keywords item_category / weight / alpha of model.recommend_calibrated from --calibrate / --calibrate-smooth /
+    --categories, or None without --calibrate.  Read and checked against <dataset-dir>/num_items.txt before any model is
+    built; p.error() for --calibrate-smooth alone, --calibrate without --categories or with a cap flag, a number out of
+    range, a file that cannot be read, an item outside the catalogue, an item named twice and a category outside
+    [0, 2^31)."""
+    if args.calibrate is None:
+        if args.calibrate_smooth is not None:
+            p.error('--calibrate-smooth smooths the term of --calibrate W: give the weight')
+        return None
+    if args.categories is None:
+        p.error('--calibrate follows the category mix of the session: give --categories FILE (`id:category` per line)')
+    if args.max_per_category is not None or args.category_caps is not None:
+        p.error('--calibrate is the soft counterpart of --max-per-category / --category-caps: give one of the two')
+    if not 0.0 <= args.calibrate <= 1.0:
+        p.error('--calibrate must be in [0, 1]')
+    alpha = 0.01 if args.calibrate_smooth is None else args.calibrate_smooth
+    if not 0.0 < alpha < 1.0:
+        p.error('--calibrate-smooth must be in (0, 1)')
+    try:
+        with open(Path(args.dataset_dir) / 'num_items.txt') as f:
+            num_items = int(f.readline())
+        ids, cats = read_pair_file(args.categories, 'id:category')
+    except (OSError, ValueError) as e:
+        p.error(str(e))
+    item_category = [-1] * num_items
+    for i, c in zip(ids, cats):
+        if not 0 <= i < num_items:
+            p.error('--categories: item id %d; ids are in [0, %d)' % (i, num_items))
+        if not 0 <= c < 2 ** 31:
+            p.error('--categories: category %d of item %d; categories are in [0, 2^31)' % (c, i))
+        if item_category[i] >= 0:
+            p.error('--categories: item %d is named twice' % i)
+        item_category[i] = c
+    return dict(item_category=item_category, weight=args.calibrate, alpha=alpha)
+
+
 def build_model(model_name, args, num_items, device, caps=None):
     """(model on the CPU, evaluation collate_fn, training collate_fn) of a launcher's flags (run, scripts/recommend.py)"""
     from src.models import LESSR, MSGIFSR, NISER, SRGNN

@@ -28,11 +28,17 @@ items of the served order that hold at most N items of one category (model.recom
 pool, csrc/cap_select.hip); --category-caps FILE (`category:cap` per line) sets the cap of the categories it names instead of
 N.  --pool M (--top <= M <= 4096) fixes the pool the list is taken from; by default the 128 most probable items, and the 4096
 most probable ones for a batch in which some session's list runs short.  Same output format, served order.  Not together with
---sample or --diversity."""
+--sample or --diversity.
+--calibrate W (in [0, 1]) with --categories FILE re-ranks the --pool M most probable items (--top <= M <= 128, default
+min(128, max(4 top, top))) into a slate whose category mix follows that of the session's own items (model.recommend_calibrated:
+greedy on (1 - W) * value - W * KL(target, list), one more kernel, csrc/calibrate.hip); --calibrate-smooth A (default 0.01)
+is the smoothing of the KL term.  Same output format, in PICK order, with the items' own values.  Not together with --sample,
+--diversity, --max-per-category or --category-caps."""
 import argparse
 import sys
 
-from common import DEFAULTS, build_model, cap_flags, catalog_flags, model_flags, read_caps, read_catalog, variant_flags
+from common import (DEFAULTS, build_model, calibrate_flags, cap_flags, catalog_flags, model_flags, read_calibration, read_caps,
+                    read_catalog, variant_flags)
 
 MAX_TOP = 128           # SREC_SELECT_MAXK (include/srec.h)
 MAX_CAP_POOL = 4096     # SREC_CAP_MAXP
@@ -103,9 +109,11 @@ def parser(model):
                         '(largest cosine to the items picked so far); finite, >= 0; printed in pick order')
     p.add_argument('--pool', type=int, default=None, metavar='M',
                    help='--diversity: items per session the slate is picked from, --top <= M <= %d (default: min(%d, 4 * top)); '
-                        '--categories: the pool the capped list is taken from, --top <= M <= %d (default: %d, then %d)'
+                        '--categories: the pool the capped list is taken from, --top <= M <= %d (default: %d, then %d); '
+                        '--calibrate: as for --diversity'
                         % (MAX_TOP, MAX_TOP, MAX_CAP_POOL, MAX_TOP, MAX_CAP_POOL))
     cap_flags(p)
+    calibrate_flags(p)
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -144,12 +152,20 @@ def parse(argv=None):
             p.error('--pool must be between --top and %d' % MAX_TOP)
     elif args.pool is not None and args.categories is None:
         p.error('--pool goes with --diversity or --categories')
-    if args.categories is not None:
+    if args.calibrate is not None:
+        if args.sample:
+            p.error('--calibrate re-ranks the most probable items and --sample draws them: give one of the two')
+        if args.diversity is not None:
+            p.error('--calibrate and --diversity are two re-ranks of the same pool: give one of the two')
+        if args.pool is not None and not args.top <= args.pool <= MAX_TOP:
+            p.error('--pool must be between --top and %d' % MAX_TOP)
+    elif args.categories is not None:
         if args.sample or args.diversity is not None:
             p.error('--categories caps the most probable items in served order: not together with --sample or --diversity')
         if args.pool is not None and not args.top <= args.pool <= MAX_CAP_POOL:
             p.error('--pool must be between --top and %d' % MAX_CAP_POOL)
-    args.caps = read_caps(p, args)
+    args.calibration = read_calibration(p, args)
+    args.caps = None if args.calibration is not None else read_caps(p, args)
     args.catalog = read_catalog(p, args)
     return args
 
@@ -174,6 +190,9 @@ def main(argv=None):
     model.table_written()
     item_bias = None if args.catalog is None else ops.catalog_bias(num_items, device=device, **args.catalog)
     rule = None if args.caps is None else ops.cap_rule(num_items, device=device, **args.caps)
+    calibration = args.calibration
+    if calibration is not None:           # (the category vector goes to the device once, as int32: no read per batch)
+        calibration = dict(calibration, item_category=th.tensor(calibration['item_category'], dtype=th.int32, device=device))
 
     sessions = read_session_file(args.sessions)
     cap = session_capacity(ops.limits(), getattr(args, 'order', 1), args.exclude_seen or getattr(args, 'extra', False))
@@ -196,6 +215,10 @@ def main(argv=None):
                 val, idx = model.recommend_diverse(*[x.to(device) for x in inputs], k=args.top, diversity=args.diversity,
                                                    pool=args.pool, exclude_seen=args.exclude_seen, item_bias=item_bias,
                                                    renormalize=args.renormalize)
+            elif calibration is not None:
+                val, idx = model.recommend_calibrated(*[x.to(device) for x in inputs], k=args.top, pool=args.pool,
+                                                      exclude_seen=args.exclude_seen, item_bias=item_bias,
+                                                      renormalize=args.renormalize, **calibration)
             elif rule is not None:
                 val, idx = model.recommend_capped(*[x.to(device) for x in inputs], k=args.top, rule=rule, pool=args.pool,
                                                   exclude_seen=args.exclude_seen, item_bias=item_bias,
