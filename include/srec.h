@@ -402,6 +402,13 @@ int srec_hg_live_rows(const void* desc, const void* lists, int* counts, void* st
 int srec_hg_drop_prep16_live(const float* x, const float* cnt, int rows, int D, float p, int seed, const int* counter, int salt,
                              float* ms, float* xc, float* rm, float* xres, float pa, long na, float* mk, void* xc16,
                              const void* desc, const void* lists, int* counts, void* stream);
+/* ... srec_hg_drop_prep (xc16 / desc + lists + counts nullable: else as _prep16 / _prep16_live) on rows that are formed in the same
+ * pass: Y [rows, D] = the row-normalised X_p stacked, inv [rows] their 1 / norm - arguments and results of srec_normalize_group_fwd
+ * (np <= 4 HOST arrays, sum nrow_p == rows; D <= 256: one wavefront per row).  Y is the x of the layer call. */
+int srec_hg_drop_prep_norm(int np, const void* X, const int* ld, const int* nrow, const void* dyn, float* Y, float* inv, int eps_mode,
+                           float eps, const float* cnt, int rows, int D, float p, int seed, const int* counter, int salt, float* ms,
+                           float* xc, float* rm, float* xres, float pa, long na, float* mk, void* xc16, const void* desc,
+                           const void* lists, int* counts, void* stream);
 /* (ms of srec_hg_drop_prep / _prep16 is nullable: srec_hg_drop_merge with ms = NULL recomputes the masks from p / seed / counter /
  * salt, the mask tensor is then neither written nor read) */
 int srec_hg_drop_merge(const float* t, int S, const float* ms, long n, float* dx, float p, int seed, const int* counter,
@@ -412,6 +419,25 @@ int srec_hg_drop_merge(const float* t, int S, const float* ms, long n, float* dx
 int srec_hg_pre_merge(const void* desc, const float* g, int ld_g, const float* t, int S, float* dx, int ld_dx, void* stream);
 int srec_hg_bwd(const void* desc, const float* x, int ld_x, const float* g, int ld_g, const unsigned char* arg, float* dx,
                 int ld_dx, float* ws, void* stream);
+/* The layer with its caller's L2 normalisations inside its own launches (node kernels only: H == 8, D % 8 == 0, D <= 256, at most 8
+ * relation instances into a type; anything else is SREC_BAD_ARG).  Each writes every byte, with the same value, that the pair of calls
+ * it stands for writes.
+ *   srec_hg_fwd_exit = srec_hg_fwd + srec_norm_perm_pick_fwd without the un-normalised out: allf [NT, D] / invr [NT] in per-session
+ *     order (cat_inv [NT]: stacked row -> concatenated row, -1 = capacity padding; there are as many concatenated as stacked rows),
+ *     the left D columns of pout[k] [B, .] (row stride ld_p[k]) = the normalised output row pick[k][b] (zeros for b >= *dynB or
+ *     a negative pick).  B = desc.B is the length of every pick list.  HOST arrays of npick <= 4.
+ *   srec_hg_bwd_exit = srec_norm_perm_pick_bwd + srec_hg_bwd: g [NT, D] is an OUTPUT, formed from g_allf (row stride ld_ga) and the
+ *     pick gradients g_pick[k] [B, D] (row stride ld_gp[k], entries nullable) by the score-gradient launch.
+ *   srec_hg_pre_merge_norm = srec_hg_pre_merge + srec_normalize_group_bwd without the stacked dx: the layer's x is Y [NT, D], the
+ *     normalised rows of one raw tensor per node type (inv [NT] their 1 / norm); dX[t] [ncap[t], D] (row stride ld[t]; HOST arrays of
+ *     n_types entries) receives the gradient of type t's raw rows. */
+int srec_hg_fwd_exit(const void* desc, const float* x, int ld_x, unsigned char* arg, const int* cat_inv, float* allf, float* invr,
+                     int npick, const void* pick, const void* pout, const int* ld_p, int eps_mode, float eps, void* stream);
+int srec_hg_bwd_exit(const void* desc, const float* x, int ld_x, float* g, int ld_g, const unsigned char* arg, float* dx, int ld_dx,
+                     float* ws, const int* cat_inv, const float* allf, const float* invr, const float* g_allf, int ld_ga, int npick,
+                     const void* pick, const void* g_pick, const int* ld_gp, void* stream);
+int srec_hg_pre_merge_norm(const void* desc, const float* g, int ld_g, const float* t, int S, const float* Y, const float* inv,
+                           const void* dX, const int* ld, void* stream);
 
 /* grouped, K-segmented bf16-operand GEMM (gemm_group_bf16.hip): up to 8 problems C_p [M,N] (+)= sum_s opA(A_ps) opB(B_ps)
  * in one launch.  desc: host srec_gemm_group (srec_hg.h).  mode 0: A [M,K], B [N,K] (nn.Linear forward); 1: A [M,K],

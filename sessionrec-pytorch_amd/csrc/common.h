@@ -64,6 +64,12 @@ static __device__ __forceinline__ int dyn_count(const int* dyn, int n_static) {
     return v < n_static ? v : n_static;
 }
 static __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+// 1 / norm of a row from its sum of squares.  eps_mode 0: 1/max(||x||, eps) (F.normalize)   1: 1/(||x|| + eps) (niser.py)
+// (rowops.hip's normalisation kernels and the MSHGNN layer kernels that carry a normalisation, hgat.hip)
+static __device__ __forceinline__ float inv_norm(float sumsq, int eps_mode, float eps) {
+    const float n = sqrtf(sumsq);
+    return eps_mode == 0 ? 1.f / fmaxf(n, eps) : 1.f / (n + eps);
+}
 
 // ---- dropout masks without a generator state: a counter-based hash.  key = f(host seed, per-step device counter, call-site
 // salt); element i of the masked tensor keeps its value (scaled by 1 / (1 - p)) iff hash(key, i) / 2^24 >= p.  The forward

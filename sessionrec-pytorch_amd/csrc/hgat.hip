@@ -54,6 +54,14 @@ __device__ __forceinline__ void st4(unsigned short* p, float4 v) {
     *reinterpret_cast<uint2*>(p) = __builtin_bit_cast(uint2, b);
 }
 
+// the normalisations a layer call may carry for its caller (srec_hg_fwd_exit / srec_hg_bwd_exit / srec_hg_pre_merge_norm, srec.h)
+struct HgExit {
+    const int* cat_inv; int npick; const int* pick[4];
+    float* allf; float* invr; float* pout[4]; int ld_p[4]; int eps_mode; float eps;        // forward: written
+    const float* gallf; int ld_ga; const float* gpick[4]; int ld_gp[4];                    // backward (allf / invr are read)
+};
+struct HgEntry { const float* Y; const float* inv; float* dX[MAXT]; int ld[MAXT]; };
+
 template <int N>
 __device__ __forceinline__ int find_range(const int (&start)[N], int n, int x) {
     int b = 0;
@@ -197,6 +205,11 @@ struct AggArgs {
     unsigned char* arg;
     int H, D;
     float slope;
+    // XF (the exit record of srec_hg_fwd_exit, hg_agg_node_kernel only): the output row leaves normalised, in per-session order, + the picks
+    const int* cat_inv;
+    float* allf; float* invr;
+    int npick; const int* pick[4]; float* pout[4]; int ld_p[4];
+    int eps_mode; float eps;
 };
 
 #ifdef SREC_HG_TIMING   // development probe (tools/hg_timing.py)
@@ -420,7 +433,12 @@ __device__ __forceinline__ void ld8f(const float* p, float (&f)[8]) {
     f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
 }
 
-template <typename T, int AGG_EIF, int WV>   // AGG_EIF: edges (x 4 row loads of 16 bytes) in flight per wave; WV: waves per SIMD
+// XF: the output row does not go to out - it is L2-normalised in the wavefront (npp_row's arithmetic, rowops.hip: per-lane partial
+// over columns 4 lane .. + 3, wave_sum, inv_norm) and written to allf[cat_inv[row]] (+ 1 / norm to invr) and to the pick row of
+// its session in every pick list that names it.  A stacked row past its type's live count zeroes one capacity-padding row of
+// allf / invr instead (there are as many of either), and the wavefronts of the first npick B rows also zero the pick rows of the
+// sessions past *dynB: every byte norm_perm_pick_fwd_kernel writes is written.
+template <typename T, int AGG_EIF, int WV, bool XF = false>   // AGG_EIF: edges (x 4 row loads of 16 bytes) in flight per wave; WV: waves per SIMD
 __global__ __launch_bounds__(256, WV) void hg_agg_node_kernel(AggArgs a) {
     __shared__ float sc[WPB][MAXH][MAXDEG];                        // general path only (a relation with > 8 in-edges)
     __shared__ int su[WPB][MAXDEG];
@@ -608,8 +626,10 @@ __global__ __launch_bounds__(256, WV) void hg_agg_node_kernel(AggArgs a) {
         if (ob > b || (ob == b && oh < bh)) { b = ob; bh = oh; }
         best[x] = b; bi[x] = bh;
     }
+    float o[8];
+#pragma unroll
+    for (int x = 0; x < 8; ++x) o[x] = 0.f;
     if (half == 0 && cok) {
-        float o[8];
         unsigned lo = 0u, hi = 0u;
         if (live) {
             float sm[8];
@@ -618,14 +638,66 @@ __global__ __launch_bounds__(256, WV) void hg_agg_node_kernel(AggArgs a) {
             for (int x = 0; x < 8; ++x) o[x] = best[x] + sm[x];   // + mean of the session's input features (nodes of this type)
 #pragma unroll
             for (int x = 0; x < 4; ++x) { lo |= (unsigned)bi[x] << (8 * x); hi |= (unsigned)bi[4 + x] << (8 * x); }
-        } else {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) o[x] = 0.f;
         }
-        float* op = a.out + (size_t)row * a.ld_out + c;
-        *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<float4*>(op + 4) = make_float4(o[4], o[5], o[6], o[7]);
+        if (!XF) {
+            float* op = a.out + (size_t)row * a.ld_out + c;
+            *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4*>(op + 4) = make_float4(o[4], o[5], o[6], o[7]);
+        }
         *reinterpret_cast<uint2*>(a.arg + (size_t)row * D + c) = make_uint2(lo, hi);
+    }
+    if (XF) {
+        // lane L takes columns 4 L .. 4 L + 3: one half of the 8 columns lane L >> 1 holds (columns >= D: zeros)
+        const int m = lane >> 1, c4 = lane * 4;
+        const bool up = lane & 1, cok4 = c4 < D;
+        float lo4[4], hi4[4];
+#pragma unroll
+        for (int x = 0; x < 4; ++x) { lo4[x] = __shfl(o[x], m, 64); hi4[x] = __shfl(o[4 + x], m, 64); }
+        float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (cok4) y = up ? make_float4(hi4[0], hi4[1], hi4[2], hi4[3]) : make_float4(lo4[0], lo4[1], lo4[2], lo4[3]);
+        const int NTs = a.row0[a.nt];
+        if (live) {
+            float s;
+            {
+                // row_sumsq (rowops.hip) squares the four columns of a 16-byte load with packed multiplies and adds them in x, y, z, w
+                // order - no fused multiply-add.  The row sits in registers here, where the compiler would contract: pinned.
+#pragma clang fp contract(off)
+                const float xx = y.x * y.x, yy = y.y * y.y, zz = y.z * y.z, ww = y.w * y.w;
+                s = 0.f + (((xx + yy) + zz) + ww);
+            }
+            const float iv = inv_norm(wave_sum(s), a.eps_mode, a.eps);
+            y.x *= iv; y.y *= iv; y.z *= iv; y.w *= iv;
+            const int r = a.cat_inv[row];
+            if (r >= 0 && r < NTs) {
+                if (cok4) *reinterpret_cast<float4*>(a.allf + (size_t)r * D + c4) = y;
+                if (lane == 0) a.invr[r] = iv;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < a.npick && (unsigned)sb < (unsigned)a.B && a.pick[k][sb] == row && cok4)
+                    *reinterpret_cast<float4*>(a.pout[k] + (size_t)sb * a.ld_p[k] + c4) = y;
+        } else {
+            int r = v;                                               // rank among the rows past their type's live count
+            int nlive = 0;
+#pragma unroll
+            for (int q = 0; q < MAXT; ++q)
+                if (q < a.nt) {
+                    const int lq = max(0, dyn_count(a.dyn_n[q], a.ncap[q]));
+                    nlive += lq;
+                    if (q < t) r += a.ncap[q];
+                    if (q <= t) r -= lq;
+                }
+            r += nlive;                                              // the capacity padding of allf starts behind the live rows
+            if (r >= 0 && r < NTs) {
+                if (cok4) *reinterpret_cast<float4*>(a.allf + (size_t)r * D + c4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (lane == 0) a.invr[r] = 0.f;
+            }
+        }
+        const int nB = dyn_count(a.dynB, a.B);
+        for (int jj = row; jj < a.npick * a.B; jj += NTs) {          // pick rows of the sessions past the live count, or without a pick: zeros
+            const int k = jj / a.B, b = jj - k * a.B;
+            if ((b >= nB || a.pick[k][b] < 0) && cok4) *reinterpret_cast<float4*>(a.pout[k] + (size_t)b * a.ld_p[k] + c4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
     }
 }
 
@@ -640,13 +712,19 @@ struct PreArgs {
     const float* rm_cnt; float rm_p; srec_rng rm_rng;    // rm_cnt [2, NT] != NULL: rm = cnt0 m0 + cnt1 m1 from the masks' hash
     float* dx; int ld_dx;
     const int* sess;                    // session of every stacked row (written by the forward's hg_dots launch)
+    // NORM (the entry record of srec_hg_pre_merge_norm): x = nY are normalised rows; d x goes through the normalisation into the types' raw gradients
+    const float* nY; const float* ninv;
+    float* ndX[MAXT]; int nld[MAXT];
 };
 
 // dx[row,:] = nres * g[row,:] + (1/n_session) * sum_{rows of the session} g   (residual + session-mean terms)
 // MERGE: ... + (sum_s t[0][s]) * ms0 + (sum_s t[1][s]) * ms1, the two convs' masked data gradients (S partial sums each, t [2, S,
 // NT, D] contiguous; masks recomputed from the hash of hg_drop_prep as for the residual scale) - the layer's whole d x in ONE
 // pass at the end of its backward instead of a pre-fill here and a read-modify-write in hg_drop_merge (srec_hg_pre_merge)
-template <bool MERGE>
+// NORM: the rows of x are the L2-normalised rows nY of one raw tensor per node type (normalize_group_fwd): the finished d x row
+// stays in registers, goes through normalize_group_bwd's arithmetic (same per-lane partial, same wave_sum) and is written to the
+// row's place in its type's raw-gradient tensor - dx itself is not written (nobody else reads it)
+template <bool MERGE, bool NORM = false>
 __global__ void hg_pre_kernel(PreArgs a, const float* __restrict__ tm = nullptr, int S = 0) {
     const int row = blockIdx.x * WPB + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= a.row0[a.nt]) return;
@@ -654,9 +732,10 @@ __global__ void hg_pre_kernel(PreArgs a, const float* __restrict__ tm = nullptr,
     const int v = row - a.row0[t];
     const bool live = v < dyn_count(a.dyn_n[t], a.ncap[t]);
     const int c = lane * 4;
-    if (c >= a.D) return;
+    const bool cok = c < a.D;
+    if (!NORM && !cok) return;                                 // (NORM: every lane stays for the row reduction)
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) {
+    if (live && cok) {
         const int* seg = a.seg[t];
         const int lo = a.sess[row];                        // (one load instead of a 5-round-trip search of the offsets)
         const int s0 = seg[lo], s1 = seg[lo + 1];
@@ -691,7 +770,7 @@ __global__ void hg_pre_kernel(PreArgs a, const float* __restrict__ tm = nullptr,
         o.x = o.x * inv + rs.x * gv.x; o.y = o.y * inv + rs.y * gv.y;
         o.z = o.z * inv + rs.z * gv.z; o.w = o.w * inv + rs.w * gv.w;
     }
-    if (MERGE) {
+    if (MERGE && cok) {
         const int NT = a.row0[a.nt];
         const size_t n = (size_t)NT * a.D, i = (size_t)row * a.D + c;
         float4 s0 = *reinterpret_cast<const float4*>(tm + i), s1 = *reinterpret_cast<const float4*>(tm + (size_t)S * n + i);
@@ -708,6 +787,23 @@ __global__ void hg_pre_kernel(PreArgs a, const float* __restrict__ tm = nullptr,
         o.y += s0.y * srec_keep(key, i0 + 1, p, sc) + s1.y * srec_keep(key, i1 + 1, p, sc);
         o.z += s0.z * srec_keep(key, i0 + 2, p, sc) + s1.z * srec_keep(key, i1 + 2, p, sc);
         o.w += s0.w * srec_keep(key, i0 + 3, p, sc) + s1.w * srec_keep(key, i1 + 3, p, sc);
+    }
+    if (NORM) {
+        float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+        float dot = 0.f;
+        if (live && cok) {
+            // (the expressions of normalize_group_bwd_kernel, token for token: whatever the compiler contracts there it contracts
+            // here - not pinned by a pragma, because the kernel this must equal is not pinned either; the tests compare the bytes)
+            y = *reinterpret_cast<const float4*>(a.nY + (size_t)row * a.D + c);
+            dot += y.x * o.x + y.y * o.y + y.z * o.z + y.w * o.w;
+        }
+        dot = wave_sum(dot);
+        const float iv = live ? a.ninv[row] : 0.f;
+        if (!cok) return;
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) r = make_float4(iv * (o.x - y.x * dot), iv * (o.y - y.y * dot), iv * (o.z - y.z * dot), iv * (o.w - y.w * dot));
+        *reinterpret_cast<float4*>(a.ndX[t] + (size_t)v * a.nld[t] + c) = r;
+        return;
     }
     *reinterpret_cast<float4*>(a.dx + (size_t)row * a.ld_dx + c) = o;
 }
@@ -735,6 +831,12 @@ struct DstArgs {
     const int* dyn_t[MAXT];
     int row0_t[MAXT + 1], ncap_t[MAXT], ninst_t[MAXT], inst_t[MAXT][8];
     int nt;
+    // XB (the exit record of srec_hg_bwd_exit, hg_bwd_dst_node_kernel only): g is derived here from the gradients of the normalised,
+    // per-session-ordered rows and written to gout for the later launches
+    float* gout;
+    const int* cat_inv; const int* sess;
+    const float* allf; const float* invr; const float* gallf; int ld_ga;
+    int npick; const int* pick[4]; const float* gpick[4]; int ld_gp[4];
 };
 
 // per (instance, destination), ALL heads in one wavefront: d(pre-activation score) of every in-edge -> DP[e,h];
@@ -855,7 +957,10 @@ __device__ __forceinline__ float head_sums8(const float (&ph)[MAXH], int lane, i
 // instances run in parallel, g / arg of the node are read once, the 8 values of an (edge, head) array are 16-byte accesses.
 // Same arithmetic per edge and the same reduction trees as hg_bwd_dst_kernel: bit-identical DP / der.  A node with more than
 // 8 in-edges in some relation takes the per-instance loop (the body of hg_bwd_dst_kernel).
-template <typename T, int DIF, int WV>   // DIF: edges (x 4 row loads) in flight together; WV: waves per SIMD
+// XB: the gradient row g[row] does not exist yet - the wavefront forms it from the exit record with the arithmetic of
+// norm_perm_pick_bwd_kernel (rowops.hip: same per-lane partial of the dot product, same wave_sum), stores it for the launches
+// behind this one (hg_bwd_src, the column sums, hg_pre) and goes on with it in registers.
+template <typename T, int DIF, int WV, bool XB = false>   // DIF: edges (x 4 row loads) in flight together; WV: waves per SIMD
 __global__ __launch_bounds__(256, WV) void hg_bwd_dst_node_kernel(DstArgs a) {
     __shared__ float da[WPB][MAXDEG][MAXH];
     __shared__ int su[WPB][MAXDEG];
@@ -870,6 +975,8 @@ __global__ __launch_bounds__(256, WV) void hg_bwd_dst_node_kernel(DstArgs a) {
     if (v >= dyn_count(a.dyn_t[t], a.ncap_t[t])) {
         for (int q = 0; q < ni; ++q)
             if (lane < H) a.der[a.inst_t[t][q]][(size_t)v * H + lane] = 0.f;
+        if (XB && lane * 4 < D)                                      // capacity padding of the stacked gradient: zeros
+            *reinterpret_cast<float4*>(a.gout + (size_t)row * a.ld_g + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
     const int q = lane >> 3, j = lane & 7;
@@ -883,8 +990,34 @@ __global__ __launch_bounds__(256, WV) void hg_bwd_dst_node_kernel(DstArgs a) {
     float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
     uchar4 a4 = make_uchar4(0, 0, 0, 0);
     if (c < D) {
-        g4 = *reinterpret_cast<const float4*>(a.g + (size_t)row * a.ld_g + c);
+        if (!XB) g4 = *reinterpret_cast<const float4*>(a.g + (size_t)row * a.ld_g + c);
         a4 = *reinterpret_cast<const uchar4*>(a.arg + (size_t)row * D + c);
+    }
+    if (XB) {
+        const int r = a.cat_inv[row], b = a.sess[row];               // the row's place in per-session order, its session
+        float4 yy = make_float4(0.f, 0.f, 0.f, 0.f), gg = yy;
+        float iv = 0.f, dot = 0.f;
+        if (r >= 0 && c < D) {
+            int hit = -1;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < a.npick && a.gpick[k] != nullptr && a.pick[k][b] == row) hit = k;
+            iv = a.invr[r];
+            yy = *reinterpret_cast<const float4*>(a.allf + (size_t)r * D + c);
+            gg = *reinterpret_cast<const float4*>(a.gallf + (size_t)r * a.ld_ga + c);
+            if (hit >= 0) {
+                const float4 p = *reinterpret_cast<const float4*>(a.gpick[hit] + (size_t)b * a.ld_gp[hit] + c);
+                gg.x += p.x; gg.y += p.y; gg.z += p.z; gg.w += p.w;
+            }
+            // (the expressions of norm_perm_pick_bwd_kernel, token for token, here and for g4 below: contracted as there, which the
+            // tests check byte for byte - the kernel this must equal carries no pragma, so none here)
+            dot += yy.x * gg.x + yy.y * gg.y + yy.z * gg.z + yy.w * gg.w;
+        }
+        dot = wave_sum(dot);
+        if (c < D) {
+            g4 = make_float4(iv * (gg.x - yy.x * dot), iv * (gg.y - yy.y * dot), iv * (gg.z - yy.z * dot), iv * (gg.w - yy.w * dot));
+            *reinterpret_cast<float4*>(a.gout + (size_t)row * a.ld_g + c) = g4;
+        }
     }
     const bool valid = i >= 0 && j < deg;
     HGT_W(1);
@@ -974,8 +1107,14 @@ __global__ __launch_bounds__(256, WV) void hg_bwd_dst_node_kernel(DstArgs a) {
     {
         float gq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         uint2 aq = make_uint2(0xffffffffu, 0xffffffffu);
+        if (XB) {                                                    // columns c8 .. c8 + 7 sit in lanes 2 m, 2 m + 1 (m = lane & 31)
+            const int l0 = 2 * (lane & 31);
+            const float t0 = __shfl(g4.x, l0, 64), t1 = __shfl(g4.y, l0, 64), t2 = __shfl(g4.z, l0, 64), t3 = __shfl(g4.w, l0, 64);
+            const float t4 = __shfl(g4.x, l0 + 1, 64), t5 = __shfl(g4.y, l0 + 1, 64), t6 = __shfl(g4.z, l0 + 1, 64), t7 = __shfl(g4.w, l0 + 1, 64);
+            if (cok8) { gq[0] = t0; gq[1] = t1; gq[2] = t2; gq[3] = t3; gq[4] = t4; gq[5] = t5; gq[6] = t6; gq[7] = t7; }
+        }
         if (cok8) {
-            ld8f(a.g + (size_t)row * a.ld_g + c8, gq);
+            if (!XB) ld8f(a.g + (size_t)row * a.ld_g + c8, gq);
             aq = *reinterpret_cast<const uint2*>(a.arg + (size_t)row * D + c8);
         }
 #pragma unroll
@@ -1513,8 +1652,8 @@ extern "C" int srec_hg_ws_floats(const void* desc_, long* n_floats) {
     return 0;
 }
 
-extern "C" int srec_hg_fwd(const void* desc_, const float* x, int ld_x, float* out, int ld_out, unsigned char* arg,
-                           void* stream) {
+static int hg_fwd_run(const void* desc_, const float* x, int ld_x, float* out, int ld_out, unsigned char* arg, const HgExit* xr,
+                      void* stream) {
     const srec_hg_desc* d = (const srec_hg_desc*)desc_;
     if (bad_desc(d) || (ld_x & 3)) return SREC_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1577,7 +1716,22 @@ extern "C" int srec_hg_fwd(const void* desc_, const float* x, int ld_x, float* o
         for (int t = 0; node && t < d->n_types; ++t) node = al16(g.smean[t]) && (g.ninst[t] == 0 || al16(g.bsum[t]));
         for (int i = 0; node && i < d->n_inst; ++i)
             node = al16(g.Ps[i]) && al16(g.eLs[i]) && al16(g.eRd[i]) && al16(g.A[i]) && al16(g.Mk[i]);
-        if (node) {
+        if (xr != nullptr) {                          // the output leaves through the exit record (node kernel only)
+            node = H == MAXH && (D & 7) == 0 && D <= 256 && (ld_x & 3) == 0 && al16(arg) && al16(x) && al16(g.xres);
+            for (int t = 0; node && t < d->n_types; ++t) node = al16(g.smean[t]) && (g.ninst[t] == 0 || al16(g.bsum[t]));
+            for (int i = 0; node && i < d->n_inst; ++i)
+                node = al16(g.Ps[i]) && al16(g.eLs[i]) && al16(g.eRd[i]) && al16(g.A[i]) && al16(g.Mk[i]);
+            if (!node || xr->cat_inv == nullptr || xr->allf == nullptr || xr->invr == nullptr || xr->npick < 0 || xr->npick > 4)
+                return SREC_BAD_ARG;
+            g.out = nullptr; g.cat_inv = xr->cat_inv; g.allf = xr->allf; g.invr = xr->invr; g.npick = xr->npick;
+            g.eps_mode = xr->eps_mode; g.eps = xr->eps;
+            for (int k = 0; k < xr->npick; ++k) {
+                g.pick[k] = xr->pick[k]; g.pout[k] = xr->pout[k]; g.ld_p[k] = xr->ld_p[k];
+                if (g.pick[k] == nullptr || g.pout[k] == nullptr || (g.ld_p[k] & 3) || g.ld_p[k] < D) return SREC_BAD_ARG;
+            }
+            if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL((hg_agg_node_kernel<unsigned short, 1, 5, true>), dim3(cdiv(rows, WPB)), dim3(64 * WPB), 0, st, g);
+            else hipLaunchKernelGGL((hg_agg_node_kernel<float, 2, 3, true>), dim3(cdiv(rows, WPB)), dim3(64 * WPB), 0, st, g);
+        } else if (node) {
             // (same box, rocprof: 1 edge in flight at 5 waves per SIMD 31.6 us; 2 edges at 4: 32.5; anything that spills: 38 - 97)
             if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL((hg_agg_node_kernel<unsigned short, 1, 5>), dim3(cdiv(rows, WPB)), dim3(64 * WPB), 0, st, g);
             else hipLaunchKernelGGL((hg_agg_node_kernel<float, 2, 3>), dim3(cdiv(rows, WPB)), dim3(64 * WPB), 0, st, g);
@@ -1586,6 +1740,24 @@ extern "C" int srec_hg_fwd(const void* desc_, const float* x, int ld_x, float* o
     }
     SREC_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int srec_hg_fwd(const void* desc_, const float* x, int ld_x, float* out, int ld_out, unsigned char* arg,
+                           void* stream) {
+    return hg_fwd_run(desc_, x, ld_x, out, ld_out, arg, nullptr, stream);
+}
+
+// pick / pout / ld_p: HOST arrays of npick <= 4 entries
+extern "C" int srec_hg_fwd_exit(const void* desc_, const float* x, int ld_x, unsigned char* arg, const int* cat_inv, float* allf,
+                                float* invr, int npick, const void* pick, const void* pout, const int* ld_p, int eps_mode, float eps,
+                                void* stream) {
+    if (npick < 0 || npick > 4 || (npick > 0 && (pick == nullptr || pout == nullptr || ld_p == nullptr))) return SREC_BAD_ARG;
+    HgExit r{};
+    r.cat_inv = cat_inv; r.allf = allf; r.invr = invr; r.npick = npick; r.eps_mode = eps_mode; r.eps = eps;
+    for (int k = 0; k < npick; ++k) {
+        r.pick[k] = ((const int* const*)pick)[k]; r.pout[k] = ((float* const*)pout)[k]; r.ld_p[k] = ld_p[k];
+    }
+    return hg_fwd_run(desc_, x, ld_x, nullptr, 0, arg, &r, stream);
 }
 
 static int fill_pre(const srec_hg_desc* d, const float* g, int ld_g, float* dx, int ld_dx, PreArgs& a) {
@@ -1608,21 +1780,49 @@ static int fill_pre(const srec_hg_desc* d, const float* g, int ld_g, float* dx, 
 // the layer's d x in one pass, AFTER the backward-data GEMMs of a feature-dropout call (SREC_HG_LATE_DX in desc.p16 made srec_hg_bwd leave
 // d x alone): dx [NT, D] = residual + session-mean terms of g (as srec_hg_bwd would have written) + the two convs' masked data
 // gradients t [2, S, NT, D] (as srec_hg_drop_merge would have added); masks from desc.rm_p / rm_seed / rm_counter / rm_salt.
-extern "C" int srec_hg_pre_merge(const void* desc_, const float* g, int ld_g, const float* t, int S, float* dx, int ld_dx,
-                                 void* stream) {
+static int hg_pre_merge_run(const void* desc_, const float* g, int ld_g, const float* t, int S, float* dx, int ld_dx, const HgEntry* er,
+                            void* stream) {
     const srec_hg_desc* d = (const srec_hg_desc*)desc_;
     if (bad_desc(d) || (ld_g & 3) || (ld_dx & 3) || t == nullptr || S < 1 || d->rm_cnt == nullptr) return SREC_BAD_ARG;
     PreArgs a{};
     if (int rc = fill_pre(d, g, ld_g, dx, ld_dx, a)) return rc;
     const int rows = a.row0[d->n_types];
     if ((long)2 * rows * d->D > 0xffffffffL) return SREC_BAD_ARG;
+    if (er != nullptr) {                         // d x leaves through the entry normalisation (one wavefront = one row)
+        if (er->Y == nullptr || er->inv == nullptr || d->D > 256) return SREC_BAD_ARG;
+        a.nY = er->Y; a.ninv = er->inv;
+        for (int tt = 0; tt < d->n_types; ++tt) {
+            a.ndX[tt] = er->dX[tt]; a.nld[tt] = er->ld[tt];
+            if (a.ndX[tt] == nullptr || (a.nld[tt] & 3) || a.nld[tt] < d->D) return SREC_BAD_ARG;
+        }
+        if (rows > 0) hipLaunchKernelGGL((hg_pre_kernel<true, true>), dim3(cdiv(rows, WPB)), dim3(256), 0, (hipStream_t)stream, a, t, S);
+        SREC_LAUNCH_CHECK();
+        return 0;
+    }
+    if (dx == nullptr) return SREC_BAD_ARG;
     if (rows > 0) hipLaunchKernelGGL(hg_pre_kernel<true>, dim3(cdiv(rows, WPB)), dim3(256), 0, (hipStream_t)stream, a, t, S);
     SREC_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const float* g, int ld_g, const unsigned char* arg,
-                           float* dx, int ld_dx, float* ws, void* stream) {
+extern "C" int srec_hg_pre_merge(const void* desc_, const float* g, int ld_g, const float* t, int S, float* dx, int ld_dx,
+                                 void* stream) {
+    return hg_pre_merge_run(desc_, g, ld_g, t, S, dx, ld_dx, nullptr, stream);
+}
+
+// dX / ld: HOST arrays of desc.n_types entries
+extern "C" int srec_hg_pre_merge_norm(const void* desc_, const float* g, int ld_g, const float* t, int S, const float* Y,
+                                      const float* inv, const void* dX, const int* ld, void* stream) {
+    const srec_hg_desc* d = (const srec_hg_desc*)desc_;
+    if (bad_desc(d) || dX == nullptr || ld == nullptr) return SREC_BAD_ARG;
+    HgEntry e{};
+    e.Y = Y; e.inv = inv;
+    for (int tt = 0; tt < d->n_types; ++tt) { e.dX[tt] = ((float* const*)dX)[tt]; e.ld[tt] = ld[tt]; }
+    return hg_pre_merge_run(desc_, g, ld_g, t, S, nullptr, 0, &e, stream);
+}
+
+static int hg_bwd_run(const void* desc_, const float* x, int ld_x, const float* g, int ld_g, const unsigned char* arg, float* dx,
+                      int ld_dx, float* ws, const HgExit* xr, void* stream) {
     const srec_hg_desc* d = (const srec_hg_desc*)desc_;
     if (bad_desc(d) || (ld_g & 3) || (ld_dx & 3) || (ld_x & 3) || ws == nullptr) return SREC_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1632,11 +1832,20 @@ extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const fl
     for (int i = 0; i < d->n_inst; ++i) ninst_t[d->blk_type[d->inst_dblk[i]]]++;
     int rows = 0;
     for (int t = 0; t < d->n_types; ++t) rows += d->ncap[t];
-    if (!(d->p16 & SREC_HG_LATE_DX)) {                       // (the caller finishes d x with srec_hg_pre_merge after its GEMMs)
+    const bool xb = xr != nullptr;          // g is written by the score-gradient launch (exit record)
+    if (xb && (d->n_inst <= 0 || D > 256 || xr->cat_inv == nullptr || xr->allf == nullptr || xr->invr == nullptr ||
+               xr->gallf == nullptr || (xr->ld_ga & 3) || xr->npick < 0 || xr->npick > 4 || d->sess == nullptr))
+        return SREC_BAD_ARG;
+    bool pre_done = (d->p16 & SREC_HG_LATE_DX) != 0;           // (the caller finishes d x with srec_hg_pre_merge after its GEMMs)
+    auto pre = [&]() -> int {
         PreArgs a{};
         if (int rc = fill_pre(d, g, ld_g, dx, ld_dx, a)) return rc;
         if (rows > 0) hipLaunchKernelGGL(hg_pre_kernel<false>, dim3(cdiv(rows, WPB)), dim3(256), 0, st, a, (const float*)nullptr, 0);
-    }
+        pre_done = true;
+        return 0;
+    };
+    if (!pre_done && !xb)
+        if (int rc = pre()) return rc;
     if (d->n_inst > 0) {
         DstArgs a{};
         a.ni = d->n_inst; a.H = H; a.D = D; a.slope = d->slope; a.g = g; a.ld_g = ld_g; a.arg = arg;
@@ -1668,7 +1877,19 @@ extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const fl
             a.inst_t[t][a.ninst_t[t]++] = i;
             node = node && al16(a.A[i]) && al16(a.Mk[i]) && al16(a.eLs[i]) && al16(a.eRd[i]) && al16(a.DP[i]) && al16(a.der[i]);
         }
-        if (node && trows > 0) {
+        if (xb) {
+            if (!node || trows <= 0) return SREC_BAD_ARG;              // (the exit record exists for the node kernel only)
+            a.gout = const_cast<float*>(g); a.cat_inv = xr->cat_inv; a.sess = d->sess;
+            a.allf = xr->allf; a.invr = xr->invr; a.gallf = xr->gallf; a.ld_ga = xr->ld_ga; a.npick = xr->npick;
+            for (int k = 0; k < xr->npick; ++k) {
+                a.pick[k] = xr->pick[k]; a.gpick[k] = xr->gpick[k]; a.ld_gp[k] = xr->ld_gp[k];
+                if (a.pick[k] == nullptr || (a.ld_gp[k] & 3)) return SREC_BAD_ARG;
+            }
+            if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL((hg_bwd_dst_node_kernel<unsigned short, 2, 4, true>), dim3(cdiv(trows, WPB)), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((hg_bwd_dst_node_kernel<float, 1, 3, true>), dim3(cdiv(trows, WPB)), dim3(256), 0, st, a);
+            if (!pre_done)                                             // the d x pre-fill reads the g written just now
+                if (int rc = pre()) return rc;
+        } else if (node && trows > 0) {
             // (same box, rocprof: 2 edges in flight at 4 waves per SIMD 28.2 us; 1 edge 30.2; 5 waves per SIMD spill: 32.7 / 36.1)
             if (d->p16 & SREC_HG_P16_BF16) hipLaunchKernelGGL((hg_bwd_dst_node_kernel<unsigned short, 2, 4>), dim3(cdiv(trows, WPB)), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((hg_bwd_dst_node_kernel<float, 1, 3>), dim3(cdiv(trows, WPB)), dim3(256), 0, st, a);
@@ -1761,6 +1982,26 @@ extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const fl
     }
     SREC_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int srec_hg_bwd(const void* desc_, const float* x, int ld_x, const float* g, int ld_g, const unsigned char* arg,
+                           float* dx, int ld_dx, float* ws, void* stream) {
+    return hg_bwd_run(desc_, x, ld_x, g, ld_g, arg, dx, ld_dx, ws, nullptr, stream);
+}
+
+// pick / g_pick / ld_gp: HOST arrays of npick <= 4 entries (g_pick entries nullable)
+extern "C" int srec_hg_bwd_exit(const void* desc_, const float* x, int ld_x, float* g, int ld_g, const unsigned char* arg, float* dx,
+                                int ld_dx, float* ws, const int* cat_inv, const float* allf, const float* invr, const float* g_allf,
+                                int ld_ga, int npick, const void* pick, const void* g_pick, const int* ld_gp, void* stream) {
+    if (g == nullptr || npick < 0 || npick > 4 || (npick > 0 && (pick == nullptr || g_pick == nullptr || ld_gp == nullptr)))
+        return SREC_BAD_ARG;
+    HgExit r{};
+    r.cat_inv = cat_inv; r.allf = const_cast<float*>(allf); r.invr = const_cast<float*>(invr); r.gallf = g_allf; r.ld_ga = ld_ga;
+    r.npick = npick;
+    for (int k = 0; k < npick; ++k) {
+        r.pick[k] = ((const int* const*)pick)[k]; r.gpick[k] = ((const float* const*)g_pick)[k]; r.ld_gp[k] = ld_gp[k];
+    }
+    return hg_bwd_run(desc_, x, ld_x, g, ld_g, arg, dx, ld_dx, ws, &r, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ live-source rows
@@ -1859,10 +2100,20 @@ namespace {
 // mk [na] (all relation instances back to back).  Masks come from the counter-based hash of common.h.
 // In front of them live.nb workgroups (0: none) build the live-source row lists of the layer call (hg_live_rows_block): they
 // read the batch's topology only and start first, so the longest workgroups of the launch are not its tail.
+// NORM: x does not exist yet - the rows are the L2-normalised rows of up to 4 raw tensors (one per node type, HgNorm), formed
+// here with normalize_group_fwd's arithmetic (rowops.hip), one wavefront per row (D <= 256): the stacked x and 1 / norm are
+// written for the layer's other readers and the backward, the masks apply to the row in registers (same hash indices).
+struct HgNorm {
+    const float* X[4]; const int* dyn[4];
+    int ld[4], n[4], row0[4], np;
+    float* Y; float* inv;
+    int eps_mode; float eps;
+};
+template <bool NORM>
 __global__ __launch_bounds__(256) void hg_drop_prep_kernel(const float* __restrict__ x, const float* __restrict__ cnt, long n, int D, long rows,
                                     float p, srec_rng rng, float* __restrict__ ms, float* __restrict__ xc,
                                     float* __restrict__ rm, float* __restrict__ xres, int nb1, float pa, long na,
-                                    float* __restrict__ mk, unsigned short* __restrict__ xc16, LiveArgs live) {
+                                    float* __restrict__ mk, unsigned short* __restrict__ xc16, LiveArgs live, HgNorm g) {
     if ((int)blockIdx.x < live.nb) { hg_live_rows_block(live, (int)blockIdx.x); return; }
     const int bx = (int)blockIdx.x - live.nb;
     const unsigned key = srec_rng_key(rng);
@@ -1873,12 +2124,42 @@ __global__ __launch_bounds__(256) void hg_drop_prep_kernel(const float* __restri
             if (j + e < na) mk[j + e] = srec_keep(key ^ 0xA5A5A5A5u, (unsigned)(j + e), pa, sa);
         return;
     }
-    const long i = ((long)bx * blockDim.x + threadIdx.x) * 4;
-    if (i >= n) return;
+    long i;
+    float4 xv;
+    if (NORM) {
+        const int r = bx * WPB + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane * 4;
+        if (r >= rows) return;
+        int q = 0;
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            if (k < g.np && r >= g.row0[k]) q = k;
+        const int li = r - g.row0[q];
+        const bool lv = li < dyn_count(g.dyn[q], g.n[q]), cok = c < D;
+        xv = make_float4(0.f, 0.f, 0.f, 0.f);
+        float iv = 0.f;
+        if (lv) {
+            float s = 0.f;
+            if (cok) {
+                // (row_sumsq's expression on a 16-byte load: the compiler squares with packed multiplies and adds in order, no fused
+                // multiply-add, here as there - byte-equality with normalize_group_fwd rests on that and is what the tests compare)
+                xv = *reinterpret_cast<const float4*>(g.X[q] + (size_t)li * g.ld[q] + c);
+                s += xv.x * xv.x + xv.y * xv.y + xv.z * xv.z + xv.w * xv.w;
+            }
+            iv = inv_norm(wave_sum(s), g.eps_mode, g.eps);
+            xv.x *= iv; xv.y *= iv; xv.z *= iv; xv.w *= iv;
+        }
+        if (lane == 0) g.inv[r] = iv;
+        if (!cok) return;
+        i = (long)r * D + c;
+        *reinterpret_cast<float4*>(g.Y + i) = xv;
+    } else {
+        i = ((long)bx * blockDim.x + threadIdx.x) * 4;
+        if (i >= n) return;
+        xv = *reinterpret_cast<const float4*>(x + i);
+    }
     const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;
     const long row = i / D;
     const float c0 = cnt[row], c1 = cnt[rows + row];
-    const float4 xv = *reinterpret_cast<const float4*>(x + i);
     float4 m0, m1;
     const unsigned i0 = (unsigned)i, i1 = (unsigned)(n + i);
     m0.x = srec_keep(key, i0, p, sc); m0.y = srec_keep(key, i0 + 1, p, sc); m0.z = srec_keep(key, i0 + 2, p, sc); m0.w = srec_keep(key, i0 + 3, p, sc);
@@ -1936,7 +2217,7 @@ __global__ void hg_drop_merge_kernel(const float* __restrict__ t, int S, const f
 // multipliers mk [na] - all masks from the counter-based hash keyed by (seed, *counter, salt).
 static int hg_drop_prep_run(const float* x, const float* cnt, int rows, int D, float p, int seed, const int* counter,
                             int salt, float* ms, float* xc, float* rm, float* xres, float pa, long na, float* mk,
-                            unsigned short* xc16, void* stream, const LiveArgs& live = LiveArgs{}) {
+                            unsigned short* xc16, void* stream, const LiveArgs& live = LiveArgs{}, const HgNorm* norm = nullptr) {
     if (rows <= 0 && live.nb > 0) {
         hipLaunchKernelGGL(hg_live_rows_kernel, dim3(live.nb), dim3(256), 0, (hipStream_t)stream, live);
         SREC_LAUNCH_CHECK();
@@ -1945,11 +2226,16 @@ static int hg_drop_prep_run(const float* x, const float* cnt, int rows, int D, f
     if (D <= 0 || (D & 3) || p < 0.f || p >= 1.f || pa < 0.f || pa >= 1.f) return SREC_BAD_ARG;
     const long n = (long)rows * D;
     if (2 * n > 0xffffffffL || na > 0xffffffffL) return SREC_BAD_ARG;
-    const int nb1 = (int)((n / 4 + 255) / 256);
+    const int nb1 = norm != nullptr ? cdiv(rows, WPB) : (int)((n / 4 + 255) / 256);
     const int nb2 = (pa > 0.f && na > 0 && mk != nullptr) ? (int)(((na + 3) / 4 + 255) / 256) : 0;
-    hipLaunchKernelGGL(hg_drop_prep_kernel, dim3((unsigned)(live.nb + nb1 + nb2)), dim3(256), 0, (hipStream_t)stream, x, cnt, n, D,
-                       (long)rows, p, srec_rng{(unsigned)seed, counter, (unsigned)salt, p}, ms, xc, rm, xres, nb1, pa, na, mk, xc16,
-                       live);
+    if (norm != nullptr)
+        hipLaunchKernelGGL(hg_drop_prep_kernel<true>, dim3((unsigned)(live.nb + nb1 + nb2)), dim3(256), 0, (hipStream_t)stream, x, cnt, n,
+                           D, (long)rows, p, srec_rng{(unsigned)seed, counter, (unsigned)salt, p}, ms, xc, rm, xres, nb1, pa, na, mk,
+                           xc16, live, *norm);
+    else
+        hipLaunchKernelGGL(hg_drop_prep_kernel<false>, dim3((unsigned)(live.nb + nb1 + nb2)), dim3(256), 0, (hipStream_t)stream, x, cnt, n,
+                           D, (long)rows, p, srec_rng{(unsigned)seed, counter, (unsigned)salt, p}, ms, xc, rm, xres, nb1, pa, na, mk,
+                           xc16, live, HgNorm{});
     SREC_LAUNCH_CHECK();
     return 0;
 }
@@ -1974,6 +2260,33 @@ extern "C" int srec_hg_drop_prep16_live(const float* x, const float* cnt, int ro
     LiveArgs live{};
     if (int rc = hg_live_fill(live, (const srec_hg_desc*)desc, lists, counts)) return rc;
     return hg_drop_prep_run(x, cnt, rows, D, p, seed, counter, salt, ms, xc, rm, xres, pa, na, mk, (unsigned short*)xc16, stream, live);
+}
+
+// srec_hg_drop_prep (xc16 / desc nullable: then as srec_hg_drop_prep16 / _live) whose input rows x [rows, D] are formed in the same
+// pass: Y = the row-normalised X_p stacked, inv [rows] - srec_normalize_group_fwd's arguments and results (np <= 4 HOST arrays;
+// sum n_p == rows, D <= 256).  Y is what the layer reads as x.
+extern "C" int srec_hg_drop_prep_norm(int np, const void* X, const int* ld, const int* nrow, const void* dyn, float* Y, float* inv,
+                                      int eps_mode, float eps, const float* cnt, int rows, int D, float p, int seed,
+                                      const int* counter, int salt, float* ms, float* xc, float* rm, float* xres, float pa, long na,
+                                      float* mk, void* xc16, const void* desc, const void* lists, int* counts, void* stream) {
+    if (np <= 0 || np > 4 || X == nullptr || ld == nullptr || nrow == nullptr || Y == nullptr || inv == nullptr || D > 256)
+        return SREC_BAD_ARG;
+    HgNorm g{};
+    g.np = np; g.Y = Y; g.inv = inv; g.eps_mode = eps_mode; g.eps = eps;
+    int r = 0;
+    for (int q = 0; q < np; ++q) {
+        g.X[q] = ((const float* const*)X)[q];
+        g.dyn[q] = dyn != nullptr ? ((const int* const*)dyn)[q] : nullptr;
+        g.ld[q] = ld[q]; g.n[q] = nrow[q]; g.row0[q] = r;
+        if (g.X[q] == nullptr || nrow[q] <= 0 || (ld[q] & 3) || ld[q] < D) return SREC_BAD_ARG;
+        r += nrow[q];
+    }
+    if (r != rows) return SREC_BAD_ARG;
+    LiveArgs live{};
+    if (desc != nullptr)
+        if (int rc = hg_live_fill(live, (const srec_hg_desc*)desc, lists, counts)) return rc;
+    return hg_drop_prep_run(nullptr, cnt, rows, D, p, seed, counter, salt, ms, xc, rm, xres, pa, na, mk, (unsigned short*)xc16, stream,
+                            live, &g);
 }
 
 // dx [n] += (sum_s t[0][s]) * ms[0] + (sum_s t[1][s]) * ms[1], t [2, S, n], ms [2, n] or NULL (then the masks of

@@ -235,11 +235,7 @@ __global__ void renorm_rows_bf16_kernel(float* __restrict__ W, int ld, int n, in
     }
 }
 
-// eps_mode 0: 1/max(||x||, eps) (F.normalize)   1: 1/(||x|| + eps) (niser.py)
-__device__ __forceinline__ float inv_norm(float sumsq, int eps_mode, float eps) {
-    const float n = sqrtf(sumsq);
-    return eps_mode == 0 ? 1.f / fmaxf(n, eps) : 1.f / (n + eps);
-}
+// (inv_norm: common.h)
 
 __global__ void row_invnorm_kernel(const float* __restrict__ W, int ld, int n, int d, int eps_mode, float eps,
                                    float scale, float* __restrict__ out) {

@@ -12,6 +12,29 @@ from .ops import GemmProb, HgDesc, _ld, _rows
 # dropout state of one call.  xc [2, NT, D]: dropped inputs of conv1 / conv2;  xres [NT, D]: residual rows summed over the instances;
 # mk: attention masks per instance or None;  ms: feature masks, kept for the tests' tap only;  rng = (p, seed, counter, salt)
 DropState = namedtuple('DropState', 'xc xres mk ms rng cnt')
+# entry record of a layer call: x = the L2-normalised rows of one raw tensor per node type (what ops.normalize_stack would hand over).
+# raws [n_types] tensors [ncap_t, D];  dyns: their live counts;  eps_mode of ops.normalize
+NormEntry = namedtuple('NormEntry', 'raws dyns eps_mode')
+# exit record: the layer's output goes on as ops.norm_permute_pick(out, ...) would hand it over.  cat_perm [n_cat] concatenated row ->
+# stacked row, cat_inv [NT] its inverse (-1: capacity padding), cat_seg [B + 1];  picks: [B] stacked rows per pick list;  types
+# [(row0, ncap, dyn)];  dyn_t / dyn_b: live concatenated rows / sessions
+NormExit = namedtuple('NormExit', 'cat_perm cat_inv cat_seg picks types dyn_t dyn_b eps_mode')
+FOLD_A, FOLD_B, FOLD_C, FOLD_D = 1, 2, 4, 8          # entry forward, exit forward, exit backward, entry backward (ops.NORM_FOLD)
+FOLDS_BUILT = FOLD_A | FOLD_B | FOLD_C | FOLD_D      # (a fold without a kernel would be masked out here)
+
+
+def norm_fold_bits(mask, H, D, inst_per_type, has_entry, has_exit, p_feat, p_attn, tap_on):
+    """the normalisation folds a layer call takes (bits FOLD_*), like head_path / readout_head_fused_ok: one place decides.
+    The hosts are the node kernels (H == 8, <= 8 relation instances into every type, 8-column lanes) with one wavefront per row
+    (D <= 256).  Entry folds ride in the dropout launches: A needs a dropout launch (p_feat or p_attn > 0), D the one-pass d x of a
+    feature-dropout call with recomputed masks (the tap off)."""
+    node = H == 8 and D % 8 == 0 and 0 < D <= 256 and len(inst_per_type) > 0 and 0 < max(inst_per_type) <= 8
+    bits = 0
+    if node and has_entry and (p_feat > 0 or p_attn > 0):
+        bits |= FOLD_A | (0 if tap_on else FOLD_D)
+    if node and has_exit:
+        bits |= FOLD_B | FOLD_C
+    return bits & mask & FOLDS_BUILT
 
 
 class HgPlan:
@@ -150,10 +173,11 @@ def gemm_strategy(mode, D, ldx, n_mods, w_contiguous):
     return 'g16' if D % 64 == 0 and w_contiguous else 'grouped'
 
 
-def _drop_prep(x, plan, drop, strategy, live=None):
+def _drop_prep(x, plan, drop, strategy, live=None, norm=None):
     """-> (DropState, x16 or None): both convs' feature masks and every instance's attention mask in ONE launch (counter-based
     hash: no generator state, replay-safe); the 'g16' strategy reads bf16(xc), written by the same pass.  live = (desc, lists,
-    counts): the live-source row lists of the call ride in the same launch ('g16' only)"""
+    counts): the live-source row lists of the call ride in the same launch ('g16' only).  norm = (NormEntry, inv): x is still
+    unwritten - the launch forms it (and inv) from the entry record's raw rows first (fold A)"""
     (pf, pa), (NT, D), dev, tap = drop, x.shape, x.device, ops.DROP_TAP
     cnt = _inst_counts(plan, NT, dev)                     # (depends on the plan only: cached)
     ms = torch.empty(2, NT, D, device=dev, dtype=torch.float32) if tap is not None else None
@@ -166,7 +190,16 @@ def _drop_prep(x, plan, drop, strategy, live=None):
     salt = 101 + 2 * plan.layer_id                        # (rm = cnt0 m0 + cnt1 m1 is never stored: NULL, the backward recomputes it)
     args = (ptr(x), ptr(cnt), NT, D, float(pf), seed, rc, salt, ptr(ms), ptr(xcs), None, ptr(xres), float(pa), na, ptr(allm))
     x16 = torch.empty(2, NT, D, device=dev, dtype=torch.bfloat16) if strategy == 'g16' else None
-    if x16 is not None and live is not None:
+    if norm is not None:
+        entry, inv = norm
+        a_x, a_l, a_n, a_d = _group_arrays(entry.raws, entry.dyns)
+        use_live = x16 is not None and live is not None
+        la = ptr_array(live[1]) if use_live else None
+        lib.srec_hg_drop_prep_norm(len(entry.raws), _ct.addressof(a_x), _ct.addressof(a_l), _ct.addressof(a_n), _ct.addressof(a_d),
+                                   ptr(x), ptr(inv), entry.eps_mode, 1e-12, *args[1:], ptr(x16),
+                                   _ct.addressof(live[0]) if use_live else None, _ct.addressof(la) if use_live else None,
+                                   ptr(live[2]) if use_live else None, stream())
+    elif x16 is not None and live is not None:
         la = ptr_array(live[1])
         lib.srec_hg_drop_prep16_live(*args, ptr(x16), _ct.addressof(live[0]), _ct.addressof(la), ptr(live[2]), stream())
     elif x16 is not None:
@@ -176,6 +209,14 @@ def _drop_prep(x, plan, drop, strategy, live=None):
     if tap is not None:
         tap.append(dict(ms=ms.clone(), mk=[m.clone() for m in mk] if mk is not None else None))
     return DropState([xcs[0], xcs[1]], xres, mk, ms, (float(pf), seed, rc, salt), cnt), x16
+
+
+def _group_arrays(xs, dyns, lds=None):
+    """HOST arrays (pointers, row strides, rows, live counts) of a row-block group: srec_normalize_group_* and the folds' records"""
+    P = len(xs)
+    arr = _ct.c_void_p * P
+    return (arr(*[x.data_ptr() for x in xs]), (_ct.c_int * P)(*(lds or [_ld(x) for x in xs])), (_ct.c_int * P)(*[x.shape[0] for x in xs]),
+            arr(*[ptr(t) for t in dyns]))
 
 
 def _project(xin, x16, plan, params, strategy, P, live=None):
@@ -210,8 +251,10 @@ def _project(xin, x16, plan, params, strategy, P, live=None):
     return None
 
 
-def _backward_graph(ctx, x, g, small, arg, P, params, late_dx):
-    """srec_hg_bwd: the graph kernels' half of the backward -> (desc, dP, [attn_l, attn_r, bias gradients per module], dx)"""
+def _backward_graph(ctx, x, g, small, arg, P, params, late_dx, xrec=None, need_dx=True):
+    """srec_hg_bwd: the graph kernels' half of the backward -> (desc, dP, [attn_l, attn_r, bias gradients per module], dx).
+    xrec = (cat_inv, allf, invr, g_allf, picks, g_picks): g is still unwritten - the score-gradient launch forms it (fold C);
+    need_dx False (a late_dx call whose d x leaves through the entry normalisation, fold D): no stacked dx, None"""
     plan, nm = ctx.plan, len(ctx.plan.modules)
     # rows of a module's projection that no relation instance touches (a type without live 'inter' edges) get no
     # gradient from the kernels: those buffers start from zero
@@ -219,7 +262,7 @@ def _backward_graph(ctx, x, g, small, arg, P, params, late_dx):
     dP = [torch.empty_like(p) if cov[m] == p.shape[0] else torch.zeros_like(p) for m, p in enumerate(P)]
     # (attn_l, attn_r, bias gradients: [HD] each - the parameters' bucket slots when the table is row-sharded, ops.grad_buf)
     grads = [[ops.grad_buf(params[4 * m + 1 + j]).view(-1) for j in range(3)] for m in range(nm)]
-    dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    dx = torch.empty(x.shape, device=x.device, dtype=torch.float32) if need_dx else None
     flat = [p.reshape(-1) if i % 4 else p for i, p in enumerate(params)]
     desc = plan.fill(HgDesc(), small, ctx.lay, P, dP, flat, grads, ctx.drop)
     # (both gemm16 consumers of dP stop at the live rows)
@@ -230,7 +273,15 @@ def _backward_graph(ctx, x, g, small, arg, P, params, late_dx):
     ws = _HG_WS.get(key)
     if ws is None:
         ws = _HG_WS[key] = torch.empty(max(n.value, 1), device=x.device, dtype=torch.float32)
-    lib.srec_hg_bwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(g), _ld(g), ptr(arg), ptr(dx), x.shape[1], ptr(ws), stream())
+    if xrec is not None:
+        cat_inv, allf, invr, g_allf, picks, gps = xrec
+        a_pick, a_g = ptr_array(picks), ptr_array(gps)
+        a_ld = (_ct.c_int * len(picks))(*[(_ld(gp) if gp is not None else x.shape[1]) for gp in gps])
+        lib.srec_hg_bwd_exit(_ct.addressof(desc), ptr(x), _ld(x), ptr(g), _ld(g), ptr(arg), ptr(dx), x.shape[1], ptr(ws), ptr(cat_inv),
+                             ptr(allf), ptr(invr), ptr(g_allf), _ld(g_allf), len(picks), _ct.addressof(a_pick), _ct.addressof(a_g),
+                             _ct.addressof(a_ld), stream())
+    else:
+        lib.srec_hg_bwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(g), _ld(g), ptr(arg), ptr(dx), x.shape[1], ptr(ws), stream())
     return desc, dP, grads, dx
 
 
@@ -325,7 +376,25 @@ class HGATLayer(torch.autograd.Function):
     soft-max (gatconv.py:300)."""
 
     @staticmethod
-    def forward(ctx, x, plan, drop, *params):
+    def forward(ctx, x, plan, drop, entry, exit_, bits, *params):
+        """entry (NormEntry, x = None) / exit_ (NormExit): the normalisations around the call belong to it - the raw tensors come
+        first in params, the results are (allf, picks...), and the launches of bits (FOLD_*) carry them; a bit that is off runs
+        the launch of ops.normalize_stack / ops.norm_permute_pick at that boundary"""
+        ctx.entry, ctx.exit, ctx.bits = entry is not None, exit_, bits
+        inv = None
+        if entry is not None:
+            K = len(entry.raws)
+            ctx.tags = [ops._arena_tag(r) for r in params[:K]]          # pieces of a split tensor: their gradients go into its buffer
+            entry = entry._replace(raws=[_rows(r) for r in params[:K]])
+            params = params[K:]
+            ns, D0 = [r.shape[0] for r in entry.raws], entry.raws[0].shape[1]
+            x = torch.empty(sum(ns), D0, device=entry.raws[0].device, dtype=torch.float32)
+            inv = torch.empty(sum(ns), device=x.device, dtype=torch.float32)
+            ctx.nmeta = (ns, entry.dyns)
+            if not bits & FOLD_A:
+                a_x, a_l, a_n, a_d = _group_arrays(entry.raws, entry.dyns)
+                lib.srec_normalize_group_fwd(K, _ct.addressof(a_x), _ct.addressof(a_l), _ct.addressof(a_n), _ct.addressof(a_d), ptr(x),
+                                             D0, ptr(inv), D0, entry.eps_mode, 1e-12, stream())
         x = _rows(x)
         (NT, D), dev, nm = x.shape, x.device, len(plan.modules)
         strategy = gemm_strategy(ops.PRECISION['matmul'], D, _ld(x), nm, all(params[4 * m].is_contiguous() for m in range(nm)))
@@ -343,41 +412,118 @@ class HGATLayer(torch.autograd.Function):
         dropping = drop is not None and (drop[0] > 0 or drop[1] > 0)
         if dropping:
             x = x.contiguous()          # srec_hg_fwd / srec_hg_bwd read the dropped copies (xin, xres: [NT, D]) with x's row stride
-            dstate, x16 = _drop_prep(x, plan, drop, strategy, (desc,) + live if live is not None else None)
+            dstate, x16 = _drop_prep(x, plan, drop, strategy, (desc,) + live if live is not None else None,
+                                     (entry, inv) if bits & FOLD_A else None)
             plan.fill_drop(desc, dstate)
         elif live is not None:                       # (the lists ride in the dropout launch when there is one)
             la = ptr_array(live[0])
             lib.srec_hg_live_rows(_ct.addressof(desc), _ct.addressof(la), ptr(live[1]), stream())
         xin = [dstate.xc[cv] for cv in plan.mod_conv] if dstate is not None else [x] * nm      # what each module projects
         g16 = _project(xin, x16, plan, params, strategy, P, live)
-        out = torch.empty(NT, D, device=dev, dtype=torch.float32)
         arg = torch.empty(NT, D, device=dev, dtype=torch.uint8)
-        lib.srec_hg_fwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(out), D, ptr(arg), stream())
-        ctx.save_for_backward(x, small, arg, *P, *params)
+        allf = None
+        if exit_ is not None and bits & FOLD_B:              # the aggregation launch writes allf / invr / the pick rows itself
+            n_cat, B = exit_.cat_perm.numel(), exit_.picks[0].numel()
+            allf = torch.empty(n_cat, D, device=dev, dtype=torch.float32)
+            invr = torch.empty(n_cat, device=dev, dtype=torch.float32)
+            bufs = [torch.empty(B, 2 * D, device=dev, dtype=torch.float32) for _ in exit_.picks]   # v = left half of [v | read-out]
+            a_pick, a_out, a_ld = ptr_array(exit_.picks), ptr_array(bufs), (_ct.c_int * len(bufs))(*([2 * D] * len(bufs)))
+            lib.srec_hg_fwd_exit(_ct.addressof(desc), ptr(x), _ld(x), ptr(arg), ptr(exit_.cat_inv), ptr(allf), ptr(invr), len(bufs),
+                                 _ct.addressof(a_pick), _ct.addressof(a_out), _ct.addressof(a_ld), exit_.eps_mode, 1e-12, stream())
+            out = None
+        else:
+            out = torch.empty(NT, D, device=dev, dtype=torch.float32)
+            lib.srec_hg_fwd(_ct.addressof(desc), ptr(x), _ld(x), ptr(out), D, ptr(arg), stream())
         ctx.plan, ctx.lay, ctx.strategy, ctx.drop, ctx.g16 = plan, lay, strategy, dstate, g16
         ctx.defer, ctx.wparams = ops.defer_scope(), [params[4 * m] for m in range(nm)]
-        return out
+        extra = [inv] if inv is not None else []
+        if exit_ is None:
+            ctx.save_for_backward(x, small, arg, *P, *params, *extra)
+            return out
+        if allf is None:
+            allf, invr, bufs = ops.npp_forward(out, exit_.cat_perm, exit_.dyn_t, exit_.dyn_b, exit_.eps_mode, exit_.picks)
+        extra += [exit_.cat_perm, exit_.cat_inv, exit_.cat_seg, allf, invr] + list(exit_.picks)
+        ctx.save_for_backward(x, small, arg, *P, *params, *extra)
+        return (allf,) + tuple(b[:, :D] for b in bufs)
 
     @staticmethod
-    def backward(ctx, g):
-        plan, drop, nm = ctx.plan, ctx.drop, len(ctx.plan.modules)
+    def backward(ctx, g, *g_picks):
+        plan, drop, nm, bits = ctx.plan, ctx.drop, len(ctx.plan.modules), ctx.bits
         x, small, arg, *rest = ctx.saved_tensors
-        P, params = rest[:nm], rest[nm:]
-        g = _rows(g)
+        P, params, extra = rest[:nm], rest[nm:5 * nm], rest[5 * nm:]
+        inv = extra.pop(0) if ctx.entry else None
         NT, D = x.shape
+        xrec = None
+        if ctx.exit is not None:
+            perm, cat_inv, cat_seg, allf, invr, *picks = extra
+            g_allf = _rows(g)
+            gps = [(_rows(gp) if gp is not None else None) for gp in g_picks]
+            if bits & FOLD_C and _ld(g_allf) % 4 == 0:
+                g = torch.empty(NT, D, device=x.device, dtype=torch.float32)       # written by the score-gradient launch
+                xrec = (cat_inv, allf, invr, g_allf, picks, gps)
+            else:
+                g = ops.npp_backward(allf, invr, g_allf, perm, cat_seg, picks, gps, ctx.exit.types, ctx.exit.dyn_b, NT)
+        g = _rows(g)
         # feature dropout with recomputed masks (the tap is off): d x is written once, after the backward-data GEMMs
         late_dx = drop is not None and drop.ms is None and _ld(g) % 4 == 0
-        desc, dP, grads, dx = _backward_graph(ctx, x, g, small, arg, P, params, late_dx)
+        fold_d = bool(late_dx and ctx.entry and bits & FOLD_D)
+        desc, dP, grads, dx = _backward_graph(ctx, x, g, small, arg, P, params, late_dx, xrec, not fold_d)
         gWs = [ops.grad_buf(params[4 * m]) for m in range(nm)]
-        tgts, S = _backward_data(ctx, dP, params, dx)
-        if late_dx:
-            lib.srec_hg_pre_merge(_ct.addressof(desc), ptr(g), _ld(g), ptr(tgts), S, ptr(dx), D, stream())
-        elif drop is not None:
-            lib.srec_hg_drop_merge(ptr(tgts), S, ptr(drop.ms), NT * D, ptr(dx), *drop.rng, stream())
+        tgts, S = _backward_data(ctx, dP, params, dx if dx is not None else x)       # (late_dx: only shape and device are read)
+        dxs = None
+        if ctx.entry:                                  # the raw tensors' gradient rows (inside their arena when they have one)
+            ns, dyns = ctx.nmeta
+            dxall, dxs, o = None, [], 0
+            for n, tag in zip(ns, ctx.tags):
+                if tag is None and dxall is None:
+                    dxall = torch.empty(NT, D, device=x.device, dtype=torch.float32)
+                dxs.append(ops._arena_rows(tag, n, D, x.device) if tag is not None else dxall[o:o + n])
+                o += n
+        if fold_d:
+            a_dx, a_ld = ptr_array(dxs), (_ct.c_int * len(dxs))(*[_ld(t) for t in dxs])
+            lib.srec_hg_pre_merge_norm(_ct.addressof(desc), ptr(g), _ld(g), ptr(tgts), S, ptr(x), ptr(inv), _ct.addressof(a_dx),
+                                       _ct.addressof(a_ld), stream())
+            dxs_done = True
+        else:
+            dxs_done = False
+            if late_dx:
+                lib.srec_hg_pre_merge(_ct.addressof(desc), ptr(g), _ld(g), ptr(tgts), S, ptr(dx), D, stream())
+            elif drop is not None:
+                lib.srec_hg_drop_merge(ptr(tgts), S, ptr(drop.ms), NT * D, ptr(dx), *drop.rng, stream())
         _weight_grads(ctx, x, dP, gWs)
+        if dxs is not None and not dxs_done:
+            a_x, a_l, a_n, a_d = _group_arrays(dxs, dyns, [D] * len(dxs))
+            lib.srec_normalize_group_bwd(len(dxs), _ct.addressof(a_x), _ct.addressof(a_l), _ct.addressof(a_n), _ct.addressof(a_d), ptr(x),
+                                         D, ptr(dx), D, ptr(inv), D, stream())
         outs = [o for m in range(nm) for o in [gWs[m]] + [grads[m][j].view(params[4 * m + 1 + j].shape) for j in range(3)]]
-        return (dx, None, None) + tuple(outs)
+        return (None if dxs is not None else dx, None, None, None, None, None) + tuple(dxs or ()) + tuple(outs)
 
 
-def hgat_layer(x, plan, params, drop=None):
-    return HGATLayer.apply(x, plan, drop, *params)
+def hgat_layer(x, plan, params, drop=None, entry=None, exit_=None):
+    """entry (NormEntry; x is then None) / exit_ (NormExit): the caller's normalisations in front of / behind the layer.  Returns
+    out [NT, D], or with exit_ (allf, [picks]) as ops.norm_permute_pick.  Whether a normalisation rides in the layer's launches
+    is decided here (norm_fold_bits); a boundary that takes no fold at all runs ops.normalize_stack / ops.norm_permute_pick."""
+    D = (entry.raws[0] if entry is not None else x).shape[1]
+    per_type = [sum(1 for (m, sb, db, gr) in plan.insts if plan.blocks[db][1] == t) for t in range(len(plan.types))]
+    if entry is not None and [r.shape[0] for r in entry.raws] != [tp[1] for tp in plan.types]:
+        x, entry = ops.normalize_stack(entry.raws, entry.eps_mode, entry.dyns), None          # (one raw tensor per node type only)
+    if exit_ is not None and not (exit_.cat_perm.numel() == exit_.cat_inv.numel() == sum(tp[1] for tp in plan.types)
+                                  and 0 < len(exit_.picks) <= 4 and all(pk.numel() == plan.B for pk in exit_.picks)):
+        fexit, exit_ = exit_, None               # (the folds pair every stacked row with one concatenated row)
+        outs = hgat_layer(x, plan, params, drop, entry)
+        return ops.norm_permute_pick(outs, fexit.cat_perm, fexit.cat_seg, fexit.picks, fexit.types, fexit.dyn_t, fexit.dyn_b,
+                                     fexit.eps_mode)
+    pf, pa = drop if drop is not None else (0.0, 0.0)
+    bits = norm_fold_bits(ops.NORM_FOLD, plan.H, D, per_type, entry is not None, exit_ is not None, pf, pa, ops.DROP_TAP is not None)
+    if entry is not None and not bits & (FOLD_A | FOLD_D):
+        x, entry = ops.normalize_stack(entry.raws, entry.eps_mode, entry.dyns), None
+    fexit = exit_ if bits & (FOLD_B | FOLD_C) else None
+    outs = HGATLayer.apply(x, plan, drop, entry, fexit, bits, *(tuple(entry.raws) if entry is not None else ()), *params)
+    if exit_ is None:
+        return outs
+    if fexit is None:
+        return ops.norm_permute_pick(outs, exit_.cat_perm, exit_.cat_seg, exit_.picks, exit_.types, exit_.dyn_t, exit_.dyn_b,
+                                     exit_.eps_mode)
+    for o in outs[1:]:
+        o._srec_cat_left = True          # the left half of a private [B, 2 D] buffer (ReadoutHead writes the right half)
+    return outs[0], list(outs[1:])

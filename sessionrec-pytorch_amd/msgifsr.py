@@ -151,16 +151,19 @@ class MSHGNN(nn.Module):
                           layer_id=getattr(self, '_layer_id', 0), live=nlive)
         return plan, params
 
-    def forward_stacked(self, mg, x, all_rels=False):
-        """x: [NT, d] node features of all orders stacked (order-1 rows first) -> [NT, d]; one batched pass"""
+    def forward_stacked(self, mg, x, all_rels=False, entry=None, exit_=None):
+        """x: [NT, d] node features of all orders stacked (order-1 rows first) -> [NT, d]; one batched pass.  entry / exit_
+        (ops.NormEntry, x = None / ops.NormExit): the model's normalisation in front of / behind the layer goes with the call
+        (ops.hgat_layer) - with exit_ the result is (allf, picks) as ops.norm_permute_pick's"""
         pre = self.__dict__.pop('_pre', None)        # the plan the model's prologue launch already folded the weights for
-        if pre is not None and pre[0] is mg and pre[1] == (x.shape[1], bool(all_rels)):
+        d = (entry.raws[0] if entry is not None else x).shape[1]
+        if pre is not None and pre[0] is mg and pre[1] == (d, bool(all_rels)):
             plan, params = pre[2]
         else:
-            plan, params = self.plan(mg, x.shape[1], all_rels)
+            plan, params = self.plan(mg, d, all_rels)
         mod = self.conv1.mods['intra1']
         drop = (mod.feat_drop, mod.attn_drop) if self.training and (mod.feat_drop > 0 or mod.attn_drop > 0) else None
-        return ops.hgat_layer(x, plan, params, drop)
+        return ops.hgat_layer(x, plan, params, drop, entry, exit_)
 
     def forward(self, mg, feat):
         """feat: {k: [N_k, d]} -> {k: [N_k, d]}"""
@@ -393,8 +396,18 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             x = pieces[k - 1]
             dk = mg.dynp('N%d' % k)
             raw[k] = x if k == 1 else (fast[k - 2] if fast is not None else self.expander(x, k, dk, mg.dynp('GK%d' % k)))
-        stacked0 = None
-        if self.norm and 1 < K <= 4 and len(self.layers) > 0:
+        stacked0, entry = None, None
+        multi = self.shard is not None and self.shard.world > 1       # (see MSHGNN.plan: live = live in the GLOBAL batch)
+        # row-sharded training: the replicated gradients are all-reduced in buckets as the backward completes them
+        # (dist.VocabParallel.bucket_ready): the GAT layers' when it passes below them, the read-out head's above them
+        early = getattr(self.shard, 'bucket_ready', None) if (self.shard is not None and self.training) else None
+        # the normalisations around the layers may ride in the first / last layer's launches (ops.hgat_layer decides): nothing
+        # stands between them and the layer on a single device, and nobody else reads the stacked rows without `extra`
+        foldable = (self.norm and 1 < K <= 4 and len(self.layers) > 0 and self.shard is None and ops.NORM_FOLD != 0 and
+                    raw[1].is_cuda and torch.is_grad_enabled() and self.training)
+        if foldable and not self.extra:
+            entry = ops.NormEntry([raw[k] for k in range(1, K + 1)], tuple(mg.dynp('N%d' % k) for k in range(1, K + 1)), 0)
+        elif self.norm and 1 < K <= 4 and len(self.layers) > 0:
             # all orders normalised straight into the stacked matrix the batched layer reads: one launch, no concatenation
             stacked0 = ops.normalize_stack([raw[k] for k in range(1, K + 1)], 0, [mg.dynp('N%d' % k) for k in range(1, K + 1)])
             o = 0
@@ -410,21 +423,26 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         # followed by a hipGraph capture then makes the engine synchronise the capturing stream with the default stream and
         # hipStreamEndCapture crashes (found by tests/test_dist_gpu.py's replayed rank)
         self._s1_feat = feats[1] if self.extra else None
+        live = range(K) if (K == 1 or self.fusion) else (0,)
+        folded = None
         if len(self.layers) > 0:
             # all orders stacked once; every layer is one batched pass over all relations (ops.hgat_layer)
-            stacked = stacked0 if stacked0 is not None else (
+            stacked = stacked0 if stacked0 is not None else None if entry is not None else (
                 feats[1] if K == 1 else torch.cat([feats[k] for k in range(1, K + 1)], 0))
-            multi = self.shard is not None and self.shard.world > 1       # (see MSHGNN.plan: live = live in the GLOBAL batch)
-            # row-sharded training: the replicated gradients are all-reduced in buckets as the backward completes them
-            # (dist.VocabParallel.bucket_ready): the GAT layers' when it passes below them, the read-out head's above them
-            early = getattr(self.shard, 'bucket_ready', None) if (self.shard is not None and self.training) else None
             if early is not None:
                 stacked = ops.grad_mark(stacked, lambda: early(1))
-            for layer in self.layers:
-                stacked = layer.forward_stacked(mg, stacked, multi)
+            exit_ = None
+            if foldable:
+                exit_ = ops.NormExit(mg.cat_perm, mg.field('cat_inv'), mg.cat_seg, [mg.field('lastcat%d' % (i + 1)) for i in live],
+                                     self._npp_types(mg, K), mg.dynp('NT'), dB, 0)
+            for li, layer in enumerate(self.layers):
+                stacked = layer.forward_stacked(mg, stacked, multi, entry if li == 0 else None,
+                                                exit_ if li == len(self.layers) - 1 else None)
+            if exit_ is not None:
+                folded, stacked = stacked, None
             if early is not None:
                 stacked = ops.grad_mark(stacked, lambda: early(0))
-            fuse_npp = self.norm and 1 < K <= 4 and stacked.is_cuda
+            fuse_npp = self.norm and 1 < K <= 4 and raw[1].is_cuda
             if self.norm and not fuse_npp:
                 stacked = ops.normalize(stacked, 0, mg.dynp('N1') if K == 1 else None)   # padded rows are exact zeros
         else:
@@ -434,18 +452,16 @@ class MSGIFSR(_ScoringMixin, nn.Module):
             if self.norm:
                 h = {k: ops.normalize(v, 0, mg.dynp('N%d' % k)) for k, v in h.items()}
             stacked = h[1] if K == 1 else torch.cat([h[k] for k in range(1, K + 1)], 0)
-        live = range(K) if (K == 1 or self.fusion) else (0,)
-        if K == 1:
+        if folded is not None:
+            allf, picked = folded
+            feat_vs = dict(zip(live, picked))
+        elif K == 1:
             allf = stacked
             feat_vs = {i: ops.row_gather(stacked, mg.field('lastcat%d' % (i + 1)), dB) for i in live}
         elif len(self.layers) > 0 and fuse_npp:
             # normalisation + per-session concatenation + last-node picks in one launch (ops.NormPermutePick)
-            types, r0 = [], 0
-            for k in range(1, K + 1):
-                types.append((r0, ncap[k], mg.dynp('N%d' % k)))
-                r0 += ncap[k]
             allf, picked = ops.norm_permute_pick(stacked, mg.cat_perm, mg.cat_seg, [mg.field('lastcat%d' % (i + 1)) for i in live],
-                                                 types, mg.dynp('NT'), dB, 0)
+                                                 self._npp_types(mg, K), mg.dynp('NT'), dB, 0)
             feat_vs = dict(zip(live, picked))
         else:
             allf, picked = ops.permute_and_pick(stacked, mg.cat_perm, mg.field('cat_inv'),
@@ -473,6 +489,15 @@ class MSGIFSR(_ScoringMixin, nn.Module):
         if self.fusion and K > 1:
             return srs                                     # one session vector per order (IFR mixture)
         return srs[0]
+
+    @staticmethod
+    def _npp_types(mg, K):
+        """[(first stacked row, capacity, live count)] of the orders' row blocks in the stacked matrix"""
+        types, r0, ncap = [], 0, mg.meta['ncap']
+        for k in range(1, K + 1):
+            types.append((r0, ncap[k], mg.dynp('N%d' % k)))
+            r0 += ncap[k]
+        return types
 
     # ---- `extra`: repeat / explore mixture (msgifsr.py:281-305)
     def _in_session(self, mg, labels=None):

@@ -871,6 +871,55 @@ def grad_mark(x, fn):
     return GradMark.apply(x, fn) if (x.requires_grad and torch.is_grad_enabled()) else x
 
 
+def parse_norm_fold(text):
+    """SREC_NORM_FOLD: bit mask of the normalisation folds around the MSHGNN layer (hgat.norm_fold_bits): bit 0 layer entry forward,
+    1 layer exit forward, 2 layer exit backward, 3 layer entry backward.  Unset / empty: all (15)"""
+    text = (text or '').strip()
+    if not text:
+        return 15
+    v = int(text, 0)
+    if not 0 <= v <= 15:
+        raise ValueError('SREC_NORM_FOLD must be a bit mask 0 .. 15, got %r' % text)
+    return v
+
+
+NORM_FOLD = parse_norm_fold(os.environ.get('SREC_NORM_FOLD'))       # (tests / A-B runs: 0 = a launch per normalisation)
+
+
+def npp_forward(x, perm, dyn_t, dyn_b, eps_mode, picks):
+    """srec_norm_perm_pick_fwd -> (allf [n_cap, D], invr [n_cap], [B, 2 D] buffers whose left halves are the pick rows)"""
+    NTs, D = x.shape
+    n_cap, B, P = perm.numel(), picks[0].numel(), len(picks)
+    dev = x.device
+    allf = torch.empty(n_cap, D, device=dev, dtype=torch.float32)
+    invr = torch.empty(n_cap, device=dev, dtype=torch.float32)
+    bufs = [torch.empty(B, 2 * D, device=dev, dtype=torch.float32) for _ in range(P)]   # v = left half of [v | read-out]
+    arr, ints = _ct.c_void_p * P, _ct.c_int * P
+    a_pick, a_out = arr(*[p.data_ptr() for p in picks]), arr(*[b.data_ptr() for b in bufs])
+    a_ld = ints(*([2 * D] * P))                         # (ctypes arrays must outlive the call: no temporaries in addressof)
+    lib.srec_norm_perm_pick_fwd(ptr(x), _ld(x), ptr(perm), n_cap, ptr(dyn_t), D, eps_mode, 1e-12, ptr(allf), ptr(invr),
+                                P, B, ptr(dyn_b), _ct.addressof(a_pick), _ct.addressof(a_out), _ct.addressof(a_ld), stream())
+    return allf, invr, bufs
+
+
+def npp_backward(allf, invr, g_allf, perm, cat_seg, picks, gps, types, dyn_b, NTs):
+    """srec_norm_perm_pick_bwd -> dx [NTs, D] (stacked order, every row written)"""
+    D, B, P, nt = allf.shape[1], picks[0].numel(), len(picks), len(types)
+    dx = torch.empty(NTs, D, device=allf.device, dtype=torch.float32)
+    arr, ints = _ct.c_void_p * P, _ct.c_int * P
+    a_pick = arr(*[p.data_ptr() for p in picks])
+    a_g = arr(*[(g.data_ptr() if g is not None else None) for g in gps])
+    a_ld = ints(*[(_ld(g) if g is not None else D) for g in gps])
+    tarr = _ct.c_void_p * nt
+    a_dyn = tarr(*[ptr(t[2]) for t in types])
+    a_r0, a_nc = (_ct.c_int * nt)(*[t[0] for t in types]), (_ct.c_int * nt)(*[t[1] for t in types])
+    lib.srec_norm_perm_pick_bwd(ptr(allf), ptr(invr), ptr(g_allf), _ld(g_allf), ptr(perm), perm.numel(), ptr(cat_seg), B,
+                                ptr(dyn_b), D, P,
+                                _ct.addressof(a_pick), _ct.addressof(a_g), _ct.addressof(a_ld), ptr(dx), D, nt,
+                                _ct.addressof(a_r0), _ct.addressof(a_nc), _ct.addressof(a_dyn), NTs, stream())
+    return dx
+
+
 class NormPermutePick(torch.autograd.Function):
     """(allf, v_0, v_1, ...) = (normalize(x)[perm], normalize(x)[pick_0], ...): MSGIFSR between its last MSHGNN layer and the
     read-out (msgifsr.py:260-264 F.normalize, :131-147 per-session concatenation and last-node picks) in ONE launch, and its
@@ -880,39 +929,19 @@ class NormPermutePick(torch.autograd.Function):
     def forward(ctx, x, perm, cat_seg, dyn_t, dyn_b, types, eps_mode, *picks):
         x = _rows(x)
         NTs, D = x.shape
-        n_cap, B, P = perm.numel(), picks[0].numel(), len(picks)
-        dev = x.device
-        allf = torch.empty(n_cap, D, device=dev, dtype=torch.float32)
-        invr = torch.empty(n_cap, device=dev, dtype=torch.float32)
-        bufs = [torch.empty(B, 2 * D, device=dev, dtype=torch.float32) for _ in range(P)]   # v = left half of [v | read-out]
-        arr, ints = _ct.c_void_p * P, _ct.c_int * P
-        a_pick, a_out = arr(*[p.data_ptr() for p in picks]), arr(*[b.data_ptr() for b in bufs])
-        a_ld = ints(*([2 * D] * P))                         # (ctypes arrays must outlive the call: no temporaries in addressof)
-        lib.srec_norm_perm_pick_fwd(ptr(x), _ld(x), ptr(perm), n_cap, ptr(dyn_t), D, eps_mode, 1e-12, ptr(allf), ptr(invr),
-                                    P, B, ptr(dyn_b), _ct.addressof(a_pick), _ct.addressof(a_out), _ct.addressof(a_ld), stream())
+        allf, invr, bufs = npp_forward(x, perm, dyn_t, dyn_b, eps_mode, picks)
         ctx.save_for_backward(perm, cat_seg, allf, invr, *picks)
-        ctx.meta = (NTs, D, B, dyn_b, types)
+        ctx.meta = (NTs, D, picks[0].numel(), dyn_b, types)
         return (allf,) + tuple(b[:, :D] for b in bufs)
 
     @staticmethod
     def backward(ctx, g_allf, *g_picks):
         perm, cat_seg, allf, invr, *picks = ctx.saved_tensors
         NTs, D, B, dyn_b, types = ctx.meta
-        P, nt = len(picks), len(types)
+        P = len(picks)
         g_allf = _rows(g_allf)
         gps = [(_rows(g) if g is not None else None) for g in g_picks]
-        dx = torch.empty(NTs, D, device=allf.device, dtype=torch.float32)
-        arr, ints = _ct.c_void_p * P, _ct.c_int * P
-        a_pick = arr(*[p.data_ptr() for p in picks])
-        a_g = arr(*[(g.data_ptr() if g is not None else None) for g in gps])
-        a_ld = ints(*[(_ld(g) if g is not None else D) for g in gps])
-        tarr = _ct.c_void_p * nt
-        a_dyn = tarr(*[ptr(t[2]) for t in types])
-        a_r0, a_nc = (_ct.c_int * nt)(*[t[0] for t in types]), (_ct.c_int * nt)(*[t[1] for t in types])
-        lib.srec_norm_perm_pick_bwd(ptr(allf), ptr(invr), ptr(g_allf), _ld(g_allf), ptr(perm), perm.numel(), ptr(cat_seg), B,
-                                    ptr(dyn_b), D, P,
-                                    _ct.addressof(a_pick), _ct.addressof(a_g), _ct.addressof(a_ld), ptr(dx), D, nt,
-                                    _ct.addressof(a_r0), _ct.addressof(a_nc), _ct.addressof(a_dyn), NTs, stream())
+        dx = npp_backward(allf, invr, g_allf, perm, cat_seg, picks, gps, types, dyn_b, NTs)
         return (dx,) + (None,) * (6 + P)
 
 
@@ -1626,7 +1655,7 @@ def step_prologue(w16=(), gru=(), head=(), fold=None):
 HG_LIVE_ROWS = os.environ.get('SREC_HG_LIVE_ROWS', '1') != '0'
 DROP_TAP = None      # tests: set to a list to receive {'ms': [2, NT, D], 'mk': [per instance (E*H,)]} of every dropout layer call
 
-from .hgat import HgPlan, HGATLayer, hgat_layer  # noqa: E402,F401  (the MSHGNN layer: hgat.py imports this module)
+from .hgat import HgPlan, HGATLayer, NormEntry, NormExit, hgat_layer, norm_fold_bits  # noqa: E402,F401  (the MSHGNN layer: hgat.py imports this module)
 from .gru import (  # noqa: E402,F401  (the GRU step, the k-gram expander: gru.py imports this module)
     GramCombine, GruOrder, GRUExpand, GRUExpandAll, GRUPointwise, _gru_wfrag_args, expand_path, gram_combine, gru_expand,
     gru_expand_all, gru_expand_fast_ok, gru_fused_bwd_desc, gru_fused_desc, gru_fused_ok, gru_step, gru_step_desc, gru_wfrag,
