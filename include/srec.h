@@ -852,6 +852,32 @@ int srec_diversify(const float* X, int ld_x, long n_rows, const int* row, const 
 int srec_cap_select(const int* ids, const float* s, int B, int P, int K, const int* category, long n_items, const int* caps,
                     int G, int* pick, float* val, int* kept, int* scanned, void* stream);
 
+/* ---- serving: per-session hide / boost lists merged into an ordered pool (personal.hip) -----------------------------------
+ * "Never show this user these items, lift those": a sparse list per session instead of a dense [B, V] bias.  If M items of a
+ * session change their value, its new top-K is the top-K of (the old top-(K + M) without those items) and (those items with
+ * their new values): no catalogue pass, one merge per session.
+ * Per session an ORDERED pool of P slots: pool_ids[b * P + i], pool_s[b * P + i] - what srec_score_select /
+ * srec_score_select_many_order wrote.  A slot is FILLED iff pool_ids >= 0; unfilled slots may stand anywhere and are skipped;
+ * the filled ones are in served order (value descending, id ascending), which the kernel relies on.
+ * The list: M slots, items[b * M + j] >= 0 is a FILLED slot (int32 global id; ids are only compared, never used as an index).
+ * An id met again in a later slot of the session is ignored: the first slot wins.  t_j = base[b * M + j] + bias[b * M + j],
+ * one fp32 add; bias == NULL: every listed item is hidden, t_j = -INFINITY.  base is what srec_score_items returns for the
+ * slot.  A listed item is a CANDIDATE iff t_j > -INFINITY (a -INFINITY base - seen, filtered - stays out whatever the bias).
+ * A filled pool slot SURVIVES iff its id is in no filled list slot of the session, whatever the list says about it.
+ *   hit [B]: the filled pool slots that did not survive.
+ *   ids_out / val_out [B, K]: the first K of survivors and candidates by (value descending, id ascending), floats compared as
+ *     the select kernels do (-0.0 == +0.0, no NaN); val_out is the survivor's pool_s copied bit for bit, or t_j; the tail is
+ *     (-1, -INFINITY).  src [B, K] (may be NULL): i for pool slot i, P + j for list slot j, -1 in the tail.
+ *   kept [B]: the filled output slots, min(K, survivors + candidates).
+ * With hit[b] <= P - K, or the pool's last slot unfilled, the output is the exact top-K of the adjusted catalogue: anything
+ * outside the pool scores at or below its last slot, and K survivors stand at or above that.  P = K + M always suffices.
+ * One workgroup per session, no atomics, no workspace: a session's result is the same bits in any batch.
+ * SREC_BAD_ARG and no launch unless 1 <= P <= SREC_CAP_MAXP, 1 <= M <= SREC_PERSONAL_MAXM, 1 <= K <= SREC_CAP_MAXP, pool_ids /
+ * pool_s / items / base / ids_out / val_out / hit / kept non-null, every given pointer aligned to 4 bytes.  B <= 0 returns 0. */
+#define SREC_PERSONAL_MAXM 1024
+int srec_personal_merge(const int* pool_ids, const float* pool_s, int B, int P, const int* items, const float* base,
+                        const float* bias, int M, int K, int* ids_out, float* val_out, int* src, int* hit, int* kept, void* stream);
+
 /* ---- serving: calibrated slates - the greedy re-rank of a pool towards a target category distribution (calibrate.hip; Steck,
  * "Calibrated Recommendations", RecSys 2018).  The soft counterpart of the caps above; plain arguments, no workspace.
  * Per session a pool of M <= SREC_SELECT_MAXK slots: ids[b * M + i] a global item id and s[b * M + i] its value, as

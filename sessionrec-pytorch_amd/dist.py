@@ -468,6 +468,11 @@ class HipLocal:
         """ops.cap_select over a pool whose ids the select kernels wrote (checked): (val [B,k], pick [B,k], kept [B], scanned [B])"""
         return self.ops.cap_select(ids, val, rule, k, checked=True)
 
+    def personal_merge(self, pool_ids, pool_val, items, base, bias, k):
+        """ops.personal_merge over a pool whose ids the select kernels wrote and lists ops.personal_lists looked at (checked):
+        (val [B,k], ids [B,k], src [B,k], hit [B], kept [B])"""
+        return self.ops.personal_merge(pool_ids, pool_val, items, base, bias, k, checked=True)
+
     def calibrate(self, ids, val, category, k, weight, tcat, tw, alpha):
         """ops.calibrate over a pool whose ids the select kernel wrote and a target the caller has looked at (checked):
         (val [B,k], pick [B,k], obj [B,k], kl [B])"""
@@ -1129,6 +1134,17 @@ class VocabParallel:
         looks at nothing but the pool and the target: no row of the table is read, so there is NO collective - every rank
         runs the kernel on the pool it holds and gets the single-device call's result, bit for bit."""
         return self.local.calibrate(ids, val, category, k, weight, tcat, tw, alpha)
+
+    def personal_merge(self, pool_ids, pool_val, items, base, bias, k, data_parallel=False):
+        """the per-session list merge of ops.personal_merge over the sharded table (val [B,k], ids [B,k], src [B,k], hit [B],
+        kept [B]): pool_ids / pool_val [B, P] every session's ordered pool - what select() / select_many() returned - items
+        [B, M] its list, base [B, M] what score_items() over the sharded table returned for it and bias [B, M] or None; the same
+        on every rank (data_parallel: this rank's own sessions, as those calls returned them).  The merge compares global ids
+        and values it is handed: no row of the table is read, so there is NO collective - every rank runs the kernel on what
+        it holds and gets the single-device call's result for those operands, bit for bit."""
+        return self.local.personal_merge(pool_ids, pool_val, items, base, bias, k)
+
+    personal = personal_merge   # (the name of the served call: ServingMixin._ROUTES)
 
     def any_session(self, flag, data_parallel=False):
         """host bool, the SAME on every rank: is `flag` (bool [B], one entry per session) set for any session of the call?

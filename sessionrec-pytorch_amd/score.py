@@ -1222,6 +1222,159 @@ def cap_select(ids, val, rule, k, checked=False):
     return out_val, pick, kept, scanned
 
 
+# per-session hide / boost lists: items int32 [rows, M] (-1: padding), bias fp32 [rows, M] or None (every listed item is hidden),
+# M; rows = the sessions, or 1 for a list shared by all of them while their number is not known (personal_lists builds it)
+PersonalLists = namedtuple('PersonalLists', 'items bias M')
+
+
+def _padded_rows(who, what, x, pad, dtype):
+    """(tensor [rows, M] or [M], row lengths or None) of x - a tensor, a flat sequence or a sequence of sequences of unequal
+    length, short rows padded with `pad` (the lengths are then given); ValueError in the words of `who`"""
+    if torch.is_tensor(x):
+        return x.detach(), None
+    try:
+        rows = list(x)
+        if rows and all(isinstance(r, (list, tuple)) for r in rows):
+            M = max(len(r) for r in rows)
+            return torch.tensor([list(r) + [pad] * (M - len(r)) for r in rows], dtype=dtype).view(len(rows), M), [len(r) for r in rows]
+        return torch.as_tensor(rows), None
+    except (TypeError, ValueError, RuntimeError, OverflowError):
+        raise ValueError('%s: %s must be a tensor [B, M] or [M], or a list of per-session lists' % (who, what)) from None
+
+
+def personal_lists(who, items, bias, B, num_items, device):
+    """PersonalLists(items int32 [B, M], bias fp32 [B, M] or None, M) on `device`: the per-session lists personal_merge and the
+    models' recommend_personal take.  items: an integer tensor [B, M], or [M] shared by all sessions, -1 = padding - or Python
+    lists, one per session, of unequal length (padded here).  bias: None (every listed item is hidden) or floating, shaped
+    like items (lists: as long as the items' lists), the number ADDED to the item's score; -inf hides the item; the entry of
+    a padding slot is not looked at.  B: the sessions, or None while their number is not known - a shared list then stays one
+    row.  Checked before any launch, with ONE device-to-host read: every id in [-1, num_items), no id twice in a row, bias
+    without NaN and +inf; and 1 <= M <= SREC_PERSONAL_MAXM.  ValueError in the words of `who`."""
+    mmax = CONST['SREC_PERSONAL_MAXM']
+    it, lens = _padded_rows(who, 'personal_items', items, -1, torch.int64)
+    if it.is_floating_point() or it.is_complex() or it.dtype == torch.bool or it.dim() not in (1, 2):
+        raise ValueError('%s: personal_items must be an integer tensor [B, M] or [M], got %s %s' % (who, it.dtype, tuple(it.shape)))
+    M = it.shape[-1]
+    if not 1 <= M <= mmax:
+        raise ValueError('%s: %d listed items per session; between 1 and %d are merged in one call' % (who, M, mmax))
+    it = it.reshape(-1, M)
+    if B is not None and it.shape[0] not in (1, int(B)):
+        raise ValueError('%s: personal_items for %d sessions, the batch has %d' % (who, it.shape[0], B))
+    bs = None
+    if bias is not None:
+        bs, blens = _padded_rows(who, 'personal_bias', bias, 0.0, torch.float32)
+        if blens is not None and blens != (lens if lens is not None else [M] * len(blens)):
+            raise ValueError('%s: the lists of personal_bias must be as long as those of personal_items' % who)
+        if not bs.is_floating_point() or bs.numel() != it.numel() or bs.shape[-1] != M:
+            raise ValueError('%s: personal_bias must be a floating tensor %s like personal_items, got %s %s'
+                             % (who, tuple(it.shape), bs.dtype, tuple(bs.shape)))
+        bs = bs.reshape(-1, M).to(device=device, dtype=torch.float32)
+    it = it.to(device=device, dtype=torch.int64)
+    if it.numel() > 0:
+        rows = it.sort(dim=1).values
+        flags = [it.min(), it.max(), ((rows[:, 1:] == rows[:, :-1]) & (rows[:, 1:] >= 0)).any().to(torch.int64)]
+        if bs is not None:
+            flags.append(((torch.isnan(bs) | (bs == float('inf'))) & (it >= 0)).any().to(torch.int64))
+        lo, hi, dup, *bad = torch.stack(flags).tolist()             # the one device-to-host read
+        if lo < -1 or hi >= int(num_items):
+            raise ValueError('%s: listed item id %d; ids are in [0, %d), or -1 for a padding slot'
+                             % (who, lo if lo < -1 else hi, num_items))
+        if dup:
+            raise ValueError('%s: an item id appears twice in a session\'s list; every id at most once per session' % who)
+        if bad and bad[0]:
+            raise ValueError('%s: personal_bias holds NaN or +inf; values are finite, or -inf to hide the item' % who)
+    if B is not None and it.shape[0] != int(B):
+        it = it.expand(int(B), M)
+        bs = None if bs is None else bs.expand(int(B), M)
+    return PersonalLists(it.to(torch.int32).contiguous(), None if bs is None else bs.contiguous(), M)
+
+
+def personal_k(who, k, M):
+    """k of a personalised list as recommend_personal takes it, or ValueError in the words of `who`: 1 <= k and k + M <=
+    SREC_CAP_MAXP (the pool that is always complete holds k + M items)"""
+    pmax = CONST['SREC_CAP_MAXP']
+    k = int(k)
+    if k < 1 or k + int(M) > pmax:
+        raise ValueError('%s: k = %d with %d listed items per session; k >= 1 and k + the list\'s length <= %d (recommend_many()\'s '
+                         'limit: the pool that is always complete holds both)' % (who, k, M, pmax))
+    return k
+
+
+def personal_merge(pool_ids, pool_val, items, base, bias, k, checked=False):
+    """(val fp32 [B,k], ids int32 [B,k], src int32 [B,k], hit int32 [B], kept int32 [B]): the first k items per session of an
+    ORDERED pool after a sparse list of items changed its scores - csrc/personal.hip, one workgroup per session, no [B, V] bias
+    and no catalogue pass.  Pool slot i of session b holds the item pool_ids[b, i] and the value pool_val[b, i] - what
+    score_select / score_select_many return; ids < 0 is an unfilled slot.  List slot j holds items[b, j] (-1: padding), its
+    score base[b, j] - what score_items returns for it - and bias[b, j]; its new value is t = base + bias (one fp32 add), and
+    bias=None hides every listed item.
+      a pool slot SURVIVES iff its id is in no filled list slot; hit = the filled pool slots that do not;
+      a listed item is a CANDIDATE iff t > -inf (a -inf base - seen, filtered - stays out whatever the bias);
+      the output is the first k of survivors and candidates by (value descending, id ascending): val (the pool's bits, or t),
+      ids, src (pool slot i, or P + j for list slot j), the tail (-inf, -1, -1); kept = the filled output slots.
+    With hit <= P - k, or the pool's last slot unfilled, that is the exact top-k of the adjusted catalogue.
+    pool_ids: [B, P] and items: [B, M] of any integer dtype (in a wider dtype an id of 2^31 - 1 or more is an unfilled slot: no
+    catalogue of int32 size holds it); pool_val, base: fp32 like them; bias: floating like items, or None (views are taken as
+    they are: made contiguous here); 1 <= P <= 4096, 1 <= M <= 1024, 1 <= k <= 4096; everything on ONE device (nothing is moved).
+    Wrong shapes, dtypes, devices and k raise ValueError before any launch, and - unless checked=True, the caller vouches - so
+    does an id that stands twice in a row of items (ONE device-to-host read).  Under checked=True the first slot of a repeated
+    id wins and the later ones are ignored."""
+    who = 'personal_merge'
+    pmax, mmax = CONST['SREC_CAP_MAXP'], CONST['SREC_PERSONAL_MAXM']
+    pool_ids, pool_val, items, base = pool_ids.detach(), pool_val.detach(), items.detach(), base.detach()
+    for what, t in (('pool_ids', pool_ids), ('items', items)):
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 2:
+            raise ValueError('%s: %s must be an integer tensor [B, %s], got %s %s'
+                             % (who, what, 'P' if what == 'pool_ids' else 'M', t.dtype, tuple(t.shape)))
+    if pool_val.dtype != torch.float32 or pool_val.shape != pool_ids.shape:
+        raise ValueError('%s: pool_val must be fp32 %s like pool_ids, got %s %s'
+                         % (who, tuple(pool_ids.shape), pool_val.dtype, tuple(pool_val.shape)))
+    if base.dtype != torch.float32 or base.shape != items.shape:
+        raise ValueError('%s: base must be fp32 %s like items, got %s %s' % (who, tuple(items.shape), base.dtype, tuple(base.shape)))
+    if bias is not None:
+        bias = bias.detach()
+        if not bias.is_floating_point() or bias.shape != items.shape:
+            raise ValueError('%s: bias must be a floating tensor %s like items (or None: hide them), got %s %s'
+                             % (who, tuple(items.shape), bias.dtype, tuple(bias.shape)))
+    (B, P), M = pool_ids.shape, items.shape[1]
+    if items.shape[0] != B:
+        raise ValueError('%s: items for %d sessions, the pool has %d' % (who, items.shape[0], B))
+    if not 1 <= P <= pmax:
+        raise ValueError('%s: a pool of %d slots per session; csrc/personal.hip takes between 1 and %d' % (who, P, pmax))
+    if not 1 <= M <= mmax:
+        raise ValueError('%s: %d listed items per session; csrc/personal.hip takes between 1 and %d' % (who, M, mmax))
+    k = int(k)
+    if not 1 <= k <= pmax:
+        raise ValueError('%s: k = %d; csrc/personal.hip returns between 1 and %d items per session' % (who, k, pmax))
+    dev = pool_ids.device
+    if not (pool_val.device == items.device == base.device == dev) or (bias is not None and bias.device != dev):
+        raise ValueError('%s: pool_ids (%s), pool_val (%s), items (%s), base (%s) and bias must be on one device'
+                         % (who, dev, pool_val.device, items.device, base.device))
+    if not checked and B > 0:
+        rows = items.sort(dim=1).values
+        if bool(((rows[:, 1:] == rows[:, :-1]) & (rows[:, 1:] >= 0)).any()):       # the one device-to-host read
+            raise ValueError('%s: an item id appears twice in a row of items; every id at most once per session (checked=True: '
+                             'the first slot wins)' % who)
+
+    def int32(t):                                                   # (an id beyond int32 must not wrap into the catalogue)
+        if t.dtype == torch.int64:
+            t = torch.where((t < 0) | (t >= 2 ** 31 - 1), torch.full_like(t, -1), t)
+        return t.to(torch.int32).contiguous()
+    pool_ids, items = int32(pool_ids), int32(items)
+    pool_val, base = pool_val.contiguous(), base.contiguous()
+    if bias is not None:
+        bias = bias.to(torch.float32).contiguous()
+    val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    ids = torch.empty(B, k, device=dev, dtype=torch.int32)
+    src = torch.empty(B, k, device=dev, dtype=torch.int32)
+    hit = torch.empty(B, device=dev, dtype=torch.int32)
+    kept = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return val, ids, src, hit, kept
+    lib.srec_personal_merge(ptr(pool_ids), ptr(pool_val), B, P, ptr(items), ptr(base), ptr(bias), M, k, ptr(ids), ptr(val),
+                            ptr(src), ptr(hit), ptr(kept), stream())
+    return val, ids, src, hit, kept
+
+
 def calibrate_scalars(who, k, weight, alpha, M=None):
     """(k, weight, alpha) as the library takes them, or ValueError in the words of `who`: k in 1 .. 128 (and <= M, the pool,
     when given: M itself in 1 .. 128), weight a number in [0, 1], alpha (the smoothing of the calibration term) in (0, 1).

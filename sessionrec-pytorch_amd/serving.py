@@ -1,5 +1,5 @@
 """The serving surface every model shares: recommend / recommend_many / recommend_diverse / recommend_capped /
-recommend_calibrated, sample, cutoff, log_mass, score_items / rerank, served_rank / rank_items, the list measures
+recommend_calibrated / recommend_personal, sample, cutoff, log_mass, score_items / rerank, served_rank / rank_items, the list measures
 list_diversity / list_calibration, and the evaluation calls topk / target_rank.
 
 ServingMixin is the base of srgnn._ScoringMixin, which supplies what it needs of a model: _table, _state, _col_scale, _lse,
@@ -69,6 +69,7 @@ class ServingMixin:
                'norm': ('score_norm', {}), 'cutoff': ('score_cutoff', {}), 'diversify': ('diversify', {'checked': True}),      # (the pool's ids are the select kernel's)
                'cap': ('cap_select', {'checked': True}),            # (the pool's ids are the select kernels')
                'calibrate': ('calibrate', {'checked': True}),       # (... and the target is _calibration_target's)
+               'personal': ('personal_merge', {'checked': True}),   # (... and the lists are ops.personal_lists')
                'score_items': ('score_items', {'checked': True}),   # (model.score_items looked; sample() passes the kernel's ids)
                'ahead': ('score_ahead', {}), 'ahead_many': ('score_ahead_many', {})}
 
@@ -82,7 +83,7 @@ class ServingMixin:
         return getattr(ops, fn), kw
 
     def _run(self, q, name, *lead, **kw):
-        """served call `name` (a key of _ROUTES but 'diversify', 'cap' and 'calibrate', which score nothing) over the Query q.  The one place that
+        """served call `name` (a key of _ROUTES but 'diversify', 'cap', 'calibrate' and 'personal', which score nothing) over the Query q.  The one place that
         knows the routes' positional order: (srs, table, cs, *lead, off_ex, off_in, listed, drop_listed - not for
         'target_rank', which drops nothing - then keywords only).  lead: k | items | (labels, target) | (items, target), as
         the route takes them; kw: keywords of the call beyond the route's own and the bias (the criteria of cutoff, floor=,
@@ -282,6 +283,64 @@ class ServingMixin:
             picked = ids.gather(1, pick.clamp(min=0).long())
             out = pval, torch.where(pick < 0, torch.full_like(picked, -1), picked)
             return out + (complete,) if return_complete else out
+
+    def recommend_personal(self, *inputs, k=20, personal_items, personal_bias=None, pool=None, exclude_seen=False, item_bias=None,
+                           item_group=None, return_complete=False):
+        """(log_probs fp32 [B,k], item_ids int32 [B,k]) in served order: recommend()'s top-k under the same keywords with a
+        sparse list of items PER SESSION re-scored - "never show this user what they bought or dismissed", "page 2 without
+        page 1", "discount what was shown without a click", "lift what is in the cart" - without the dense [B, V] bias that
+        item_bias [B, V] with item_group = arange(B) would be.  personal_items: [B, M] integer ids, or [M] shared by all
+        sessions, -1 = padding - or Python lists, one per session, of unequal length; M <= 1024 and every id at most once
+        per session.  personal_bias: shaped like personal_items, floating, ADDED to the listed item's value (-inf hides it);
+        None: none of the listed items is ever shown.  A listed item's value is score_items(same keywords) of it plus its bias
+        (one fp32 add; an item that scores -inf - the session's own under exclude_seen, item_bias -inf - stays out whatever its
+        bias); every other value is the pool's own number, bit for bit.  A list that runs short ends in (-inf, -1) slots.
+        If M items of a session change their value, its new top-k is the top-k of (the old top-(k + M) without them) and (the M
+        items re-scored): the catalogue pass stays what it is, score_items() gives the M base values and ONE more launch merges
+        the two per session (csrc/personal.hip; ops.personal_merge).  1 <= k, k + M <= 4096.
+        The pool: pool=P (k <= P <= 4096) takes that pool alone - recommend(k=P) for P <= 128, recommend_many(k=P) beyond.
+        pool=None with k + M <= 128: one pool of k + M items, always complete.  pool=None with k <= 128 < k + M: the one-pass
+        pool of 128 first; with hit = the pool's items on the session's list, a session is COMPLETE when 128 - hit >= k or the
+        pool's last slot is unfilled (the pool was the whole eligible catalogue); ONE device-to-host read of "any session
+        incomplete" follows, and if so the WHOLE batch is re-run on recommend_many(k + M) and that result is returned - one
+        pool per call, so the values never mix two kernels' round-off.  pool=None with k > 128: k + M directly.
+        return_complete=True adds a bool [B]: False where the list may differ from the top-k of the adjusted catalogue (only
+        with pool= too small for the list).  exclude_seen, item_bias / item_group, mixtures (MSGIFSR fusion / extra) and
+        row-sharded tables mean what they mean in recommend(): the merge needs no collective
+        (dist.VocabParallel.personal_merge), under data-parallel feeding the lists travel with the rank's own sessions, and
+        the "any session incomplete" flag is max-all-reduced first, so that all ranks enter the larger pool's collectives
+        together or not at all.  Runs in eval mode under torch.no_grad(); k, pool, the lists and item_bias / item_group are
+        checked before anything of the model runs (ValueError; one device-to-host read for the lists).
+        Out of scope: renormalize=True (the normaliser would need the listed items' mass corrected, and that subtraction
+        cancels in fp32: there is no such keyword); lists together with sample(), cutoff(), recommend_diverse() /
+        recommend_capped() / recommend_calibrated(); served_rank() / rank_items() under lists; more than 1024 listed items."""
+        who, pmax = 'recommend_personal', ops.CONST['SREC_CAP_MAXP']
+        lists = ops.personal_lists(who, personal_items, personal_bias, None, self._num_items(), self._table().device)
+        M = lists.M
+        k = ops.personal_k(who, k, M)
+        if pool is not None:
+            pool = int(pool)
+            if not k <= pool <= pmax:
+                raise ValueError('%s: pool = %d; it holds at least the k = %d items asked for and at most %d (recommend_many()\'s '
+                                 'limit)' % (who, pool, k, pmax))
+        bias = self._item_bias(who, item_bias, item_group)
+        stages = [pool] if pool is not None else [128, k + M] if k <= 128 < k + M else [k + M]
+        fn, kw = self._route('personal')
+        with _Serving(self):
+            q = self._served(*inputs, exclude_seen=exclude_seen, renormalize=False, **bias)
+            B = q.srs[0].shape[0]
+            if lists.items.shape[0] not in (1, B):
+                raise ValueError('%s: personal_items for %d sessions, the batch has %d' % (who, lists.items.shape[0], B))
+            items = lists.items.expand(B, M).contiguous()
+            pbias = None if lists.bias is None else lists.bias.expand(B, M).contiguous()
+            base = self._run(q, 'score_items', items)
+            for P in stages:
+                val, ids = self._run(q, 'select' if P <= 128 else 'select_many', P)
+                pval, pids, _, hit, _ = fn(ids, val, items, base, pbias, k, **kw)
+                complete = (hit <= P - k) | (ids[:, -1] < 0)
+                if P == stages[-1] or not self._any_session(~complete):      # (the one device-to-host read, only with a stage to go)
+                    break
+            return (pval, pids, complete) if return_complete else (pval, pids)
 
     def _any_session(self, flag):
         """host bool: is flag [B] set for any session of the call - of ANY rank's sessions over a sharded table fed

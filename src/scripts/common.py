@@ -246,6 +246,80 @@ def read_calibration(p, args):
     return dict(item_category=item_category, weight=args.calibrate, alpha=alpha)
 
 
+def personal_flags(p):
+    """the per-session hide / boost lists of scripts/recommend.py (model.recommend_personal)"""
+    p.add_argument('--hide', default=None, metavar='FILE',
+                   help='items a session is never shown: line i holds those of session i, separated by commas or tabs (`id` or '
+                        '`id:anything`, so an output file of this script is one: page 2 is --hide page1.txt); ONE line serves all '
+                        'sessions; -1 or an empty line: none')
+    p.add_argument('--session-bias', default=None, metavar='FILE',
+                   help='added to the log-probability of the named items of a session before ranking: the layout of --hide with '
+                        '`id:value` entries; an id in both files is hidden')
+
+
+MAX_PERSONAL = 1024         # SREC_PERSONAL_MAXM (include/srec.h)
+
+
+def read_personal_file(path, valued):
+    """[{item id: value}, ...], one dict per line of the file (an empty line: an empty dict): entries separated by commas or
+    tabs, `id` or `id:anything` (valued: `id:value`, the value a number that is neither NaN nor +inf); -1 names nothing.
+    ValueError names the line that is malformed or names an id twice"""
+    out = []
+    with open(path) as f:
+        for n, line in enumerate(f.read().splitlines(), 1):
+            row = {}
+            for entry in filter(None, (e.strip() for e in line.replace('\t', ',').split(','))):
+                head, sep, tail = entry.partition(':')
+                try:
+                    i = int(head)
+                    v = float(tail) if valued else float('-inf')
+                    if valued and (not sep or v != v or v == float('inf')):
+                        raise ValueError
+                except ValueError:
+                    raise ValueError('%s line %d: `%s` is not `%s`' % (path, n, entry, 'id:value' if valued else 'id` or `id:anything')) from None
+                if i == -1:
+                    continue
+                if i in row:
+                    raise ValueError('%s line %d: item %d is named twice' % (path, n, i))
+                row[i] = v
+            out.append(row)
+    return out
+
+
+def read_personal(p, args, n_sessions):
+    """the keywords personal_items / personal_bias of model.recommend_personal from --hide / --session-bias, as Python lists
+    with one row per session or ONE row for all of them (personal_bias None with --hide alone), or None when neither is given.
+    Read and checked against <dataset-dir>/num_items.txt and the number of sessions before any model is built; p.error() for
+    a file that cannot be read, a malformed entry, an id outside the catalogue or twice on a line, more than MAX_PERSONAL
+    entries on a line and a line count that is neither 1 nor the number of sessions.  An id in both files is hidden."""
+    if args.hide is None and args.session_bias is None:
+        return None
+    try:
+        with open(Path(args.dataset_dir) / 'num_items.txt') as f:
+            num_items = int(f.readline())
+        files = [(flag, read_personal_file(path, valued)) for flag, path, valued in
+                 (('--session-bias', args.session_bias, True), ('--hide', args.hide, False)) if path is not None]
+    except (OSError, ValueError) as e:
+        p.error(str(e))
+    for flag, rows in files:
+        if len(rows) not in (1, n_sessions):
+            p.error('%s: %d lines for %d sessions; one line per session, or ONE line for all of them' % (flag, len(rows), n_sessions))
+        for n, row in enumerate(rows, 1):
+            bad = [i for i in row if not 0 <= i < num_items]
+            if bad:
+                p.error('%s line %d: item id %d; ids are in [0, %d), or -1 for none' % (flag, n, bad[0], num_items))
+    merged = [{} for _ in range(max(len(rows) for _, rows in files))]
+    for _, rows in files:                           # (--hide last: an id in both files is hidden)
+        for n, m in enumerate(merged):
+            m.update(rows[n if len(rows) > 1 else 0])
+    for n, m in enumerate(merged, 1):
+        if len(m) > MAX_PERSONAL:
+            p.error('--hide / --session-bias line %d: %d items; at most %d per session' % (n, len(m), MAX_PERSONAL))
+    items = [sorted(m) or [-1] for m in merged]
+    bias = None if args.session_bias is None else [[m.get(i, 0.0) for i in row] for row, m in zip(items, merged)]
+    return dict(personal_items=items, personal_bias=bias)
+
+
 def build_model(model_name, args, num_items, device, caps=None):
     """(model on the CPU, evaluation collate_fn, training collate_fn) of a launcher's flags (run, scripts/recommend.py)"""
     from src.models import LESSR, MSGIFSR, NISER, SRGNN

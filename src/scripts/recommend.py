@@ -33,12 +33,22 @@ most probable ones for a batch in which some session's list runs short.  Same ou
 min(128, max(4 top, top))) into a slate whose category mix follows that of the session's own items (model.recommend_calibrated:
 greedy on (1 - W) * value - W * KL(target, list), one more kernel, csrc/calibrate.hip); --calibrate-smooth A (default 0.01)
 is the smoothing of the KL term.  Same output format, in PICK order, with the items' own values.  Not together with --sample,
---diversity, --max-per-category or --category-caps."""
+--diversity, --max-per-category or --category-caps.
+--hide FILE names the items every session must NOT be shown: line i holds those of session i (ONE line: of every session),
+separated by commas or tabs, each `id` or `id:anything` - an output file of this script is one, so page 2 is
+
+    python scripts/recommend.py ... --top 10 --output page1.txt ;  python scripts/recommend.py ... --top 10 --hide page1.txt
+
+--session-bias FILE (the same layout, `id:value` entries) adds the value to the log-probability of that item for that session
+before ranking; an id in both files is hidden (model.recommend_personal: the --top + M most probable items merged with the M
+listed ones re-scored, one more kernel, csrc/personal.hip - no dense per-session bias).  --pool M (--top <= M <= 4096) fixes
+the pool the list is taken from.  Same output format, served order.  Not together with --sample, --diversity, the cap flags,
+--calibrate or --renormalize."""
 import argparse
 import sys
 
-from common import (DEFAULTS, build_model, calibrate_flags, cap_flags, catalog_flags, model_flags, read_calibration, read_caps,
-                    read_catalog, variant_flags)
+from common import (DEFAULTS, build_model, calibrate_flags, cap_flags, catalog_flags, model_flags, personal_flags,
+                    read_calibration, read_caps, read_catalog, read_personal, variant_flags)
 
 MAX_TOP = 128           # SREC_SELECT_MAXK (include/srec.h)
 MAX_CAP_POOL = 4096     # SREC_CAP_MAXP
@@ -110,10 +120,12 @@ def parser(model):
     p.add_argument('--pool', type=int, default=None, metavar='M',
                    help='--diversity: items per session the slate is picked from, --top <= M <= %d (default: min(%d, 4 * top)); '
                         '--categories: the pool the capped list is taken from, --top <= M <= %d (default: %d, then %d); '
-                        '--calibrate: as for --diversity'
-                        % (MAX_TOP, MAX_TOP, MAX_CAP_POOL, MAX_TOP, MAX_CAP_POOL))
+                        '--calibrate: as for --diversity; --hide / --session-bias: the pool the listed items are merged '
+                        'into, --top <= M <= %d (default: --top + the longest list)'
+                        % (MAX_TOP, MAX_TOP, MAX_CAP_POOL, MAX_TOP, MAX_CAP_POOL, MAX_CAP_POOL))
     cap_flags(p)
     calibrate_flags(p)
+    personal_flags(p)
     p.add_argument('--batch-size', type=int, default=DEFAULTS[model]['batch_size'], help='sessions per launch')
     p.add_argument('--output', default=None, help='write here instead of the standard output')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='operand precision of the encoder')
@@ -143,6 +155,16 @@ def parse(argv=None):
         p.error('--sample-top-p must be a probability mass in (0, 1)')
     if args.sample_min_p is not None and not 0.0 < args.sample_min_p <= 1.0:
         p.error('--sample-min-p must be in (0, 1]')
+    personal = args.hide is not None or args.session_bias is not None
+    if personal:
+        for flag, given in (('--sample', args.sample), ('--diversity', args.diversity is not None),
+                            ('--categories / --max-per-category / --category-caps',
+                             args.categories is not None or args.max_per_category is not None or args.category_caps is not None),
+                            ('--calibrate', args.calibrate is not None), ('--renormalize', args.renormalize)):
+            if given:
+                p.error('--hide / --session-bias merge per-session lists into the most probable items: not together with %s' % flag)
+        if args.pool is not None and not args.top <= args.pool <= MAX_CAP_POOL:
+            p.error('--pool must be between --top and %d' % MAX_CAP_POOL)
     if args.diversity is not None:
         if args.sample:
             p.error('--diversity re-ranks the most probable items and --sample draws them: give one of the two')
@@ -150,8 +172,8 @@ def parse(argv=None):
             p.error('--diversity must be finite and >= 0')
         if args.pool is not None and not args.top <= args.pool <= MAX_TOP:
             p.error('--pool must be between --top and %d' % MAX_TOP)
-    elif args.pool is not None and args.categories is None:
-        p.error('--pool goes with --diversity or --categories')
+    elif args.pool is not None and args.categories is None and not personal:
+        p.error('--pool goes with --diversity or --categories (or --hide / --session-bias)')
     if args.calibrate is not None:
         if args.sample:
             p.error('--calibrate re-ranks the most probable items and --sample draws them: give one of the two')
@@ -167,6 +189,13 @@ def parse(argv=None):
     args.calibration = read_calibration(p, args)
     args.caps = None if args.calibration is not None else read_caps(p, args)
     args.catalog = read_catalog(p, args)
+    args.personal = None
+    if personal:
+        try:
+            n_sessions = len(read_session_file(args.sessions))
+        except (OSError, ValueError) as e:
+            p.error('--sessions: %s' % e)
+        args.personal = read_personal(p, args, n_sessions)
     return args
 
 
@@ -206,7 +235,11 @@ def main(argv=None):
         for b in range(0, len(sessions), args.batch_size):
             inputs, _ = collate_fn([(s, 0) for s in sessions[b:b + args.batch_size]])
             n = len(sessions[b:b + args.batch_size])
-            if args.sample:
+            if args.personal is not None:
+                mine = {key: rows if rows is None or len(rows) == 1 else rows[b:b + n] for key, rows in args.personal.items()}
+                val, idx = model.recommend_personal(*[x.to(device) for x in inputs], k=args.top, pool=args.pool,
+                                                    exclude_seen=args.exclude_seen, item_bias=item_bias, **mine)
+            elif args.sample:
                 val, idx = model.sample(*[x.to(device) for x in inputs], k=args.top, temperature=args.temperature,
                                         seed=args.seed, session_keys=th.arange(b, b + n, dtype=th.int32),
                                         exclude_seen=args.exclude_seen, item_bias=item_bias, renormalize=args.renormalize,
