@@ -19,6 +19,7 @@
 #ifndef SREC_H
 #define SREC_H
 #include "srec_hg.h"
+#include "srec_ens.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -812,6 +813,41 @@ int srec_score_ahead(const void* served, const int* labels, const float* target,
 int srec_score_ahead_many_ws(int B, int V, int d, int C, int L, int M, long* bytes);
 int srec_score_ahead_many(const void* served, const int* items, const float* target, long ld_items, int M, const float* floor,
                           int among_targets, int* ahead, void* ws, void* stream);
+
+/* ---- serving and evaluation of ENSEMBLES: the served score over SEVERAL tables in one pass (ensemble.hip) ------------------
+ * A probability-averaged ensemble ("soft voting": p(v) = sum_m w_m p_m(v)) is the served score with one table, one width and
+ * one column scale PER COMPONENT; log w_m is folded into the member's offsets by the caller:
+ *   s[b,v]  = logsumexp_{c<C}( cs[c][v] * <sr[c][b], E[c][v]> + off[c,b] ),  off = off_in if v is in listed[b,:] under
+ *             SREC_LISTED_SCORE, else off_ex                                       (C == 1: s = z + off, no exp / log)
+ *   s'[b,v] = s[b,v] + bias[group[b] * ld_bias + v]
+ * `const void* desc` -> srec_served_multi (include/srec_ens.h, with SREC_ENS_MAXCOMP = 8; a HOST struct of DEVICE pointers,
+ * read during the call only).  Per component c < C
+ * (arrays of extent SREC_ENS_MAXCOMP; entries >= C are not read): sr[c] [B, d[c]] (row stride ld_sr[c]), E[c] [V, d[c]] (row
+ * stride ld_e[c]), cs[c] [V] or NULL (= 1), d[c].  Every other member means exactly what it means in srec_served: off_ex /
+ * off_in [C, B] (NULL = 0), listed [B, L] / L / listed_mode, id_lo, B, V, bias / ld_bias / group / G; ELIGIBLE is the rule
+ * stated there, unchanged.  Component c's raw dot product is the tile product of the single-table pass over (sr[c], E[c]),
+ * to the bit; with C == 1 both entry points return what srec_score_select / srec_score_ahead (floor == NULL) return, to the
+ * bit.  For C > 1 the components are folded in index order into a running (max, sum) pair, so the value may differ from
+ * srec_served's three-pass mixture in the last bits; a component at -INFINITY contributes nothing, all of them give -INFINITY.
+ * Limits: 1 <= C <= SREC_ENS_MAXCOMP; per component those of srec_served: d[c] % 4 == 0, 0 < d[c] <= 1024, sr[c] / E[c]
+ * aligned to 16 bytes, ld_sr[c] / ld_e[c] multiples of 4; 0 <= L <= 64; id_lo + V <= INT_MAX (srec_ens_select).  fp32 only;
+ * no floor, no noise, no row-sharded session tiles (id_lo serves a table shard as before).
+ * srec_ens_select: the contract of srec_score_select without `floor`: out_val [B, K] descending, out_idx [B, K] global ids,
+ *   ties towards the lower id, (-INFINITY, -1) once the eligible rows run out (K > V is legal), 1 <= K <= SREC_SELECT_MAXK;
+ *   a pure function of the inputs, no atomics.  ws: srec_ens_select_ws() bytes.
+ * srec_ens_ahead: the contract of srec_score_ahead without `floor`: ahead[b] = the number of eligible local rows v with
+ *   id_lo + v != labels[b] and (s' > target[b], or s' == target[b] and id_lo + v < labels[b]); labels[b] < 0 gives -1; target
+ *   is always the caller's; counts of disjoint row ranges add up; with (labels, target) = (out_idx[:, j], out_val[:, j]) of
+ *   srec_ens_select over the same operands, ahead[b] == j.  ahead is WRITTEN; integer atomics only.  ws: srec_ens_ahead_ws()
+ *   bytes (a token).
+ * Both return SREC_BAD_ARG for desc == NULL, then 0 and no launch for B <= 0.  Nonzero and no launch for every reason of
+ * srec_served (per component where the member is per component), for C out of range, for a NULL sr[c] or E[c] with c < C,
+ * and for the reasons of srec_score_select / srec_score_ahead beyond the descriptor.  The *_ws functions take shapes alone
+ * (d_max: the widest component). */
+int srec_ens_select_ws(int B, int V, int d_max, int C, int L, int K, long* bytes);
+int srec_ens_select(const void* desc, int K, float* out_val, int* out_idx, void* ws, void* stream);
+int srec_ens_ahead_ws(int B, int V, int d_max, int C, int L, long* bytes);
+int srec_ens_ahead(const void* desc, const int* labels, const float* target, int* ahead, void* ws, void* stream);
 
 /* ---- serving: diversified top-N - greedy MMR re-rank of a pool, and intra-list diversity (diversify.hip) ------------------
  * Per session a pool of M slots; slot i has a row index row[b * M + i] into the row source X (fp32, n_rows rows of d columns,

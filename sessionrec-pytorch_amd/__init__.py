@@ -10,3 +10,4 @@ from .batch import FlatBatch  # noqa: F401
 from .srgnn import NISER, SRGNN  # noqa: F401
 from .msgifsr import MSGIFSR  # noqa: F401
 from .lessr import LESSR  # noqa: F401
+from .ensemble import Ensemble  # noqa: F401

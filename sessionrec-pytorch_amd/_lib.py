@@ -86,6 +86,10 @@ def parse_structs(src=None):
 
 
 CONST, STRUCTS = parse_structs()
+# the descriptor of the multi-table served score has a header of its own (include/srec_ens.h, included by srec.h): bound from
+# there in the same way, beside CONST / STRUCTS, not among them
+ENS_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'srec_ens.h')
+ENS_CONST, ENS_STRUCTS = parse_structs(open(ENS_HEADER).read())
 
 
 class _Lib:

@@ -17,7 +17,7 @@ Re-exported from the modules imported at the end of this file (ops.X stays the w
             _bf16_dim_ok, _prepare_sr, _ce_fwd, _ce_bwd, _mixture_args, _byte_ws, _logp_cols, _pad_rows, BiasArgs, _bias_args,
             catalog_bias, diversify, diversify_scalars, cutoff_scalars, score_cutoff, cutoff_passes, select_many_k, score_select_many, score_ahead,
             score_ahead_many, ahead_among_targets, CapRule, cap_rule, cap_rule_check, cap_k, cap_select, calibrate, calibrate_scalars,
-            PersonalLists, personal_lists, personal_k, personal_merge
+            PersonalLists, personal_lists, personal_k, personal_merge, EnsArgs, _ens_args, ens_select, ens_ahead
   head.py   the attention read-out head: SegAttn, seg_attn, ReadoutHead, ReadoutHeadFused, readout_head, readout_head_fused,
             readout_head_fused_ok, head_path, head_wfrag, _head_wfrag_args, wfrag_missing, wfrag_put, HeadOrder, head_fwd_desc,
             head_bwd_desc, HEAD_FUSED_MAX_B
@@ -1667,7 +1667,7 @@ from .score import (  # noqa: E402,F401  (full-catalog scoring: score.py imports
     sample_noise, sample_scalars, score_sample, score_select, score_stats, score_topk, sr16_claim, sr16_written, use_bf16_scoring,
     cutoff_passes, cutoff_scalars, score_cutoff, select_many_k, score_select_many, score_ahead,
     score_ahead_many, ahead_among_targets, CapRule, cap_rule, cap_rule_check, cap_k, cap_select, calibrate, calibrate_scalars, _int_vector,
-    PersonalLists, personal_lists, personal_k, personal_merge)
+    PersonalLists, personal_lists, personal_k, personal_merge, EnsArgs, _ens_args, ens_select, ens_ahead)
 from .head import (  # noqa: E402,F401  (the attention read-out head: head.py imports this module and score.py)
     HEAD_FUSED_MAX_B, HeadOrder, ReadoutHead, ReadoutHeadFused, SegAttn, _head_wfrag_args, head_bwd_desc, head_fwd_desc, head_path,
     head_wfrag, readout_head, readout_head_fused, readout_head_fused_ok, seg_attn, wfrag_missing, wfrag_put)

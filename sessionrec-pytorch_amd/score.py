@@ -1,5 +1,5 @@
-"""Full-catalog scoring (csrc/score_ce*.hip, rank.hip, recommend.hip, select_many.hip, score_items.hip): the fused CE / statistics
-nodes, top-K, target rank, top-N select (and beyond 128 items), the scores of given items and the (B, V) log-probabilities, with the workspaces and argument conventions they share.
+"""Full-catalog scoring (csrc/score_ce*.hip, rank.hip, recommend.hip, select_many.hip, score_items.hip, ensemble.hip): the fused CE / statistics
+nodes, top-K, target rank, top-N select (and beyond 128 items), the scores of given items, the multi-table select / count of ensembles and the (B, V) log-probabilities, with the workspaces and argument conventions they share.
 ops.py keeps the GEMM wrappers and the tests' switches (reached through the module object at call time) and re-exports this."""
 import ctypes as _ct
 import numbers
@@ -8,7 +8,7 @@ from collections import namedtuple
 import torch
 
 from . import ops                    # (ops.py imports this module at its end: import the package or ops first, never score alone)
-from ._lib import CONST, STRUCTS, lib, ptr, stream
+from ._lib import CONST, ENS_CONST, ENS_STRUCTS, STRUCTS, lib, ptr, stream
 from .ops import _ld, _rows, gemm_nn, gemm_tn
 
 
@@ -1534,3 +1534,163 @@ def _pad_rows(t, n):
 
 def score_logp(sr, table, cs, ws, cs_inv_scale=1.0):
     return ScoreLogProb.apply(sr, table, cs, ws, cs_inv_scale)
+
+
+# ---- ensembles: the served score over several tables in one pass (csrc/ensemble.hip) ------------------------------------
+
+_ServedMulti = ENS_STRUCTS['srec_served_multi']    # bound from include/srec_ens.h (_lib.parse_structs), never retyped
+_ENS_MAXCOMP = ENS_CONST['SREC_ENS_MAXCOMP']
+_ENS_WS = {}           # the scratch of ens_select / ens_ahead: kinds 'ens_select', 'ens_ahead', beside _BYTE_WS, not in it
+_LISTED_TOO_MANY['ens_select'] = 'ens_select: %d listed items per session; csrc/ensemble.hip takes at most 64'
+_LISTED_TOO_MANY['ens_ahead'] = 'ens_ahead: %d listed items per session; csrc/ensemble.hip takes at most 64'
+
+
+class EnsArgs(namedtuple('EnsArgs', 'srs tables css ds C off_ex off_in listed L listed_mode id_lo B V bias ld_bias group G')):
+    """The operands of the multi-table served score as ens_select / ens_ahead launch with them: per component the session
+    vectors [B, d_c], the table [V, d_c] and the column scale (or None), then the shared members of srec_served_multi
+    (include/srec_ens.h) - the record owns what the pointers will name."""
+    __slots__ = ()
+
+    def struct(self):
+        """the host srec_served_multi of one library call (keep it, and this record, alive across the call).  ptr(): a CPU
+        tensor raises here, after every argument check"""
+        s = _ServedMulti()
+        for c in range(self.C):
+            s.sr[c], s.ld_sr[c] = ptr(self.srs[c]), _ld(self.srs[c])
+            s.E[c], s.ld_e[c] = ptr(self.tables[c]), _ld(self.tables[c])
+            s.cs[c], s.d[c] = ptr(self.css[c]), self.ds[c]
+        s.C = self.C
+        s.off_ex, s.off_in, s.listed, s.L = ptr(self.off_ex), ptr(self.off_in), ptr(self.listed), self.L
+        s.listed_mode, s.id_lo, s.B, s.V = self.listed_mode, self.id_lo, self.B, self.V
+        s.bias, s.ld_bias, s.group, s.G = ptr(self.bias), self.ld_bias, ptr(self.group), self.G
+        return s
+
+
+def _ens_args(who, comps, off_ex, off_in, listed, drop_listed, id_lo, bias, group):
+    """The argument conventions of ens_select / ens_ahead as one EnsArgs, errors (ValueError) in the words of `who`, naming the
+    offender.  comps: a sequence of 1 .. 8 (sr [B, d_c], table [V, d_c], cs [V] or None), all fp32 on one device, B and V
+    equal across the components, d_c % 4 == 0 and <= 1024; off_ex / off_in: [C, B] or None (= 0; off_in is ignored under
+    drop_listed); listed: [B, L] item ids, L <= 64, empty or None = no list; bias / group as _bias_args.  Pure torch (no
+    launch, no library call): it checks CPU tensors as well."""
+    try:
+        comps = [tuple(c) for c in comps]
+    except TypeError:
+        raise ValueError('%s: comps must be a sequence of (sr, table, cs) triples' % who) from None
+    C = len(comps)
+    if not 1 <= C <= _ENS_MAXCOMP:
+        raise ValueError('%s: %d components; csrc/ensemble.hip mixes between 1 and %d' % (who, C, _ENS_MAXCOMP))
+    srs, tables, css, ds = [], [], [], []
+    B = V = dev = None
+    for c, comp in enumerate(comps):
+        if len(comp) != 3:
+            raise ValueError('%s: component %d is not a (sr, table, cs) triple' % (who, c))
+        sr, table, cs = comp
+        for name, t, dims in (('sr', sr, 2), ('table', table, 2), ('cs', cs, 1)):
+            if t is None and name == 'cs':
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != dims:
+                raise ValueError('%s: component %d: %s must be a float32 tensor of %d dimensions, got %s' % (
+                    who, c, name, dims, '%s %s' % (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+            if dev is None:
+                dev = t.device
+            if t.device != dev:
+                raise ValueError('%s: component %d: %s is on %s, component 0 on %s' % (who, c, name, t.device, dev))
+        if B is None:
+            B, V = sr.shape[0], table.shape[0]
+        if sr.shape[0] != B:
+            raise ValueError('%s: component %d has %d sessions, component 0 has %d' % (who, c, sr.shape[0], B))
+        if table.shape[0] != V:
+            raise ValueError('%s: component %d scores %d items, component 0 scores %d' % (who, c, table.shape[0], V))
+        d = sr.shape[1]
+        if table.shape[1] != d:
+            raise ValueError('%s: component %d: sr has %d columns, its table %d' % (who, c, d, table.shape[1]))
+        if d < 4 or d % 4 or d > 1024:
+            raise ValueError('%s: component %d: width %d; csrc/ensemble.hip takes multiples of 4 up to 1024' % (who, c, d))
+        if cs is not None and cs.shape[0] != V:
+            raise ValueError('%s: component %d: cs has %d entries for %d items' % (who, c, cs.shape[0], V))
+        srs.append(_rows(sr.detach()))
+        tables.append(_rows(table.detach()))
+        css.append(None if cs is None else cs.detach().contiguous())
+        ds.append(d)
+
+    def offs(name, o):
+        if o is None:
+            return None
+        o = torch.as_tensor(o).detach()
+        if tuple(o.shape) != (C, B):
+            raise ValueError('%s: %s must be [%d, %d] (components, sessions), got %s' % (who, name, C, B, tuple(o.shape)))
+        if o.dtype != torch.float32 or o.device != dev:
+            raise ValueError('%s: %s must be float32 on %s, got %s on %s' % (who, name, dev, o.dtype, o.device))
+        return o.contiguous()
+    off_ex, off_in = offs('off_ex', off_ex), offs('off_in', None if drop_listed else off_in)
+    L = 0
+    if listed is not None and listed.numel() > 0:
+        if listed.is_floating_point() or listed.dim() != 2 or listed.shape[0] != B:
+            raise ValueError('%s: listed must hold [%d, L] integer item ids, got %s %s' % (who, B, listed.dtype, tuple(listed.shape)))
+        listed = listed.detach().to(torch.int32).contiguous()
+        L = listed.shape[1]
+        if L > _LISTED_MAX:
+            raise ValueError(_LISTED_TOO_MANY[who] % L)
+    else:
+        listed = None
+    mode = CONST['SREC_LISTED_DROP'] if drop_listed else CONST['SREC_LISTED_SCORE']
+    return EnsArgs(srs, tables, css, ds, C, off_ex, off_in, listed, L, mode, int(id_lo), B, V, *_bias_args(who, bias, group, B, V))
+
+
+def ens_select(comps, k, off_ex, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None):
+    """(values fp32 [B,k] descending, item ids int32 [B,k]): score_select over SEVERAL tables - the k best items per session
+    under s[b,v] = logsumexp_c(cs_c[v] <sr_c[b], E_c[v]> + off[c,b]) (+ bias[group[b], v]), every component with its own table,
+    width and column scale: the served score of a probability-averaged ensemble, log w_m folded into the member's offsets - no
+    (B, V) matrix per member, k <= 128 (csrc/ensemble.hip: one pass, the components folded into a running log-sum-exp).
+    comps: a sequence of 1 .. 8 (sr [B, d_c], table [V, d_c], cs [V] or None), fp32 on one device, equal B and V; off_ex /
+    off_in [C, B] or None (= 0); listed / drop_listed / id_lo / bias / group, ties, (-inf, -1) slots and eligibility as
+    score_select.  One component gives score_select's values and ids, bit for bit.  No floor, no sampling, no bf16; a wrong
+    argument raises ValueError before anything is launched (_ens_args).
+    Measured at B 512, V 37 484, d 256 (profiles/ensemble_timing.md): two single-soft-max members at k = 20
+    take 1 102 us against 1 406 us for one (B, V) log-prob matrix per component + logsumexp + topk, and 1 + 3 components 1 450
+    against 2 325 us (k = 100: 1 490 against 2 322 us); with two members at k = 100 this route LOSES to the materialised one
+    (1 700 against 1 409 us: torch.topk does not grow with k, the running lists do) - materialise there if memory allows."""
+    k = int(k)
+    if k < 1 or k > CONST['SREC_SELECT_MAXK']:
+        raise ValueError('ens_select: k = %d; the selection kernel of csrc/ensemble.hip keeps between 1 and %d items per '
+                         'session' % (k, CONST['SREC_SELECT_MAXK']))
+    a = _ens_args('ens_select', comps, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
+    B, dev = a.B, a.srs[0].device
+    val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    idx = torch.empty(B, k, device=dev, dtype=torch.int32)
+    if B == 0:
+        return val, idx
+    ws = _scratch('ens_select', dev, lib.srec_ens_select_ws, B, a.V, max(a.ds), a.C, a.L, k, cache=_ENS_WS)
+    desc = a.struct()
+    lib.srec_ens_select(_ct.addressof(desc), k, ptr(val), ptr(idx), ptr(ws), stream())
+    return val, idx
+
+
+def ens_ahead(comps, labels, target, off_ex, off_in=None, listed=None, drop_listed=False, id_lo=0, bias=None, group=None):
+    """int32 [B]: score_ahead over SEVERAL tables - the number of ELIGIBLE items that stand ahead of each session's label under
+    the score of ens_select (value above target[b], or equal to it with a lower id; the label is left out by id); -1 for a
+    session without a label (labels[b] < 0).  target: fp32 [B], the label's own value, always given by the caller
+    (Ensemble.score_items forms it).  With (labels, target) = (ids[:, j], values[:, j]) of ens_select over the same operands
+    the result is j.  Integer atomics: equal bits on every call; counts of disjoint row ranges (id_lo) add up.  Other arguments
+    as ens_select; no floor."""
+    a = _ens_args('ens_ahead', comps, off_ex, off_in, listed, drop_listed, id_lo, bias, group)
+    B, dev = a.B, a.srs[0].device
+    labels = torch.as_tensor(labels).detach()
+    if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool or labels.numel() != B:
+        raise ValueError('ens_ahead: labels must hold %d integer item ids (one per session), got %s %s'
+                         % (B, labels.dtype, tuple(labels.shape)))
+    target = torch.as_tensor(target).detach()
+    if not target.is_floating_point() or target.numel() != B:
+        raise ValueError('ens_ahead: target must hold %d floating numbers (the labels\' values), got %s %s'
+                         % (B, target.dtype, tuple(target.shape)))
+    if B == 0:
+        return torch.zeros(0, device=dev, dtype=torch.int32)
+    if labels.dtype != torch.int32:         # (an id beyond int32 stays beyond every local row: the kernel clamps around them)
+        labels = labels.to(torch.int64).clamp(min=-1, max=2 ** 31 - 1).to(torch.int32)
+    labels = labels.to(dev).reshape(B).contiguous()
+    target = target.to(device=dev, dtype=torch.float32).reshape(B).contiguous()
+    ws = _scratch('ens_ahead', dev, lib.srec_ens_ahead_ws, B, a.V, max(a.ds), a.C, a.L, cache=_ENS_WS)
+    out = torch.empty(B, device=dev, dtype=torch.int32)
+    desc = a.struct()
+    lib.srec_ens_ahead(_ct.addressof(desc), ptr(labels), ptr(target), ptr(out), ptr(ws), stream())
+    return out
